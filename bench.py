@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- dither+quantize throughput of the MI355X backend (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of the headline and prints its result line; --dump-outputs DIR then
+also writes what the last timed step computed (see dump_outputs).  Everything else -- the roofline and kernel timings of the
+headline, its known-answer check, C5, the pipes, the secondary lines and the CPU baseline -- runs only with --full
+(--no-extra / --no-cpu-baseline trim a --full run).
 
 Without a launcher (no WORLD_SIZE in the environment) and N > 1, this process starts the N ranks itself through
 torch.distributed.run BEFORE it touches the GPU, relays rank 0's JSON line and exits with the launcher's code.
@@ -13,7 +18,7 @@ Workload (config.workload = "C2"): Bayer 8x8 + 256-colour nearest-palette on 384
 already resident in HBM.  With N > 1 every rank runs the same batch on its own GPU (frames shard with no
 collective; weak scaling) and `value` is the whole-job pixel rate = N * pixels / max-over-ranks time.
 
-One JSON line is printed by rank 0.  `roofline` is for the dominant kernel (ordered pass 1), timed with
+One JSON line is printed by rank 0.  With --full, `roofline` is for the dominant kernel (ordered pass 1), timed with
 HIP events on its own stream inside the library (dp_profile_*); `cpu_baseline` is the CPU oracle
 (oracle/, the checker -- never the product path) on a bounded sample of the same workload.
 """
@@ -50,6 +55,28 @@ def make_frames(torch, n, h, w, dev, first_seed=None, numpy_frames=0, gen_seed=1
             kat = np.random.RandomState(first_seed + i).randint(0, 256, (h, w, 3), dtype=np.uint8)
             frames[i].copy_(torch.from_numpy(kat))
     return frames
+
+
+DUMP_SAMPLE_PX = 1 << 20
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(torch, out, path):
+    """What the headline's last timed step returned (out: [frames, H, W, 3] uint8 in HBM), as .npy files under `path`
+    (about 21 MB at the default 24 frames):
+      output_row_sums.npy        float64 [frames, H, 3]  sum of each row's bytes per channel (exact: every byte counts)
+      output_sample.npy          float32 [n, 3]          the RGB bytes of n = 2^20 pixels at fixed, seeded positions
+      output_sample_index.npy    float64 [n]             those positions as flat pixel indices (frame * H * W + y * W + x)"""
+    os.makedirs(path, exist_ok=True)
+    nf, h, w, _ = out.shape
+    total = nf * h * w
+    idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).randint(0, total, size=min(DUMP_SAMPLE_PX, total), dtype=np.int64))
+    flat = out.reshape(total, 3)
+    sample = flat.index_select(0, torch.from_numpy(idx).to(out.device)).cpu().numpy()
+    rows = torch.stack([out[f].sum(dim=1, dtype=torch.int64) for f in range(nf)]).cpu().numpy()   # (per frame: bounded temporaries)
+    np.save(os.path.join(path, "output_row_sums.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "output_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(path, "output_sample_index.npy"), idx.astype(np.float64))
 
 
 def kernel_sources_sha16():
@@ -117,7 +144,7 @@ def leg_traffic(result, name, pmc_leg=None):
 
 
 def rocprof_average_ms(kernel_substring, stats_name="r05_kernel_stats.csv"):
-    """AverageNs of a kernel in the committed rocprofv3 --kernel-trace --stats summary of `bench.py --no-extra --no-cpu-baseline`
+    """AverageNs of a kernel in the committed rocprofv3 --kernel-trace --stats summary of `bench.py --full --no-extra --no-cpu-baseline`
     (profiles/r05_kernel_stats.csv: every launch of the run, the slow first ones under the profiler included) -> ms, or None."""
     import csv
     path = os.path.join(ROOT, "profiles", stats_name)
@@ -380,8 +407,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=24, help="4K frames per batch (per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary 1080p / error-diffusion lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the headline's roofline and known-answer check, C5, the pipes, the secondary lines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the secondary 1080p / error-diffusion lines")
     ap.add_argument("--spawn", action="store_true", help="start the ranks through torch.distributed.run even for --gpus 1")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="(testing the N > 1 code path on a one-GPU box) every rank uses cuda:0 and the collectives run over "
@@ -496,22 +527,48 @@ def main():
     step()
     torch.cuda.synchronize()
     first_call_ms = (time.perf_counter() - t_acc) * 1e3
-    import hashlib
-    kat_ok = hashlib.sha256(out[0].cpu().numpy().tobytes()).hexdigest()[:16] == "7041bd52fdea90b5"
+    if args.full:
+        import hashlib
+        kat_ok = hashlib.sha256(out[0].cpu().numpy().tobytes()).hexdigest()[:16] == "7041bd52fdea90b5"
 
     # untimed: bring the GPU clocks up and fault in every buffer before the contract's W warm-up steps, so that a
     # short run (few steps) measures the same thing as a long one
     for _ in range(30):
         step()
     torch.cuda.synchronize()
-    backend.profile_enable(True)
+    if args.full:
+        backend.profile_enable(True)
     dt = timed(step, args.steps, args.warmup, per_step=True)
-    main_ms, fix_ms, launches = backend.profile_read()
-    backend.profile_enable(False)
+    if args.full:
+        main_ms, fix_ms, launches = backend.profile_read()
+        backend.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, out, args.dump_outputs)
     per_step = sorted(step_ms)
+    value = world * px_per_step * args.steps / dt / 1e6
+    result = {
+        "metric": "Mpixel/s dither+quantize @4K 256-color (Bayer 8x8 + nearest-palette, uint8 RGB in/out)",
+        "value": round(value, 1), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "ms_per_step_min": round(per_step[0], 4), "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
+        "rccl_world_size": dist.get_world_size() if distributed else 1,
+        **({"rehearsal": "all ranks on cuda:0, gloo collectives: code-path check only, the numbers mean nothing"}
+           if args.rehearse_on_one_gpu else {}),
+        "config": {"workload": "C2: Bayer 8x8 + 256-colour nearest palette palr(256,7), 3840x2160 RGB, "
+                               f"{args.frames} distinct frames rnd(2160,3840,1234+i) per GPU resident in HBM, frames sharded per rank",
+                   "frames_per_gpu": args.frames, "h": H4K, "w": W4K, "colors": 256, "matrix": "8x8",
+                   "parallelism": f"frames x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if distributed:
+            dist.destroy_process_group()
+        return
+
     # warm-up launches are in the record too: average per launch is what matters
     k_ms = main_ms / max(launches, 1)
-    value = world * px_per_step * args.steps / dt / 1e6
     achieved = BYTES_PER_PX * px_per_step / (k_ms * 1e-3) / 1e9
     # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so the figure
     # comes from the committed rocprofv3 --pmc pass of this same command (profiles/pmc_pass.sh)
@@ -531,19 +588,7 @@ def main():
                 traffic_src = f"profiles/{pmc_name} was taken with other kernel sources: not reported"
         except Exception:  # noqa: BLE001
             traffic = None
-    result = {
-        "metric": "Mpixel/s dither+quantize @4K 256-color (Bayer 8x8 + nearest-palette, uint8 RGB in/out)",
-        "value": round(value, 1), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "ms_per_step_min": round(per_step[0], 4), "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
-        "rccl_world_size": dist.get_world_size() if distributed else 1,
-        **({"rehearsal": "all ranks on cuda:0, gloo collectives: code-path check only, the numbers mean nothing"}
-           if args.rehearse_on_one_gpu else {}),
-        "config": {"workload": "C2: Bayer 8x8 + 256-colour nearest palette palr(256,7), 3840x2160 RGB, "
-                               f"{args.frames} distinct frames rnd(2160,3840,1234+i) per GPU resident in HBM, frames sharded per rank",
-                   "frames_per_gpu": args.frames, "h": H4K, "w": W4K, "colors": 256, "matrix": "8x8",
-                   "parallelism": f"frames x{world}"},
+    result.update({
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "ordered_lean_kernel<1,8> (main pass of dp_ordered_u8)", "kernel_ms": round(k_ms, 4),
@@ -551,7 +596,7 @@ def main():
                      "algorithmic_bytes_per_launch": BYTES_PER_PX * px_per_step},
         "parity_kat_4k": bool(kat_ok),
         "first_call_ms": round(first_call_ms, 2),
-    }
+    })
     # the same fraction from the committed rocprofv3 summary of this command (its average over ALL launches of the run, the slow
     # first ones included): the least favourable of the three ways to time the kernel, reported next to `frac`
     rp_ms = rocprof_average_ms("ordered_lean_kernel<1, 8, false, false, false>") if args.frames == 24 else None
@@ -567,7 +612,7 @@ def main():
             pass
         result["roofline"]["rocprof_avg_kernel_ms"] = round(rp_ms, 4)
         result["roofline"]["frac_rocprof_avg"] = round(BYTES_PER_PX * px_per_step / (rp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        result["roofline"]["frac_rocprof_avg_source"] = "profiles/r05_kernel_stats.csv (AverageNs of the kernel over every launch of `bench.py --no-extra --no-cpu-baseline` under rocprofv3 --kernel-trace --stats)"
+        result["roofline"]["frac_rocprof_avg_source"] = "profiles/r05_kernel_stats.csv (AverageNs of the kernel over every launch of `bench.py --full --no-extra --no-cpu-baseline` under rocprofv3 --kernel-trace --stats)"
     if valu_per_launch:
         # what actually bounds the kernel: wave64 VALU instructions of one launch (same PMC file) against
         # the issue rate of 1024 SIMDs, one instruction per 4 cycles, at the 2.4 GHz peak clock

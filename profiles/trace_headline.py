@@ -2,7 +2,7 @@
 """Per-launch durations of the headline kernel out of a rocprofv3 --kernel-trace directory.
 
 usage: profiles/trace_headline.py <rocprof outdir> <out.csv> [kernel-substring]
-bench.py --no-extra --no-cpu-baseline launches the kernel 1 (first call) + 30 (untimed clock ramp) + warmup + steps
+bench.py --full --no-extra --no-cpu-baseline launches the kernel 1 (first call) + 30 (untimed clock ramp) + warmup + steps
 times; the last warmup + steps launches are the region bench.py times.
 """
 import csv, glob, os, sys

@@ -615,3 +615,23 @@ def test_pil_image_from_the_staging_buffer_owns_its_pixels():
     out4[..., :3] = 0
     assert own.mode == "RGB" and np.array_equal(np.asarray(own), want)
     assert not np.array_equal(np.asarray(view)[..., :3], want)   # (a view: what apply_dithering must not return)
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.dump_outputs (what `bench.py --dump-outputs DIR` writes after the timed steps), on a small host tensor: exact
+    row sums of every frame, and the RGB bytes of seeded pixel positions, the same positions on every call."""
+    import torch
+    import bench
+    out = torch.from_numpy(np.random.RandomState(5).randint(0, 256, (3, 20, 30, 3), dtype=np.uint8))
+    bench.dump_outputs(torch, out, str(tmp_path / "a"))
+    bench.dump_outputs(torch, out, str(tmp_path / "b"))
+    rows = np.load(tmp_path / "a" / "output_row_sums.npy")
+    sample = np.load(tmp_path / "a" / "output_sample.npy")
+    index = np.load(tmp_path / "a" / "output_sample_index.npy")
+    assert rows.dtype == np.float64 and sample.dtype == np.float32 and index.dtype == np.float64
+    arr = out.numpy()
+    assert np.array_equal(rows, arr.sum(axis=2, dtype=np.int64).astype(np.float64))
+    assert index.shape == (3 * 20 * 30,) and index.min() >= 0 and index.max() < 3 * 20 * 30
+    assert np.array_equal(sample, arr.reshape(-1, 3)[index.astype(np.int64)].astype(np.float32))
+    for name in ("output_row_sums.npy", "output_sample.npy", "output_sample_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))

@@ -479,7 +479,7 @@ def test_bench_three_rank_rehearsal_uneven_shards():
     env = dict(os.environ)
     env.pop("DITHER_PIE_EXPERIMENTS", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--rehearse-on-one-gpu", "--steps", "2",
-                        "--warmup", "1", "--frames", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                        "--warmup", "1", "--frames", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                        timeout=1100, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -508,7 +508,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ)
     env.pop("DITHER_PIE_EXPERIMENTS", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2",
-                        "--warmup", "1", "--frames", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                        "--warmup", "1", "--frames", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -521,3 +521,43 @@ def test_bench_two_rank_rehearsal():
     assert "2 band(s)" in res["c4_kmeans_pass"]["workload"]
     assert "cpu_baseline" not in res
     assert res["roofline"]["frac"] > 0 and res["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(d, tmp_path):
+    """A plain bench.py run (no --full): one JSON line with the headline only, `steps` timed steps, and --dump-outputs
+    writing what the last timed step computed -- row sums of every frame and a seeded sample of pixels -- which must equal
+    the same batch dithered here."""
+    import subprocess
+    import sys
+    import torch
+    from conftest import ROOT
+    env = dict(os.environ)
+    env.pop("DITHER_PIE_EXPERIMENTS", None)
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--frames", "2", "--dump-outputs", str(dump)], capture_output=True, text=True, env=env,
+                       timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert res["unit"] == "Mpixel/s" and res["higher_is_better"] is True and res["dtype"] == "u8"
+    for key in ("roofline", "parity_kat_4k", "c5_video", "c5_pipes", "extra", "cpu_baseline"):
+        assert key not in res, key
+    rows = np.load(dump / "output_row_sums.npy")
+    sample = np.load(dump / "output_sample.npy")
+    index = np.load(dump / "output_sample_index.npy")
+    assert rows.dtype == np.float64 and rows.shape == (2, 2160, 3)
+    assert sample.dtype == np.float32 and sample.shape == (1 << 20, 3)
+    assert index.dtype == np.float64 and index.shape == (1 << 20,)
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+    import bench   # (the repository root is on sys.path: conftest.py)
+    dev = torch.device("cuda", 0)
+    frames = bench.make_frames(torch, 2, 2160, 3840, dev, first_seed=1234, numpy_frames=2)
+    out = d.ImageDitherer(256, d.DitherMode.BAYER, bench.palr(256), False, {"size": "8x8"}).apply_dithering_frames(frames)
+    want_rows = torch.stack([out[f].sum(dim=1, dtype=torch.int64) for f in range(2)]).cpu().numpy()
+    assert np.array_equal(rows, want_rows.astype(np.float64))
+    flat = out.reshape(-1, 3).cpu().numpy()
+    assert np.array_equal(sample, flat[index.astype(np.int64)].astype(np.float32))

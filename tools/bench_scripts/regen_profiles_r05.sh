@@ -16,11 +16,11 @@ timeout -k 10 300 bash profiles/pmc_pass_cmd4.sh $O/pmc_kpix python3 tools/bench
 timeout -k 10 300 bash profiles/pmc_pass_cmd4.sh $O/pmc_ed python3 tools/bench_scripts/ed_prof.py 16 256 && python3 profiles/pmc_summarise.py $O/pmc_ed $O/pmc_ed_summary.json ed_wavefront > /dev/null && rm -rf $O/pmc_ed/p? && echo "pmc ed done" && \
 timeout -k 10 300 bash profiles/pmc_pass_cmd4.sh $O/pmc_c5 python3 tools/bench_scripts/c5_prof.py 4 && python3 profiles/pmc_summarise.py $O/pmc_c5 $O/pmc_c5_summary.json ordered_ > /dev/null && rm -rf $O/pmc_c5/p? && echo "pmc c5 done"
 else
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --no-extra --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt.err && \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --no-extra --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt.err && \
 python3 profiles/trace_headline.py $O/kt $O/trace_headline.csv && \
 find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \; && find $O/kt -name "*kernel_trace.csv" -delete && \
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktfull -- python3 bench.py > $O/bench_full_under_rocprof.json 2> $O/ktfull.err && \
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktfull -- python3 bench.py --full > $O/bench_full_under_rocprof.json 2> $O/ktfull.err && \
 find $O/ktfull -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_full.csv \; && rm -rf $O/ktfull && \
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err && \
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err && \
 find $O -name "*.csv" -size +2M -delete && tail -c 400 $O/bench.json
 fi
