@@ -24,7 +24,7 @@ LIB_PATH = os.environ.get("DP_LIB_PATH") or (EXPERIMENTS_PATH if EXPERIMENTS els
 CSRC = os.path.join(_HERE, "csrc")
 # the ABI revision this binding was written against (include/ditherpie_hip.h: DP_ABI_VERSION); load() refuses a library
 # that reports another one -- a stale build bound through DP_LIB_PATH would otherwise read K as a pointer
-ABI_VERSION = 102
+ABI_VERSION = 103
 
 DP_OK, DP_EINVAL, DP_EUNSUPPORTED, DP_EHIP, DP_ENOMEM, DP_EWORKSPACE = range(6)
 DP_MAX_COLORS = 1024
@@ -67,6 +67,7 @@ _SIGS = {
     "dp_error_diffusion_numba_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _i, _vp, _sz, _vp]),
     "dp_hybrid_numba_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, C.c_double, C.c_double, _vp, _sz, _vp]),
     "dp_variable_diffusion_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dp_riemersma_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
     "dp_variance_gate_workspace_bytes": (_sz, [_i64, _i, _i]),
     "dp_variance_gate_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _f, _i, _vp, _sz, _vp]),
     "dp_kmeans_step_u8": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

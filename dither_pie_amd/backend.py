@@ -194,11 +194,12 @@ def _ws_keep():
 
 
 class _Launch:
-    """with _Launch(device, nbytes) as ws: ... -- the (device, stream) lock held, ws a scratch tensor of >= nbytes."""
+    """with _Launch(device, nbytes) as ws: ... -- the (device, stream) lock held, ws a scratch tensor of >= nbytes
+    (nbytes None: a call without workspace, only the lock; ws is None and the cached scratch is left as it is)."""
 
     def __init__(self, device, nbytes):
         self.key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        self.device, self.nbytes = device, max(int(nbytes), 1)
+        self.device, self.nbytes = device, None if nbytes is None else max(int(nbytes), 1)
 
     def __enter__(self):
         with _ws_guard:
@@ -216,6 +217,8 @@ class _Launch:
                     del _ws_cache[k]
         self.ent = ent
         ent[1].acquire()
+        if self.nbytes is None:
+            return None
         try:
             t = ent[0]
             if t is None or t.numel() < self.nbytes or t.numel() > _WS_SHRINK * max(self.nbytes, 1 << 20):
@@ -300,6 +303,19 @@ def hybrid_numba(frames, pal: Palette, lum_factor=1.0, col_factor=0.2, out=None)
     with torch.cuda.device(f.device), _Launch(f.device, ws_bytes) as ws:
         check(L.dp_hybrid_numba_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, float(lum_factor), float(col_factor),
                                    ws.data_ptr(), ws.numel(), _stream()))
+    return out.view(frames.shape)
+
+
+def riemersma(frames, pal: Palette, out=None):
+    """Riemersma dithering (RiemersmaDitherStrategy.dither, dithering_lib.py:812-841): error diffusion along the Hilbert curve
+    of the next power-of-two square, the reference's float32 arithmetic and KD-tree nearest; uint8 frames in HBM."""
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    _check_palette_device(pal, f)
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):   # (no workspace: the lock of the (device, stream) only)
+        check(L.dp_riemersma_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, _stream()))
     return out.view(frames.shape)
 
 

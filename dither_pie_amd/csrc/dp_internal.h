@@ -230,6 +230,7 @@ size_t variance_gate_ws_bytes(int64_t n_frames, int h, int w);
 int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal, int model,
                               float p0, float p1, int serpentine, const uint8_t *gate, const float *coef, void *ws,
                               hipStream_t s);
+int launch_riemersma(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal, hipStream_t s);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,
                           hipStream_t s);
 }  // namespace dp

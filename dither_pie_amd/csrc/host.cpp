@@ -734,6 +734,25 @@ int dp_variable_diffusion_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_
                                      gate_dev, coef_dev, workspace_dev, (hipStream_t)stream);
 }
 
+int dp_riemersma_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal, void *stream)
+{
+    if (!pal || n_frames < 0 || h < 0 || w < 0) {
+        set_error("dp_riemersma_u8: bad argument (NULL palette or negative size)");
+        return DP_EINVAL;
+    }
+    if (n_frames == 0 || h == 0 || w == 0) return DP_OK;  // nothing to do (pointers may be null)
+    if (!in_dev || !out_dev) {
+        set_error("dp_riemersma_u8: bad argument (NULL frame buffer)");
+        return DP_EINVAL;
+    }
+    try {   // (no exception may cross the C ABI)
+        return launch_riemersma(in_dev, out_dev, n_frames, h, w, snapshot(pal), (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        set_error("dp_riemersma_u8: %s", e.what());
+        return DP_ENOMEM;
+    }
+}
+
 size_t dp_variance_gate_workspace_bytes(int64_t n_frames, int h, int w)
 {
     if (n_frames < 0 || h < 0 || w < 0) return 0;

@@ -7,7 +7,7 @@ dither_pie_gui.py / video_processor.py.  Pixel work happens in libditherpie_hip.
 file is host plumbing only (palette preparation, parameter handling, tensor hand-off).  There is no
 CPU fallback: without the shared library or a HIP device the calls raise DitherPieError.
 
-In scope: none, bayer, blue_noise, IGN, error_diffusion, polka_dot, perceptual,
+In scope: none, bayer, blue_noise, IGN, error_diffusion, riemersma, polka_dot, perceptual,
 hybrid, adaptive_variance, ostromoukhov; k-means / uniform / median-cut palettes.  The other DitherMode members exist for configuration compatibility and raise
 NotImplementedError when used.
 
@@ -81,7 +81,7 @@ __all__ = [
     "BaseDitherStrategy", "ErrorDiffusionKernel", "NoDitherStrategy", "MatrixDitherStrategy",
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
-    "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "generate_blue_noise",
+    "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "generate_blue_noise",
 ]
 
 
@@ -119,7 +119,7 @@ class PaletteSource(Enum):
     FROM_FILE = "file"
 
 
-_OUT_OF_SCOPE = {DitherMode.RIEMERSMA, DitherMode.WAVELET, DitherMode.HALFTONE}
+_OUT_OF_SCOPE = {DitherMode.WAVELET, DitherMode.HALFTONE}
 # per-pixel independent given global coordinates: these shard by row bands / tiles (sharding.dither_band); the diffusers do not
 ORDERED_MODES = {DitherMode.NONE, DitherMode.BAYER, DitherMode.BLUE_NOISE, DitherMode.INTERLEAVED_GRADIENT_NOISE, DitherMode.POLKA_DOT}
 
@@ -859,6 +859,49 @@ class ColorReducer:
         return grid[:num_colors]
 
 
+# ------------------------------------------------------------------------------------- Riemersma
+def _hilbert_order(n: int) -> np.ndarray:
+    """The path of the Riemersma ditherer over an n x n square, n = 2^k (dithering_lib.py:771-805): int32 [n*n, 2] of
+    (row, col) = (y, x) per path index, where (x, y) comes from the reference's hilbert_xy level loop (evaluated here for all
+    indices at once)."""
+    bits = int(math.log2(n))
+    t = np.arange(n * n, dtype=np.int64)
+    x = np.zeros_like(t)
+    y = np.zeros_like(t)
+    for lvl in range(bits):
+        s = 1 << lvl
+        rx = 1 & (t >> 1)
+        ry = 1 & (t ^ rx)
+        flip = (ry == 0) & (rx == 1)
+        x = np.where(flip, s - 1 - x, x)
+        y = np.where(flip, s - 1 - y, y)
+        x, y = np.where(ry == 0, y, x), np.where(ry == 0, x, y)
+        x += s * rx
+        y += s * ry
+        t >>= 2
+    return np.stack([y, x], axis=1).astype(np.int32)
+
+
+def _next_power_of_two(x: int) -> int:
+    """Smallest power of two >= x; 1 for x <= 1 (dithering_lib.py:808-809)."""
+    return 1 << (int(x) - 1).bit_length() if x > 0 else 1
+
+
+class RiemersmaDitherStrategy(BaseDitherStrategy):
+    """Error diffusion along a Hilbert curve (dithering_lib.py:812-841): the in-image indices of the path over the next
+    power-of-two square each push their error into the next four path indices (7/16, 1/16, 5/16, 3/16).  No parameters."""
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("Riemersma dithering carries state along the whole path and cannot be tiled")
+        return backend.riemersma(frames, pal, out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+
 # ------------------------------------------------------------------------------------- ImageDitherer
 class ImageDitherer:
     """dithering_lib.py:1877-1992.  Plain attributes only, so instances pickle like the reference's
@@ -875,6 +918,7 @@ class ImageDitherer:
         DitherMode.HYBRID: HybridDitherStrategy,
         DitherMode.ADAPTIVE_VARIANCE: AdaptiveVarianceDitherStrategy,
         DitherMode.OSTROMOUKHOV: OstromoukhovDitherStrategy,
+        DitherMode.RIEMERSMA: RiemersmaDitherStrategy,
     }
 
     def __init__(self, num_colors: int = 16, dither_mode: Optional[DitherMode] = DitherMode.BAYER,
@@ -905,7 +949,7 @@ class ImageDitherer:
         if mode in _OUT_OF_SCOPE:
             raise NotImplementedError(
                 f"dither mode {mode.value!r} is outside the MI355X backend's scope "
-                "(none, bayer, blue_noise, IGN, polka_dot, error_diffusion, perceptual, hybrid, "
+                "(none, bayer, blue_noise, IGN, polka_dot, error_diffusion, riemersma, perceptual, hybrid, "
                 "adaptive_variance, ostromoukhov)")
         cls = self._STRATEGIES.get(mode)
         if cls is None:

@@ -51,8 +51,9 @@ extern "C" {
 /* 100: rounds 1-2.  101: dp_kmeans_step_u8 takes mean_dev (round 3).  102: round 4's surface (dp_distinct_first_u8,
  * dp_kmeans_hist_*, dp_hybrid_numba_u8, dp_error_diffusion_numba_u8 computing the float64 reading of the numba branch,
  * dp_error_diffusion_workspace_bytes at 6 words per column) and round 5's larger dp_kmeans_hist_workspace_bytes (whole
- * 32-byte sectors per scatter workgroup and cell) with the overflow word in the histogram's info block. */
-#define DP_ABI_VERSION 102
+ * 32-byte sectors per scatter workgroup and cell) with the overflow word in the histogram's info block.  103: dp_riemersma_u8
+ * (an addition; no existing argument list changed). */
+#define DP_ABI_VERSION 103
 
 #define DP_MODE_NEAREST 0 /* NoDitherStrategy                     dithering_lib.py:333-341 */
 #define DP_MODE_MATRIX 1  /* MatrixDitherStrategy (Bayer, blue)   dithering_lib.py:346-378 */
@@ -169,6 +170,17 @@ int dp_error_diffusion_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t
  * Parity status: restated in the CPU oracle (orc_hybrid_numba_u8) and in numpy; fixtures pending, NOT pinned (no numba here). */
 int dp_hybrid_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
                        double lum_factor, double col_factor, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Riemersma dithering: RiemersmaDitherStrategy.dither (dithering_lib.py:812-841) with its path helpers _hilbert_order and
+ * _next_power_of_two (:771-809).  Error diffusion along the Hilbert curve of the dim x dim square, dim = the next power of two
+ * of max(h, w): only path indices inside the image are visited, each pushes its float32 error into the next four path indices
+ * (7/16, 1/16, 5/16, 3/16; float32 product and add, clipped to [0, 255] after every add; indices outside the image neither
+ * send nor receive).  Nearest entry as scipy's KDTree.query(k=1) reports it (float64 distances, the tree's order on exact
+ * ties), output bytes = out_colors of the entry, as for every other mode.  Bit-identical to the reference.
+ *   in_dev/out_dev  n_frames x h x w x 3 uint8, distinct buffers (as for dp_error_diffusion_u8)
+ * No workspace: the path is computed on the fly.  An empty batch (n_frames, h or w 0) returns DP_OK; n_frames <= 2^31 - 1. */
+int dp_riemersma_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                    void *stream);
 
 /* variable-weight diffusers -------------------------------------------------------
  * Replaces the pure-Python branches of PerceptualDitherStrategy.dither (dithering_lib.py:1030-1066, model 1),
@@ -325,7 +337,7 @@ int dp_resize_nearest_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_fram
 
 /* measurement -----------------------------------------------------------------------------------
  * Per-thread kernel timing with HIP events recorded on the stream the kernels run on.  While
- * enabled, every dp_ordered_u8 / dp_error_diffusion_u8 / dp_kmeans_step_u8 launch made by the calling
+ * enabled, every dp_ordered_u8 / dp_error_diffusion_u8 / dp_riemersma_u8 / dp_kmeans_step_u8 launch made by the calling
  * thread is bracketed by events; dp_profile_read synchronises them, returns the summed milliseconds
  * of the main kernel (pass 1 for dp_ordered_u8) and of the fix-up pass, and the number of main-kernel
  * launches, then clears the record. */
