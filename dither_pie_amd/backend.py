@@ -319,6 +319,126 @@ def riemersma(frames, pal: Palette, out=None):
     return out.view(frames.shape)
 
 
+class HalftoneParams(C.Structure):
+    """struct dp_halftone_params (include/ditherpie_hip.h)."""
+    _fields_ = [("cell_size", C.c_double), ("cos_a", C.c_double), ("sin_a", C.c_double), ("exponent", C.c_double),
+                ("min_dot", C.c_double), ("max_dot", C.c_double), ("sharpness", C.c_double), ("exp_class", C.c_int32),
+                ("shape", C.c_int32), ("paper_idx", C.c_int32), ("reserved", C.c_int32), ("fix_idx_dev", C.c_void_p),
+                ("fix_thr_dev", C.c_void_p), ("n_fix", C.c_int64)]
+
+
+HT_EXP_IDENTITY, HT_EXP_SQRT, HT_EXP_SQUARE, HT_EXP_POW = 0, 1, 2, 3
+HT_SHAPES = {"circle": 0, "square": 1, "diamond": 2}   # any other name is a circle, as in the reference
+
+
+def halftone_params(pal_f32, cell_size=8, angle=45.0, dot_gain=1.0, min_dot_size=0.0, max_dot_size=1.0, shape="circle",
+                    sharpness=1.5):
+    """The host half of HalftoneDitherStrategy (dithering_lib.py:1598-1693), done once per call in numpy as the reference
+    does it: cos / sin of np.radians(angle), the exponent 1 / dot_gain and the path numpy's `**` takes for it, the paper
+    entry (first argmax of the float32 brightness of pal_f32).  ValueError where the reference would crash or compute NaN:
+    cell_size <= 0 or not finite, dot_gain <= 0 or not finite."""
+    cs, dg = float(cell_size), float(dot_gain)
+    if not (np.isfinite(cs) and cs > 0):
+        raise ValueError(f"halftone cell_size must be a finite number > 0, not {cell_size!r}")
+    if not (np.isfinite(dg) and dg > 0):
+        raise ValueError(f"halftone dot_gain must be a finite number > 0, not {dot_gain!r}")
+    a = np.radians(angle)
+    e = 1.0 / dot_gain
+    cls = {1.0: HT_EXP_IDENTITY, 0.5: HT_EXP_SQRT, 2.0: HT_EXP_SQUARE}.get(e, HT_EXP_POW)
+    pal = np.asarray(pal_f32, np.float32).reshape(-1, 3)
+    paper = int(np.argmax(0.299 * pal[:, 0] + 0.587 * pal[:, 1] + 0.114 * pal[:, 2]))
+    return HalftoneParams(cs, float(np.cos(a)), float(np.sin(a)), float(e), float(min_dot_size), float(max_dot_size),
+                          float(sharpness), cls, HT_SHAPES.get(shape, 0), paper, 0, None, None, 0)
+
+
+def halftone_thresholds_at(idx, w, P: HalftoneParams):
+    """float32 screen thresholds of pixels idx = y * w + x, by the reference's numpy expressions (dithering_lib.py:1661-1693)
+    applied to those pixels only: np.power for the pixels dp_halftone_pow_flags lists."""
+    idx = np.asarray(idx, np.int64)
+    y, x = idx // w, idx % w
+    cs = P.cell_size
+    xr = x * P.cos_a - y * P.sin_a
+    yr = x * P.sin_a + y * P.cos_a
+    dx = (xr % cs) / cs - 0.5
+    dy = (yr % cs) / cs - 0.5
+    if P.shape == 1:
+        dist, max_dist = np.maximum(np.abs(dx), np.abs(dy)), 0.5
+    elif P.shape == 2:
+        dist, max_dist = np.abs(dx) + np.abs(dy), 1.0
+    else:
+        dist, max_dist = np.sqrt(dx ** 2 + dy ** 2), 0.5
+    t = np.power(np.clip(dist / max_dist, 0.0, 1.0), P.exponent)
+    t = P.min_dot + t * (P.max_dot - P.min_dot)
+    if P.sharpness != 1.0:
+        t = 0.5 + (t - 0.5) * P.sharpness
+    return np.clip(t, 0.0, 1.0).astype(np.float32)
+
+
+_HT_FIXUPS = OrderedDict()   # (device, h, w, geometry) -> (sorted int32 pixel indices, float32 thresholds) on the device
+_HT_FIXUPS_CAP = 32
+_ht_guard = threading.Lock()
+
+
+def halftone_fixups(device, h, w, P: HalftoneParams):
+    """The pow class's fix-up list for an h x w frame (cached per geometry): the pixels dp_halftone_pow_flags lists, sorted,
+    with thresholds from halftone_thresholds_at.  One host round trip the first time a geometry is seen."""
+    key = (device.index, h, w, P.cell_size, P.cos_a, P.sin_a, P.exponent, P.min_dot, P.max_dot, P.sharpness, P.shape)
+    with _ht_guard:
+        hit = _HT_FIXUPS.get(key)
+        if hit is not None:
+            _HT_FIXUPS.move_to_end(key)
+            return hit
+    L = _lib.load()
+    count = torch.zeros(1, dtype=torch.int64, device=device)
+    cap = 1 << 16
+    while True:
+        idx = torch.empty(cap, dtype=torch.int32, device=device)
+        check(L.dp_halftone_pow_flags(h, w, C.byref(P), idx.data_ptr(), cap, count.data_ptr(), _stream()))
+        n = int(count.item())
+        if n <= cap:
+            break
+        cap = n
+    ids = np.sort(idx[:n].cpu().numpy())
+    thr = halftone_thresholds_at(ids, w, P)
+    hit = (torch.from_numpy(ids).to(device), torch.from_numpy(thr).to(device))
+    torch.cuda.current_stream(device).synchronize()   # the list is complete before any stream of any thread can be handed it
+    with _ht_guard:
+        _HT_FIXUPS[key] = hit
+        while len(_HT_FIXUPS) > _HT_FIXUPS_CAP:
+            _HT_FIXUPS.popitem(last=False)
+    return hit
+
+
+def halftone(frames, pal: Palette, params, out=None):
+    """Halftone dithering (HalftoneDitherStrategy.dither, dithering_lib.py:1498-1695) of uint8 frames in HBM; params: the
+    reference's parameter dict (cell_size, angle, dot_gain, min_dot_size, max_dot_size, shape, sharpness; missing ones take
+    the reference's defaults).  Frames are independent; no tiles."""
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    _check_palette_device(pal, f)
+    P = halftone_params(pal.pal_f32, **params)
+    if n == 0 or h == 0 or w == 0:
+        return out.view(frames.shape)
+    L = _lib.load()
+    with torch.cuda.device(f.device):
+        keep = None
+        if P.exp_class == HT_EXP_POW:
+            keep = halftone_fixups(f.device, h, w, P)
+            if keep[0].numel():
+                # the cache may drop the list (another thread, 32 newer geometries) while this launch is in flight: the
+                # allocator must not hand its memory out again before the launching stream is past it
+                stream = torch.cuda.current_stream(f.device)
+                keep[0].record_stream(stream)
+                keep[1].record_stream(stream)
+                P.fix_idx_dev, P.fix_thr_dev, P.n_fix = keep[0].data_ptr(), keep[1].data_ptr(), keep[0].numel()
+        ws_bytes = L.dp_halftone_workspace_bytes(n, h, w, C.byref(P))
+        with _Launch(f.device, max(ws_bytes, 1)) as ws:   # (0: a refused geometry; the call below says why)
+            check(L.dp_halftone_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, C.byref(P), ws.data_ptr(), ws.numel(),
+                                   _stream()))
+    return out.view(frames.shape)
+
+
 DIFFUSER_PERCEPTUAL, DIFFUSER_HYBRID, DIFFUSER_ADAPTIVE_VARIANCE, DIFFUSER_OSTROMOUKHOV = 1, 2, 3, 4
 
 

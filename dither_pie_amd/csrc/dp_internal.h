@@ -231,6 +231,11 @@ int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames,
                               float p0, float p1, int serpentine, const uint8_t *gate, const float *coef, void *ws,
                               hipStream_t s);
 int launch_riemersma(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal, hipStream_t s);
+size_t halftone_ws_bytes(int64_t n_frames, int h, int w, const dp_halftone_params &P);
+int launch_halftone(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal,
+                    const dp_halftone_params &P, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_halftone_pow_flags(int h, int w, const dp_halftone_params &P, int32_t *idx, int64_t cap,
+                              unsigned long long *count, hipStream_t s);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,
                           hipStream_t s);
 }  // namespace dp

@@ -753,6 +753,97 @@ int dp_riemersma_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, i
     }
 }
 
+// the parameter checks of the halftone entry points (nothing here touches the GPU); K < 0: the palette is not known
+static bool halftone_params_ok(const char *fn, const dp_halftone_params *P, int K)
+{
+    if (!P) {
+        set_error("%s: bad argument (NULL params)", fn);
+        return false;
+    }
+    if (!(std::isfinite(P->cell_size) && P->cell_size > 0.0)) {
+        set_error("%s: bad argument (cell_size must be finite and > 0)", fn);
+        return false;
+    }
+    if (!(std::isfinite(P->cos_a) && std::isfinite(P->sin_a) && std::isfinite(P->exponent) && std::isfinite(P->min_dot) &&
+          std::isfinite(P->max_dot) && std::isfinite(P->sharpness))) {
+        set_error("%s: bad argument (non-finite parameter)", fn);
+        return false;
+    }
+    if (P->exp_class < DP_HT_EXP_IDENTITY || P->exp_class > DP_HT_EXP_POW || P->shape < DP_HT_SHAPE_CIRCLE ||
+        P->shape > DP_HT_SHAPE_DIAMOND) {
+        set_error("%s: bad argument (unknown exponent class or shape)", fn);
+        return false;
+    }
+    if (K >= 0 && (P->paper_idx < 0 || P->paper_idx >= K)) {
+        set_error("%s: bad argument (paper_idx outside the palette)", fn);
+        return false;
+    }
+    if (P->reserved != 0) {
+        set_error("%s: bad argument (reserved must be 0)", fn);
+        return false;
+    }
+    if (P->n_fix < 0 || (P->n_fix > 0 && (!P->fix_idx_dev || !P->fix_thr_dev))) {
+        set_error("%s: bad argument (fix-up list: negative length or NULL pointers)", fn);
+        return false;
+    }
+    return true;
+}
+
+size_t dp_halftone_workspace_bytes(int64_t n_frames, int h, int w, const dp_halftone_params *params)
+{
+    if (n_frames < 0 || h < 0 || w < 0 || !halftone_params_ok("dp_halftone_workspace_bytes", params, -1)) return 0;
+    return halftone_ws_bytes(n_frames, h, w, *params);
+}
+
+int dp_halftone_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                   const dp_halftone_params *params, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    if (!pal || n_frames < 0 || h < 0 || w < 0) {
+        set_error("dp_halftone_u8: bad argument (NULL palette or negative size)");
+        return DP_EINVAL;
+    }
+    if (!halftone_params_ok("dp_halftone_u8", params, pal->dev.K)) return DP_EINVAL;
+    if (n_frames == 0 || h == 0 || w == 0) return DP_OK;  // nothing to do (pointers may be null)
+    if (!in_dev || !out_dev || !workspace_dev) {
+        set_error("dp_halftone_u8: bad argument (NULL frame buffer or workspace)");
+        return DP_EINVAL;
+    }
+    if (n_frames > 0x7fffffff) {
+        set_error("dp_halftone_u8: too many frames for one call");
+        return DP_EINVAL;
+    }
+    if ((int64_t)h * (int64_t)w > 0x7fffffff) {
+        set_error("dp_halftone_u8: more than 2^31 - 1 pixels per frame");
+        return DP_EUNSUPPORTED;
+    }
+    try {   // (no exception may cross the C ABI)
+        return launch_halftone(in_dev, out_dev, n_frames, h, w, snapshot(pal), *params, workspace_dev, workspace_bytes,
+                               (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        set_error("dp_halftone_u8: %s", e.what());
+        return DP_ENOMEM;
+    }
+}
+
+int dp_halftone_pow_flags(int h, int w, const dp_halftone_params *params, int32_t *idx_dev, int64_t cap,
+                          unsigned long long *count_dev, void *stream)
+{
+    if (h < 0 || w < 0 || cap < 0 || !count_dev || (cap > 0 && !idx_dev)) {
+        set_error("dp_halftone_pow_flags: bad argument (negative size or NULL buffer)");
+        return DP_EINVAL;
+    }
+    if (!halftone_params_ok("dp_halftone_pow_flags", params, -1)) return DP_EINVAL;
+    if ((int64_t)h * (int64_t)w > 0x7fffffff) {
+        set_error("dp_halftone_pow_flags: more than 2^31 - 1 pixels");
+        return DP_EUNSUPPORTED;
+    }
+    if (h == 0 || w == 0) {
+        DP_HIP(hipMemsetAsync(count_dev, 0, sizeof(unsigned long long), (hipStream_t)stream));
+        return DP_OK;
+    }
+    return launch_halftone_pow_flags(h, w, *params, idx_dev, cap, count_dev, (hipStream_t)stream);
+}
+
 size_t dp_variance_gate_workspace_bytes(int64_t n_frames, int h, int w)
 {
     if (n_frames < 0 || h < 0 || w < 0) return 0;

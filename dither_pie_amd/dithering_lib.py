@@ -81,7 +81,8 @@ __all__ = [
     "BaseDitherStrategy", "ErrorDiffusionKernel", "NoDitherStrategy", "MatrixDitherStrategy",
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
-    "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "generate_blue_noise",
+    "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
+    "generate_blue_noise",
 ]
 
 
@@ -900,6 +901,74 @@ class RiemersmaDitherStrategy(BaseDitherStrategy):
     def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
         out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
         return _decode(out, palette_arr)
+
+
+# ------------------------------------------------------------------------------------- Halftone
+class HalftoneDitherStrategy(BaseDitherStrategy):
+    """Newspaper-style halftone (dithering_lib.py:1498-1695): a screen of cells rotated by `angle`, each cell's mean colour
+    mapped to its nearest entry, a pixel inked with that entry when its darkness exceeds the screen threshold, the paper
+    (brightest) entry otherwise.  GPU kernels in halftone.hip; frames are independent, a frame cannot be tiled.
+
+    Drop-in for the reference's class (same constructor, metadata, dither() contract).  Not dispatched by ImageDitherer:
+    DitherMode.HALFTONE still raises NotImplementedError there; dither_frames() is the device-batch entry.  Divergence:
+    cell_size <= 0, a dot_gain that is not a finite number > 0, and an empty image raise ValueError at dither time (the
+    reference crashes or computes NaN-driven output)."""
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            'cell_size': {'type': 'int', 'default': 8, 'min': 2, 'max': 32, 'label': 'Cell Size',
+                          'description': 'Distance between dot centers (smaller = finer detail)'},
+            'angle': {'type': 'float', 'default': 45.0, 'min': 0.0, 'max': 90.0, 'label': 'Screen Angle',
+                      'description': 'Rotation angle in degrees (45\u00b0 is classic newspaper)'},
+            'dot_gain': {'type': 'float', 'default': 1.0, 'min': 0.5, 'max': 3.0, 'step': 0.1, 'label': 'Dot Gain',
+                         'description': 'Controls dot growth (1.0 = linear, higher = more contrast)'},
+            'min_dot_size': {'type': 'float', 'default': 0.0, 'min': 0.0, 'max': 0.5, 'step': 0.05, 'label': 'Min Dot Size',
+                             'description': 'Minimum dot threshold (0 = pure white possible)'},
+            'max_dot_size': {'type': 'float', 'default': 1.0, 'min': 0.5, 'max': 1.0, 'step': 0.05, 'label': 'Max Dot Size',
+                             'description': 'Maximum dot threshold (1.0 = pure black possible)'},
+            'shape': {'type': 'choice', 'default': 'circle', 'choices': ['circle', 'square', 'diamond'], 'label': 'Dot Shape',
+                      'description': 'Shape of halftone dots'},
+            'sharpness': {'type': 'float', 'default': 1.5, 'min': 0.5, 'max': 4.0, 'step': 0.1, 'label': 'Sharpness',
+                          'description': 'Edge sharpness (higher = crisper dots)'},
+        }
+
+    def __init__(self, cell_size: int = 8, angle: float = 45.0, dot_gain: float = 1.0, min_dot_size: float = 0.0,
+                 max_dot_size: float = 1.0, shape: str = "circle", sharpness: float = 1.5):
+        self.cell_size = cell_size
+        self.angle = angle
+        self.dot_gain = dot_gain
+        self.min_dot_size = min_dot_size
+        self.max_dot_size = max_dot_size
+        self.shape = shape
+        self.sharpness = sharpness
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'cell_size': self.cell_size, 'angle': self.angle, 'dot_gain': self.dot_gain,
+                'min_dot_size': self.min_dot_size, 'max_dot_size': self.max_dot_size, 'shape': self.shape,
+                'sharpness': self.sharpness}
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("halftone cells average over the whole image: a frame cannot be tiled")
+        return backend.halftone(frames, pal, self.get_current_parameters(), out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"halftone needs a non-empty image, not {h} x {w}")
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> halftoned uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(..., palette, use_gamma).apply_dithering would halftone it (palette: the reference's list of RGB
+        triples; use_gamma as there).  Frames stay in HBM."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, out=out)
 
 
 # ------------------------------------------------------------------------------------- ImageDitherer

@@ -52,7 +52,8 @@ extern "C" {
  * dp_kmeans_hist_*, dp_hybrid_numba_u8, dp_error_diffusion_numba_u8 computing the float64 reading of the numba branch,
  * dp_error_diffusion_workspace_bytes at 6 words per column) and round 5's larger dp_kmeans_hist_workspace_bytes (whole
  * 32-byte sectors per scatter workgroup and cell) with the overflow word in the histogram's info block.  103: dp_riemersma_u8
- * (an addition; no existing argument list changed). */
+ * (an addition; no existing argument list changed).  Still 103: dp_halftone_workspace_bytes, dp_halftone_u8 and
+ * dp_halftone_pow_flags with struct dp_halftone_params (additions; no existing argument list changed). */
 #define DP_ABI_VERSION 103
 
 #define DP_MODE_NEAREST 0 /* NoDitherStrategy                     dithering_lib.py:333-341 */
@@ -181,6 +182,74 @@ int dp_hybrid_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames
  * No workspace: the path is computed on the fly.  An empty batch (n_frames, h or w 0) returns DP_OK; n_frames <= 2^31 - 1. */
 int dp_riemersma_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
                     void *stream);
+
+/* Halftone dithering: HalftoneDitherStrategy.dither with _generate_halftone_screen_with_cells (dithering_lib.py:1498-1695).
+ * Per frame: every pixel is assigned to a cell of a screen rotated by `angle` (x_rot = x cos - y sin, y_rot = x sin + y cos;
+ * cell = floor(r / cell_size), offset by the minimum over the image, id = cy * max_x + cx), each cell's mean colour (exact
+ * integer channel sums / count, one float64 division) is mapped to the nearest entry as scipy's KDTree.query(k=1) reports
+ * it, and a pixel takes its cell's entry when its float32 darkness 1 - ((0.299 R + 0.587 G) + 0.114 B) / 255 exceeds the
+ * float32 screen threshold, the paper entry otherwise (:1614-1634).  The threshold is the reference's float64 chain
+ * (:1664-1693): numpy's floored remainder / cell_size - 0.5 per axis, distance by shape, normalised and clipped,
+ * ** exponent, min_dot + t * (max_dot - min_dot), 0.5 + (t - 0.5) * sharpness only when sharpness != 1.0, clipped, rounded
+ * to float32.  Input bytes go through lut_in, output bytes are out_colors of the entry, as for every other mode.
+ * Bit-identical to the reference; the pow class needs the caller's fix-up list (below).
+ *
+ * The caller does what the reference does once per call in numpy: cos_a = np.cos(np.radians(angle)), sin_a likewise;
+ * exponent = 1.0 / dot_gain and its class -- numpy's `**` takes a square root for 0.5, a square for 2.0 and the identity
+ * for 1.0, np.power otherwise; paper_idx = the first argmax of the palette's float32 brightness
+ * 0.299 R + 0.587 G + 0.114 B (:1609-1611).  The library computes the cell extremes from the four image corners (each
+ * rotated coordinate is monotone in x and in y under IEEE rounding). */
+#define DP_HT_EXP_IDENTITY 0 /* exponent 1.0 */
+#define DP_HT_EXP_SQRT 1     /* exponent 0.5: np.sqrt */
+#define DP_HT_EXP_SQUARE 2   /* exponent 2.0: np.square */
+#define DP_HT_EXP_POW 3      /* any other exponent: np.power (see dp_halftone_pow_flags) */
+#define DP_HT_SHAPE_CIRCLE 0 /* also any shape name the reference does not know */
+#define DP_HT_SHAPE_SQUARE 1
+#define DP_HT_SHAPE_DIAMOND 2
+typedef struct dp_halftone_params {
+    double cell_size;          /* > 0, finite (the reference's int or float) */
+    double cos_a, sin_a;       /* finite */
+    double exponent;           /* 1.0 / dot_gain, finite; read for DP_HT_EXP_POW only */
+    double min_dot, max_dot;   /* min_dot_size, max_dot_size, finite */
+    double sharpness;          /* finite */
+    int32_t exp_class;         /* DP_HT_EXP_* */
+    int32_t shape;             /* DP_HT_SHAPE_* */
+    int32_t paper_idx;         /* 0 .. K-1 */
+    int32_t reserved;          /* must be 0 (DP_EINVAL otherwise) */
+    /* DP_HT_EXP_POW: the float32 thresholds of the pixels dp_halftone_pow_flags lists, computed by the caller with np.power
+     * (device pow is not numpy's to the last bit).  fix_idx_dev: n_fix pixel indices y * w + x in ascending order;
+     * fix_thr_dev: their thresholds.  A listed pixel the device can decide keeps its own (equal) value; a flagged pixel
+     * that is not listed keeps the device's value.  n_fix 0: no list (pointers may be NULL). */
+    const int32_t *fix_idx_dev;
+    const float *fix_thr_dev;
+    int64_t n_fix;
+} dp_halftone_params;
+
+/* Workspace of dp_halftone_u8 for this batch and geometry: per cell four uint32 words (channel sums and count, then the
+ * chosen output colour) and one word of the exact-tie list, for as many frames as run at once (frames go in groups of
+ * <= 256 MB of cells, at least one).  0 for bad arguments or a geometry dp_halftone_u8 refuses. */
+size_t dp_halftone_workspace_bytes(int64_t n_frames, int h, int w, const dp_halftone_params *params);
+
+/*   in_dev/out_dev  n_frames x h x w x 3 uint8 (distinct buffers)
+ * Per group of frames: a cell pass (pixels of a 64 x 16 tile summed in LDS, then global atomics), a colour pass per
+ * occupied cell (float64 scan of the palette, scipy's traversal replay for exact ties in a pass of its own) and an ink
+ * pass per pixel.  Frames are independent; a frame cannot be split into tiles or bands (a cell's mean spans the image).
+ * Argument checks run before any HIP call: NULL palette / params / buffers, negative sizes, cell_size <= 0, a non-finite
+ * parameter, an unknown class or shape, paper_idx outside the palette, reserved != 0, a fix-up list without pointers ->
+ * DP_EINVAL.
+ * DP_EUNSUPPORTED: more than 2^31 - 1 cells (the reference's int32 ids) or a cell coordinate outside int32, or cells that
+ * could hold more than 16 843 009 pixels (uint32 sums).  An empty batch returns DP_OK; n_frames <= 2^31 - 1. */
+int dp_halftone_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                   const dp_halftone_params *params, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* DP_HT_EXP_POW: list the pixels of an h x w frame whose float32 threshold the device's pow cannot decide: the chain after
+ * pow, evaluated 64 float64 ulps below and above the device's value, rounds to two different float32 values (the chain
+ * is monotone, so equal ends prove the float32 result for any pow within that distance).  About one pixel in 10^6
+ * qualifies (more where sharpening cancels).  Writes up to `cap` pixel indices y * w + x in no particular order to
+ * idx_dev and the total count (which may exceed cap) to *count_dev (device memory, one 64-bit word).  The list depends on
+ * the geometry only; other classes list nothing. */
+int dp_halftone_pow_flags(int h, int w, const dp_halftone_params *params, int32_t *idx_dev, int64_t cap,
+                          unsigned long long *count_dev, void *stream);
 
 /* variable-weight diffusers -------------------------------------------------------
  * Replaces the pure-Python branches of PerceptualDitherStrategy.dither (dithering_lib.py:1030-1066, model 1),
