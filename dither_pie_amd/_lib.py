@@ -71,6 +71,9 @@ _SIGS = {
     "dp_halftone_workspace_bytes": (_sz, [_i64, _i, _i, _vp]),
     "dp_halftone_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dp_halftone_pow_flags": (_i, [_i, _i, _vp, _vp, _i64, _vp, _vp]),
+    "dp_wavelet_uniforms_needed": (_i64, [_i, _i, _i]),
+    "dp_wavelet_workspace_bytes": (_sz, [_i64, _i, _i, _vp]),
+    "dp_wavelet_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dp_variance_gate_workspace_bytes": (_sz, [_i64, _i, _i]),
     "dp_variance_gate_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _f, _i, _vp, _sz, _vp]),
     "dp_kmeans_step_u8": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -439,6 +439,83 @@ def halftone(frames, pal: Palette, params, out=None):
     return out.view(frames.shape)
 
 
+class WaveletParams(C.Structure):
+    """struct dp_wavelet_params (include/ditherpie_hip.h)."""
+    _fields_ = [("wavelet", C.c_int32), ("subband_quant", C.c_int32), ("uniforms_dev", C.c_void_p),
+                ("n_uniforms", C.c_int64)]
+
+
+WAVELETS = ("haar", "db1", "db2", "db4", "sym2", "sym4", "coif1", "bior1.3", "bior2.2")   # DP_WL_* order
+
+
+def wavelet_check(wavelet="haar", subband_quant=8, seed=42):
+    """(wavelet id, Q, seed) of WaveletDitherStrategy's parameters; ValueError for a wavelet outside the nine, a Q that is
+    not an int in [1, 2^31 - 1], a seed outside [0, 2^32) (numpy's RandomState refuses those too)."""
+    if wavelet not in WAVELETS:
+        raise ValueError(f"wavelet must be one of {', '.join(WAVELETS)}, not {wavelet!r}")
+    if isinstance(subband_quant, bool) or not isinstance(subband_quant, (int, np.integer)) or \
+            not 1 <= int(subband_quant) <= 0x7fffffff:
+        raise ValueError(f"subband_quant must be an int in [1, 2^31 - 1], not {subband_quant!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"wavelet seed must be an int in [0, 2^32), not {seed!r}")
+    return WAVELETS.index(wavelet), int(subband_quant), int(seed)
+
+
+_WL_STREAMS = OrderedDict()   # (device, seed, n) -> float64 uniforms on the device
+_WL_STREAMS_BYTES = 1 << 30   # the cache keeps at most this many bytes of streams (and always the newest one)
+_wl_guard = threading.Lock()
+
+
+def wavelet_stream(device, seed, n):
+    """RandomState(seed).random_sample(n) on `device` (float64), cached per (device, seed, n): generated with numpy on the
+    host -- its legacy MT19937 is the definition -- and uploaded the first time a geometry is seen."""
+    key = (device.index, int(seed), int(n))
+    with _wl_guard:
+        hit = _WL_STREAMS.get(key)
+        if hit is not None:
+            _WL_STREAMS.move_to_end(key)
+            return hit
+    u = np.random.RandomState(seed).random_sample(n)
+    hit = torch.from_numpy(u).to(device)
+    torch.cuda.current_stream(device).synchronize()   # complete before any stream of any thread can be handed it
+    with _wl_guard:
+        _WL_STREAMS[key] = hit
+        total = sum(t.numel() * 8 for t in _WL_STREAMS.values())
+        while len(_WL_STREAMS) > 1 and total > _WL_STREAMS_BYTES:
+            _, old = _WL_STREAMS.popitem(last=False)
+            total -= old.numel() * 8
+    return hit
+
+
+def wavelet(frames, pal: Palette, params, out=None):
+    """Wavelet dithering (WaveletDitherStrategy.dither, dithering_lib.py:846-941) of uint8 frames in HBM; params: the
+    reference's parameter dict (wavelet, subband_quant, seed; missing ones take the reference's defaults).  Every frame
+    uses the same random stream, as the reference's fresh RandomState(seed) per call does.  Frames are independent; no
+    tiles."""
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    _check_palette_device(pal, f)
+    wid, q, seed = wavelet_check(**params)
+    if n == 0 or h == 0 or w == 0:
+        return out.view(frames.shape)
+    L = _lib.load()
+    with torch.cuda.device(f.device):
+        need = L.dp_wavelet_uniforms_needed(h, w, wid)
+        if need < 0:
+            raise ValueError(f"wavelet: refused geometry {h} x {w}")
+        u = wavelet_stream(f.device, seed, need)
+        # the cache may drop the stream (another thread, newer geometries) while this launch is in flight: the allocator
+        # must not hand its memory out again before the launching stream is past it
+        u.record_stream(torch.cuda.current_stream(f.device))
+        P = WaveletParams(wid, q, u.data_ptr(), u.numel())
+        ws_bytes = L.dp_wavelet_workspace_bytes(n, h, w, C.byref(P))
+        with _Launch(f.device, max(ws_bytes, 1)) as ws:   # (0: a refused geometry; the call below says why)
+            check(L.dp_wavelet_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, C.byref(P), ws.data_ptr(), ws.numel(),
+                                  _stream()))
+    return out.view(frames.shape)
+
+
 DIFFUSER_PERCEPTUAL, DIFFUSER_HYBRID, DIFFUSER_ADAPTIVE_VARIANCE, DIFFUSER_OSTROMOUKHOV = 1, 2, 3, 4
 
 

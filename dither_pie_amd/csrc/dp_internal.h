@@ -236,6 +236,11 @@ int launch_halftone(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, in
                     const dp_halftone_params &P, void *ws, size_t ws_bytes, hipStream_t s);
 int launch_halftone_pow_flags(int h, int w, const dp_halftone_params &P, int32_t *idx, int64_t cap,
                               unsigned long long *count, hipStream_t s);
+int wavelet_filter_len(int wid);
+int64_t wavelet_uniforms_needed(int h, int w, int wid);
+size_t wavelet_ws_bytes(int64_t n_frames, int h, int w, int wid);
+int launch_wavelet(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal,
+                   const dp_wavelet_params &P, void *ws, size_t ws_bytes, hipStream_t s);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,
                           hipStream_t s);
 }  // namespace dp

@@ -844,6 +844,74 @@ int dp_halftone_pow_flags(int h, int w, const dp_halftone_params *params, int32_
     return launch_halftone_pow_flags(h, w, *params, idx_dev, cap, count_dev, (hipStream_t)stream);
 }
 
+// the parameter checks of the wavelet entry points (nothing here touches the GPU)
+static bool wavelet_params_ok(const char *fn, const dp_wavelet_params *P)
+{
+    if (!P) {
+        set_error("%s: bad argument (NULL params)", fn);
+        return false;
+    }
+    if (wavelet_filter_len(P->wavelet) == 0) {
+        set_error("%s: bad argument (unknown wavelet id %d)", fn, (int)P->wavelet);
+        return false;
+    }
+    if (P->subband_quant < 1) {
+        set_error("%s: bad argument (subband_quant must be >= 1)", fn);
+        return false;
+    }
+    return true;
+}
+
+int64_t dp_wavelet_uniforms_needed(int h, int w, int wavelet)
+{
+    if (h < 0 || w < 0 || wavelet_filter_len(wavelet) == 0) return -1;
+    if (h == 0 || w == 0) return 0;
+    return wavelet_uniforms_needed(h, w, wavelet);
+}
+
+size_t dp_wavelet_workspace_bytes(int64_t n_frames, int h, int w, const dp_wavelet_params *params)
+{
+    if (n_frames <= 0 || h <= 0 || w <= 0 || !params || wavelet_filter_len(params->wavelet) == 0) return 0;
+    if ((int64_t)h * (int64_t)w > 0x7fffffff) return 0;
+    return wavelet_ws_bytes(n_frames, h, w, params->wavelet);
+}
+
+int dp_wavelet_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                  const dp_wavelet_params *params, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    if (!pal || n_frames < 0 || h < 0 || w < 0) {
+        set_error("dp_wavelet_u8: bad argument (NULL palette or negative size)");
+        return DP_EINVAL;
+    }
+    if (!wavelet_params_ok("dp_wavelet_u8", params)) return DP_EINVAL;
+    if (n_frames == 0 || h == 0 || w == 0) return DP_OK;  // nothing to do (pointers may be null)
+    if (!in_dev || !out_dev || !workspace_dev) {
+        set_error("dp_wavelet_u8: bad argument (NULL frame buffer or workspace)");
+        return DP_EINVAL;
+    }
+    if (n_frames > 0x7fffffff) {
+        set_error("dp_wavelet_u8: too many frames for one call");
+        return DP_EINVAL;
+    }
+    if ((int64_t)h * (int64_t)w > 0x7fffffff) {
+        set_error("dp_wavelet_u8: more than 2^31 - 1 pixels per frame");
+        return DP_EUNSUPPORTED;
+    }
+    const int64_t need = wavelet_uniforms_needed(h, w, params->wavelet);
+    if (!params->uniforms_dev || params->n_uniforms < need) {
+        set_error("dp_wavelet_u8: bad argument (uniform stream of %lld values, %lld needed)", (long long)params->n_uniforms,
+                  (long long)need);
+        return DP_EINVAL;
+    }
+    try {   // (no exception may cross the C ABI)
+        return launch_wavelet(in_dev, out_dev, n_frames, h, w, snapshot(pal), *params, workspace_dev, workspace_bytes,
+                              (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        set_error("dp_wavelet_u8: %s", e.what());
+        return DP_ENOMEM;
+    }
+}
+
 size_t dp_variance_gate_workspace_bytes(int64_t n_frames, int h, int w)
 {
     if (n_frames < 0 || h < 0 || w < 0) return 0;

@@ -8,7 +8,8 @@ file is host plumbing only (palette preparation, parameter handling, tensor hand
 CPU fallback: without the shared library or a HIP device the calls raise DitherPieError.
 
 In scope: none, bayer, blue_noise, IGN, error_diffusion, riemersma, polka_dot, perceptual,
-hybrid, adaptive_variance, ostromoukhov; k-means / uniform / median-cut palettes.  The other DitherMode members exist for configuration compatibility and raise
+hybrid, adaptive_variance, ostromoukhov; k-means / uniform / median-cut palettes.  HalftoneDitherStrategy and
+WaveletDitherStrategy run on the GPU as classes (drop-ins for the reference's), not through ImageDitherer.  The other DitherMode members exist for configuration compatibility and raise
 NotImplementedError when used.
 
 Extras that the reference does not have (all optional): ImageDitherer.apply_dithering_frames() for
@@ -82,7 +83,7 @@ __all__ = [
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
-    "generate_blue_noise",
+    "WaveletDitherStrategy", "generate_blue_noise",
 ]
 
 
@@ -964,6 +965,65 @@ class HalftoneDitherStrategy(BaseDitherStrategy):
     def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
         """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> halftoned uint8 CUDA tensor of the same shape, each frame as
         ImageDitherer(..., palette, use_gamma).apply_dithering would halftone it (palette: the reference's list of RGB
+        triples; use_gamma as there).  Frames stay in HBM."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, out=out)
+
+
+# ------------------------------------------------------------------------------------- Wavelet
+class WaveletDitherStrategy(BaseDitherStrategy):
+    """Wavelet dithering (dithering_lib.py:846-941): per channel a one-level 2-D DWT (pywt.dwt2, 'symmetric'), each subband
+    quantised to subband_quant levels with uniform noise, the inverse DWT, crop and clip; then per pixel the nearest or the
+    second-nearest palette entry, chosen by a uniform threshold.  GPU kernels in wavelet.hip (the transforms restate
+    PyWavelets 1.x in float32 to the last bit; no pywt needed at run time); frames are independent, a frame cannot be
+    tiled.  The random stream (numpy's RandomState(seed)) is generated on the host once per geometry and kept on the
+    device.
+
+    Drop-in for the reference's class (same constructor, metadata, dither() contract).  Not dispatched by ImageDitherer:
+    DitherMode.WAVELET still raises NotImplementedError there; dither_frames() is the device-batch entry.  Divergences: a
+    wavelet outside the nine of the metadata, a subband_quant that is not an int in [1, 2^31 - 1], a seed outside
+    [0, 2^32) and an empty image raise ValueError at dither time (the reference needs pywt for other wavelets, or crashes)."""
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            'wavelet': {'type': 'choice', 'default': 'haar',
+                        'choices': ['haar', 'db1', 'db2', 'db4', 'sym2', 'sym4', 'coif1', 'bior1.3', 'bior2.2'],
+                        'label': 'Wavelet Type', 'description': 'Type of wavelet basis function'},
+            'subband_quant': {'type': 'int', 'default': 8, 'min': 2, 'max': 32, 'label': 'Subband Quantization',
+                              'description': 'Number of quantization levels for wavelet subbands'},
+            'seed': {'type': 'int', 'default': 42, 'min': 0, 'max': 9999, 'label': 'Random Seed',
+                     'description': 'Seed for random threshold generation (same seed = same output)'},
+        }
+
+    def __init__(self, wavelet: str = 'haar', subband_quant: int = 8, seed: int = 42):
+        self.wavelet = wavelet
+        self.subband_quant = subband_quant
+        self.seed = seed
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'wavelet': self.wavelet, 'subband_quant': self.subband_quant, 'seed': self.seed}
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("wavelet subbands are quantised over the whole image: a frame cannot be tiled")
+        return backend.wavelet(frames, pal, self.get_current_parameters(), out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        from . import backend
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"wavelet needs a non-empty image, not {h} x {w}")
+        backend.wavelet_check(**self.get_current_parameters())
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> dithered uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(..., palette, use_gamma).apply_dithering would dither it (palette: the reference's list of RGB
         triples; use_gamma as there).  Frames stay in HBM."""
         import torch
         with torch.cuda.device(frames_u8_cuda.device):

@@ -53,7 +53,8 @@ extern "C" {
  * dp_error_diffusion_workspace_bytes at 6 words per column) and round 5's larger dp_kmeans_hist_workspace_bytes (whole
  * 32-byte sectors per scatter workgroup and cell) with the overflow word in the histogram's info block.  103: dp_riemersma_u8
  * (an addition; no existing argument list changed).  Still 103: dp_halftone_workspace_bytes, dp_halftone_u8 and
- * dp_halftone_pow_flags with struct dp_halftone_params (additions; no existing argument list changed). */
+ * dp_halftone_pow_flags with struct dp_halftone_params (additions; no existing argument list changed).  Still 103:
+ * dp_wavelet_uniforms_needed, dp_wavelet_workspace_bytes and dp_wavelet_u8 with struct dp_wavelet_params (additions). */
 #define DP_ABI_VERSION 103
 
 #define DP_MODE_NEAREST 0 /* NoDitherStrategy                     dithering_lib.py:333-341 */
@@ -250,6 +251,55 @@ int dp_halftone_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, in
  * the geometry only; other classes list nothing. */
 int dp_halftone_pow_flags(int h, int w, const dp_halftone_params *params, int32_t *idx_dev, int64_t cap,
                           unsigned long long *count_dev, void *stream);
+
+/* Wavelet dithering: WaveletDitherStrategy.dither (dithering_lib.py:846-941).  Per frame and channel: pywt.dwt2 (mode
+ * 'symmetric', float32, axis 0 then axis 1) of the channel's float32 values (input bytes through lut_in); each subband in
+ * the order cA, cH, cV, cD quantised by _quant_subband -- unless its float32 min equals its max, when it is kept as it is
+ * and draws nothing -- with noise = float32 of the next uniforms of the stream; pywt.idwt2 (axis 1 then axis 0), crop to
+ * h x w, clip to [0, 255].  Then per pixel scipy's KDTree.query(k=2) in float64, factor = d0^2 / (d0^2 + d1^2) from the
+ * re-squared sqrt distances (0 when the sum is 0), and the nearest entry when factor <= the pixel's float64 uniform, the
+ * second-nearest otherwise; the uniforms of the pixels follow every subband draw of the frame, in pixel order.  Output
+ * bytes are out_colors of the entry.  Bit-identical to the reference (numpy 1.x scalar semantics, pywt 1.x filters and
+ * loop orders).
+ *
+ * The stream is the reference's RandomState(seed).random_sample, created afresh for every frame (so every frame of a
+ * geometry reads the same stream): the caller generates it (float64, in device memory) with at least
+ * dp_wavelet_uniforms_needed(h, w, wavelet) values. */
+#define DP_WL_HAAR 0
+#define DP_WL_DB1 1
+#define DP_WL_DB2 2
+#define DP_WL_DB4 3
+#define DP_WL_SYM2 4
+#define DP_WL_SYM4 5
+#define DP_WL_COIF1 6
+#define DP_WL_BIOR1_3 7
+#define DP_WL_BIOR2_2 8
+typedef struct dp_wavelet_params {
+    int32_t wavelet;                /* DP_WL_* (the filters are compiled into the library) */
+    int32_t subband_quant;          /* Q: 1 .. 2^31 - 1 */
+    const double *uniforms_dev;     /* the stream, n_uniforms values */
+    int64_t n_uniforms;             /* >= dp_wavelet_uniforms_needed(h, w, wavelet) */
+} dp_wavelet_params;
+
+/* Values of the stream one frame may read: 12 subbands of ((h + F - 1) / 2) x ((w + F - 1) / 2) and h * w thresholds
+ * (F: the filter length).  -1 for bad arguments. */
+int64_t dp_wavelet_uniforms_needed(int h, int w, int wavelet);
+
+/* Workspace of dp_wavelet_u8 for this batch and geometry: per frame a 256-byte head (subband extremes, tie count), six
+ * float32 planes of ((h + F - 1) / 2) x w, the 12 subbands and one word per pixel for the exact-tie list, for as many
+ * frames as run at once (groups of <= 512 MB, at least one frame).  0 for bad arguments. */
+size_t dp_wavelet_workspace_bytes(int64_t n_frames, int h, int w, const dp_wavelet_params *params);
+
+/*   in_dev/out_dev  n_frames x h x w x 3 uint8 (distinct buffers)
+ * Per group of frames: the axis-0 and axis-1 analysis (subband extremes by order-preserving integer atomics), the axis-1
+ * synthesis with the subbands quantised on load, and a per-pixel pass (axis-0 synthesis, clip, float64 two-nearest scan;
+ * exact distance ties replay scipy's traversal in a pass of its own).  Frames are independent; a frame cannot be split
+ * into tiles or bands (the subband extremes span the frame).
+ * Argument checks run before any HIP call: NULL palette / params / buffers / stream, negative sizes, an unknown wavelet,
+ * subband_quant < 1, a stream shorter than dp_wavelet_uniforms_needed -> DP_EINVAL.
+ * DP_EUNSUPPORTED: more than 2^31 - 1 pixels per frame.  An empty batch returns DP_OK. */
+int dp_wavelet_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                  const dp_wavelet_params *params, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* variable-weight diffusers -------------------------------------------------------
  * Replaces the pure-Python branches of PerceptualDitherStrategy.dither (dithering_lib.py:1030-1066, model 1),
