@@ -634,7 +634,7 @@ size_t dp_error_diffusion_workspace_bytes(int64_t n_frames, int h, int w)
 static int error_diffusion_common(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w,
                                   const dp_palette *pal, const int32_t *dx, const int32_t *dy, const float *wq,
                                   const double *wq64, int ntaps, int serpentine, void *workspace_dev, size_t workspace_bytes,
-                                  void *stream, const double *hybrid = nullptr);
+                                  void *stream, const char *fn, const double *hybrid = nullptr);
 
 int dp_error_diffusion_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w,
                           const dp_palette *pal, const int32_t *dx, const int32_t *dy, const float *wq,
@@ -642,7 +642,7 @@ int dp_error_diffusion_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_fra
                           void *stream)
 {
     return error_diffusion_common(in_dev, out_dev, n_frames, h, w, pal, dx, dy, wq, nullptr, ntaps, serpentine, workspace_dev,
-                                  workspace_bytes, stream);
+                                  workspace_bytes, stream, "dp_error_diffusion_u8");
 }
 
 int dp_error_diffusion_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w,
@@ -661,7 +661,7 @@ int dp_error_diffusion_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t
         wq[k] = (float)wq64[k];
     }
     return error_diffusion_common(in_dev, out_dev, n_frames, h, w, pal, dx, dy, wq, wq64, ntaps, serpentine, workspace_dev,
-                                  workspace_bytes, stream);
+                                  workspace_bytes, stream, "dp_error_diffusion_numba_u8");
 }
 
 int dp_hybrid_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
@@ -674,32 +674,30 @@ int dp_hybrid_numba_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames
     static const float wq[4] = {7.0f / 16.0f, 3.0f / 16.0f, 5.0f / 16.0f, 1.0f / 16.0f};
     const double hybrid[2] = {lum_factor, col_factor};
     return error_diffusion_common(in_dev, out_dev, n_frames, h, w, pal, dx, dy, wq, wq64, 4, 0, workspace_dev, workspace_bytes, stream,
-                                  hybrid);
+                                  "dp_hybrid_numba_u8", hybrid);
 }
 
 static int error_diffusion_common(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w,
                                   const dp_palette *pal, const int32_t *dx, const int32_t *dy, const float *wq,
                                   const double *wq64, int ntaps, int serpentine, void *workspace_dev, size_t workspace_bytes,
-                                  void *stream, const double *hybrid)
+                                  void *stream, const char *fn, const double *hybrid)
 {
     if (n_frames == 0 && pal && h >= 1 && w >= 1) return DP_OK;  // nothing to do (pointers may be null)
     if (!in_dev || !out_dev || !pal || n_frames < 0 || h < 1 || w < 1 || ntaps < 0 || ntaps > 16 ||
         (ntaps && (!dx || !dy || !wq))) {
-        set_error("dp_error_diffusion_u8: bad argument");
+        set_error("%s: bad argument", fn);
         return DP_EINVAL;
     }
     for (int k = 0; k < ntaps; ++k) {
         const bool forward = dy[k] > 0 || (dy[k] == 0 && dx[k] > 0);
         if (!forward || dy[k] > 2 || dx[k] < -2 || dx[k] > 2) {
-            set_error("dp_error_diffusion_u8: tap %d (dx=%d, dy=%d) is outside the supported causal window", k,
-                      dx[k], dy[k]);
+            set_error("%s: tap %d (dx=%d, dy=%d) is outside the supported causal window", fn, k, dx[k], dy[k]);
             return DP_EUNSUPPORTED;
         }
     }
     if (n_frames == 0) return DP_OK;
     if (!workspace_dev || workspace_bytes < dp_error_diffusion_workspace_bytes(n_frames, h, w)) {
-        set_error("dp_error_diffusion_u8: workspace too small (need %zu bytes)",
-                  dp_error_diffusion_workspace_bytes(n_frames, h, w));
+        set_error("%s: workspace too small (need %zu bytes)", fn, dp_error_diffusion_workspace_bytes(n_frames, h, w));
         return DP_EWORKSPACE;
     }
     const int rc_tab = ensure_ed_tables(pal);

@@ -2795,6 +2795,18 @@ int num_cus()
 
 static inline bool env_set(const char *name) { return exp_env(name) != nullptr; }
 
+// experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel family of every launch on stderr (tests that must know
+// which kernel a case reached); the product library compiles to nothing here
+static inline void trace_family(const char *family, bool aligned)
+{
+#ifdef DP_EXPERIMENTS
+    if (std::getenv("DP_ORDERED_TRACE")) fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d)\n", family, aligned ? 1 : 0);
+#else
+    (void)family;
+    (void)aligned;
+#endif
+}
+
 template <int MODE>
 int launch_cell(uint32_t grid, size_t lds, hipStream_t s, const uint8_t *in, uint8_t *out, unsigned long long *flags,
                 const Geo &g, const PalDev &pal, const ThrDev &thr, float sx, float sy, float sc, uint32_t n_tiles)
@@ -2876,6 +2888,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         unsigned long long *fl = flags;  // chunks run back to back on one stream: the bitmap is reused
         const bool integer = pal.is_integer != 0;
         int fix_mode;
+        const char *family = "brute";  // (trace_family: which pass-1 kernel this launch takes)
         ProfMark *pm = prof_begin(s);
         const bool int_thr_ok = thr.m != nullptr && thr.th_h * thr.th_w <= 256;
         // the table the lean kernels would stage: 4-entry blocks when the accelerator built them, else 8-entry blocks
@@ -2984,67 +2997,83 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
     } while (0)
             if (comp_ok && mode == DP_MODE_NEAREST) {
                 DP_COMP(0);
+                family = "compact";
                 rc = DP_OK;
                 fix_mode = 0;
             } else if (comp_ok && mode == DP_MODE_IGN) {
                 DP_COMP(3);
+                family = "compact";
                 rc = DP_OK;
                 fix_mode = 3;
             } else if (comp_ok && mode == DP_MODE_MATRIX && int_comp) {
                 DP_COMP(1);
+                family = "compact";
                 rc = DP_OK;
                 fix_mode = 2;
             } else if (comp_ok && mode == DP_MODE_MATRIX) {
                 DP_COMP(2);
+                family = "compact";
                 rc = DP_OK;
                 fix_mode = 2;
 #undef DP_COMP
 #undef DP_COMP_K
             } else if (fast_ok && mode == DP_MODE_NEAREST) {
                 DP_FAST(0);
+                family = "fast";
                 rc = DP_OK;
                 fix_mode = 0;
             } else if (fast_ok && mode == DP_MODE_IGN) {
                 DP_FAST(3);
+                family = "fast";
                 rc = DP_OK;
                 fix_mode = 3;
             } else if (fast_ok && mode == DP_MODE_MATRIX && int_fast) {
                 DP_FAST(1);
+                family = "fast";
                 rc = DP_OK;
                 fix_mode = 2;
             } else if (fast_ok && mode == DP_MODE_MATRIX && thr.fpad != nullptr) {
                 DP_FAST(2);
+                family = "fast";
                 rc = DP_OK;
                 fix_mode = 2;
 #undef DP_FAST
             } else if (lean_geo && mode == DP_MODE_NEAREST) {
                 DP_LEAN(0);
+                family = "lean";
                 rc = DP_OK;
                 fix_mode = 0;
             } else if (lean_geo && mode == DP_MODE_IGN) {
                 DP_LEAN(3);
+                family = "lean";
                 rc = DP_OK;
                 fix_mode = 3;
             } else if (lean_geo && mode == DP_MODE_MATRIX && int_lean) {
                 DP_LEAN(1);
+                family = "lean";
                 rc = DP_OK;
                 fix_mode = 2;
             } else if (lean_geo && mode == DP_MODE_MATRIX && thr.fpad != nullptr) {
                 DP_LEAN(2);
+                family = "lean";
                 rc = DP_OK;
                 fix_mode = 2;
 #undef DP_LEAN
 #undef DP_LEAN_K
             } else if (mode == DP_MODE_NEAREST) {
+                family = "cell";
                 rc = launch_cell<0>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
                 fix_mode = 0;
             } else if (mode == DP_MODE_IGN) {
+                family = "cell";
                 rc = launch_cell<3>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
                 fix_mode = 3;
             } else if (int_thr_ok) {
+                family = "cell";
                 rc = launch_cell<1>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
                 fix_mode = 2;
             } else {
+                family = "cell";
                 rc = launch_cell<2>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
                 fix_mode = 2;
             }
@@ -3067,6 +3096,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         if (cf_ok) hipLaunchKernelGGL((ordered_compact_float_kernel<M>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles); \
         else hipLaunchKernelGGL(ordered_lean_float_kernel<M>, dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles); \
     } while (0)
+            family = cf_ok ? "compact_float" : "lean_float";
             if (mode == DP_MODE_NEAREST) {
                 DP_LEANF(0);
                 fix_mode = 0;
@@ -3092,6 +3122,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
             fix_mode = 2;
         }
         DP_HIP(hipGetLastError());
+        trace_family(family, g.aligned);
         prof_mid(pm, s);
         // one resident workgroup per CU (the 96 KB LDS list admits no more): a persistent grid avoids queueing
         const uint32_t fgrid = std::min<uint32_t>((n_words + kBlock * 8 - 1) / (kBlock * 8), (uint32_t)num_cus());
