@@ -93,6 +93,17 @@ _SIGS = {
     "dp_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }
 EXPORTS = tuple(_SIGS)
+# include/ditherpie_hip_indexed.h: the indexed-output extension (index planes beside packed RGB).  A table of its own
+# because the suite pins EXPORTS to the functions of ditherpie_hip.h; load() resolves both.
+_SIGS_INDEXED = {
+    "dp_index_map_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "dp_index_map_destroy": (None, [_vp]),
+    "dp_index_map_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "dp_index_from_rgb_u8": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
+    "dp_rgb_from_index_u8": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
+    "dp_resize_nearest_plane_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+}
+EXPORTS_INDEXED = tuple(_SIGS_INDEXED)
 
 
 def build(force=False):
@@ -133,7 +144,7 @@ def load():
                 if got != ABI_VERSION:
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
-                for name, (res, args) in _SIGS.items():
+                for name, (res, args) in list(_SIGS.items()) + list(_SIGS_INDEXED.items()):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

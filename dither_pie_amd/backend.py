@@ -713,6 +713,135 @@ def resize_nearest(frames, oh, ow):
     return out if frames.dim() == 4 else out[0]
 
 
+# ------------------------------------------------------------------------------------- indexed output
+# include/ditherpie_hip_indexed.h.  A dithered frame holds only the K output colours of its palette; an index plane is
+# the same image at one (two) byte(s) per pixel.
+class IndexMap:
+    """dp_index_map: the colour -> index hash table and the index -> colour list of K <= 1024 uint8 RGB colours
+    (duplicates allowed: a colour's index is its LOWEST position).  Built on the host; the first launch uploads it to the
+    current device, where it then stays."""
+
+    def __init__(self, colors_u8):
+        self.colors = np.ascontiguousarray(colors_u8, dtype=np.uint8).reshape(-1, 3)
+        self.K = self.colors.shape[0]
+        self._h = C.c_void_p()
+        L = _lib.load()
+        self._destroy = L.dp_index_map_destroy
+        check(L.dp_index_map_create(_np_ptr(self.colors), self.K, C.byref(self._h)))
+        k, slots, probe = C.c_int(), C.c_int(), C.c_int()
+        check(L.dp_index_map_info(self._h, C.byref(k), C.byref(slots), C.byref(probe)))
+        self.slots, self.max_probe = slots.value, probe.value
+        self.index_bytes = 1 if self.K <= 256 else 2
+        self.device = None   # set by the first launch
+
+    def _on(self, device):
+        if self.device is None:
+            self.device = device
+        elif self.device != device:
+            raise ValueError(f"index map lives on {self.device}, data on {device}")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._destroy(h)
+            self._h = None
+
+
+_INDEX_DTYPES = {1: torch.uint8, 2: torch.int16}
+
+
+def _index_bytes(imap, index_bytes):
+    nb = imap.index_bytes if index_bytes is None else int(index_bytes)
+    if nb not in (1, 2):
+        raise ValueError(f"index_bytes must be 1 or 2, not {index_bytes!r}")
+    if nb == 1 and imap.K > 256:
+        raise ValueError(f"one-byte indices cannot hold {imap.K} colours")
+    return nb
+
+
+def _check_buffer(out, device, shape, dtype, what):
+    """As _check_out: a caller-supplied buffer must be exactly what the kernel writes before its pointer reaches one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype):
+        raise TypeError(f"{what} must be a CUDA {str(dtype).replace('torch.', '')} tensor")
+    if out.device != device:
+        raise ValueError(f"{what} is on {out.device}, the input on {device}")
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"{what} must be contiguous and hold exactly {n} elements")
+    return out.view(shape)
+
+
+def _counted(count, strict, what, fn):
+    if not strict:
+        return count
+    n = int(count.item())
+    if n:
+        raise DitherPieError(_lib.DP_EINVAL, f"{fn}: {n} {what}")
+    return None
+
+
+def to_indices(frames, imap: IndexMap, index_bytes=None, out=None, strict=True):
+    """uint8 CUDA RGB frames [...,3] -> index planes [...]: torch.uint8 for one-byte indices (K <= 256, the default
+    there), torch.int16 for two-byte ones (the default above 256, index_bytes=2 at any K; the values are < 1024, so the
+    signed type holds them as they are).  A pixel that equals no colour of the map gets index 0 and is counted:
+    strict=True reads the count back (one synchronisation) and raises DitherPieError naming it, and returns the planes;
+    strict=False returns (planes, count) with count an int64 CUDA tensor of one element, nothing read back."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8):
+        raise TypeError("frames must be a CUDA uint8 tensor")
+    if frames.dim() < 1 or frames.shape[-1] != 3:
+        raise ValueError("frames must be [...,3]")
+    nb = _index_bytes(imap, index_bytes)
+    f = frames.contiguous()
+    planes = _check_buffer(out, f.device, tuple(f.shape[:-1]), _INDEX_DTYPES[nb], "out")
+    imap._on(f.device)
+    count = torch.zeros(1, dtype=torch.int64, device=f.device)
+    with torch.cuda.device(f.device):
+        if f.numel():
+            check(_lib.load().dp_index_from_rgb_u8(f.data_ptr(), planes.data_ptr(), f.numel() // 3, imap._h, nb,
+                                                   count.data_ptr(), _stream()))
+    left = _counted(count, strict, "pixel(s) equal no colour of the index map", "to_indices")
+    return planes if strict else (planes, left)
+
+
+def from_indices(planes, imap: IndexMap, out=None, strict=True):
+    """Index planes [...] (torch.uint8 or torch.int16, as to_indices returns them) -> uint8 RGB frames [...,3].  An
+    index outside [0, K) is written as colour 0 and counted; strict as for to_indices."""
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dtype in (torch.uint8, torch.int16)):
+        raise TypeError("planes must be a CUDA uint8 or int16 tensor")
+    nb = 1 if planes.dtype == torch.uint8 else 2
+    _index_bytes(imap, nb)
+    p = planes.contiguous()
+    rgb = _check_buffer(out, p.device, tuple(p.shape) + (3,), torch.uint8, "out")
+    imap._on(p.device)
+    count = torch.zeros(1, dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        if p.numel():
+            check(_lib.load().dp_rgb_from_index_u8(p.data_ptr(), rgb.data_ptr(), p.numel(), imap._h, nb, count.data_ptr(),
+                                                   _stream()))
+    left = _counted(count, strict, "index value(s) outside the index map", "from_indices")
+    return rgb if strict else (rgb, left)
+
+
+def resize_nearest_plane(planes, oh, ow):
+    """NEAREST resize of index planes [N,H,W] or [H,W] (uint8 or int16) with Pillow's coordinates, as resize_nearest
+    does for RGB frames: decoding the resized plane equals resizing the decoded frames."""
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dtype in (torch.uint8, torch.int16)):
+        raise TypeError("planes must be a CUDA uint8 or int16 tensor")
+    if planes.dim() not in (2, 3):
+        raise ValueError("planes must be [N,H,W] or [H,W]")
+    p = (planes if planes.dim() == 3 else planes.unsqueeze(0)).contiguous()
+    n, h, w = p.shape
+    out = torch.empty((n, int(oh), int(ow)), dtype=p.dtype, device=p.device)
+    with torch.cuda.device(p.device):
+        check(_lib.load().dp_resize_nearest_plane_u8(p.data_ptr(), out.data_ptr(), n, h, w, int(oh), int(ow),
+                                                     p.element_size(), _stream()))
+    return out if planes.dim() == 3 else out[0]
+
+
 def profile_enable(on=True):
     check(_lib.load().dp_profile_enable(1 if on else 0))
 

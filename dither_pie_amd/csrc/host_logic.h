@@ -1397,4 +1397,95 @@ inline void median_cut_u32(uint32_t *cur, uint32_t *other, const size_t n, const
     median_cut_u32(other + half, cur + half, n - half, depth - 1, out, 1);
 }
 
+// ---- colour -> palette index map (indexed.hip, include/ditherpie_hip_indexed.h) ---------------------------------------
+// An open-addressing table the index kernels keep in LDS.  A colour c = r | g << 8 | b << 16 is hashed by
+// h = (c * mult) mod 2^24 with an odd mult, a BIJECTION of the 24-bit colours, so (home slot, rest) = (h >> rest_bits,
+// h & rest_mask) names the colour and a four-byte slot has room for the index beside it:
+//   bits 0..12   rest  (13 bits at 2048 slots, 12 at 4096)
+//   bits 13..15  disp  slots between the entry's home and where linear probing put it, 0..kIndexMapMaxProbe
+//   bits 16..25  index (the LOWEST j with C[j] == c: colours are inserted in index order, later duplicates are dropped)
+// 0xFFFFFFFF is an empty slot (disp 7 is never stored).  A reader at step d of its probe run compares the low 16 bits of
+// slot (home + d) mod slots with rest | d << 13: equal rest and equal disp mean equal home, hence equal h, hence the same
+// colour -- no second table, no false positive, and no need to stop at an empty slot: the run is bounded by the map's own
+// longest displacement, which the builder keeps <= kIndexMapMaxProbe by choosing mult.
+constexpr int kIndexMapMaxProbe = 6;        // the kernels are compiled for at most this displacement (7 probes)
+constexpr int kIndexMapMaxSlots = 4096;
+constexpr uint32_t kIndexMapEmpty = 0xFFFFFFFFu;
+
+struct IndexMapHost {
+    int K = 0;
+    int slots = 0;        // 2048 for K <= 512, 4096 above: the load never exceeds 1/4
+    int rest_bits = 0;    // 24 - log2(slots)
+    int max_probe = 0;    // longest displacement of any entry
+    uint32_t mult = 0;
+    std::vector<uint32_t> table;   // slots words
+    std::vector<uint32_t> colors;  // K: r | g << 8 | b << 16 (what an index decodes to)
+};
+
+inline uint32_t index_map_hash(const uint32_t c, const uint32_t mult) { return (c * mult) & 0xFFFFFFu; }
+
+// index of colour c, or -1 when no entry equals it: what the kernels compute, restated for the host
+inline int index_map_lookup(const IndexMapHost &m, const uint32_t c)
+{
+    const uint32_t h = index_map_hash(c, m.mult), home = h >> m.rest_bits, rest = h & ((1u << m.rest_bits) - 1u);
+    for (int d = 0; d <= m.max_probe; ++d) {
+        const uint32_t w = m.table[(home + (uint32_t)d) & (uint32_t)(m.slots - 1)];
+        if ((w & 0xFFFFu) == (rest | ((uint32_t)d << 13))) return (int)(w >> 16);
+    }
+    return -1;
+}
+
+// Fills `table` for one multiplier; returns the longest displacement, or -1 when an entry would need more than `limit`.
+inline int index_map_fill(const std::vector<uint32_t> &colors, const int slots, const int rest_bits, const uint32_t mult,
+                          const int limit, std::vector<uint32_t> &table)
+{
+    table.assign((size_t)slots, kIndexMapEmpty);
+    const uint32_t mask = (uint32_t)slots - 1u, rest_mask = (1u << rest_bits) - 1u;
+    int longest = 0;
+    for (size_t j = 0; j < colors.size(); ++j) {
+        const uint32_t h = index_map_hash(colors[j], mult), home = h >> rest_bits, rest = h & rest_mask;
+        int d = 0;
+        for (;; ++d) {
+            if (d > limit) return -1;
+            uint32_t &w = table[(home + (uint32_t)d) & mask];
+            if (w == kIndexMapEmpty) {
+                w = rest | ((uint32_t)d << 13) | ((uint32_t)j << 16);
+                break;
+            }
+            if ((w & 0xFFFFu) == (rest | ((uint32_t)d << 13))) break;   // the colour is there already, at a lower index
+        }
+        longest = std::max(longest, d);
+    }
+    return longest;
+}
+
+// colors_u8: K x 3 bytes, 1 <= K <= DP_MAX_COLORS (the caller checks).  Tries odd multipliers from a fixed sequence and
+// keeps the one with the shortest longest displacement (stopping early at <= 1); false when 4096 candidates all exceed
+// kIndexMapMaxProbe (at a load of <= 1/4 the first few candidates succeed on every list tried; the bound is what makes
+// the kernels' probe loop finite whatever the list).
+inline bool index_map_build(const uint8_t *colors_u8, const int K, IndexMapHost &m)
+{
+    m.K = K;
+    m.slots = K <= 512 ? 2048 : kIndexMapMaxSlots;
+    m.rest_bits = K <= 512 ? 13 : 12;
+    m.colors.resize((size_t)K);
+    for (int j = 0; j < K; ++j)
+        m.colors[(size_t)j] = (uint32_t)colors_u8[3 * j] | ((uint32_t)colors_u8[3 * j + 1] << 8) | ((uint32_t)colors_u8[3 * j + 2] << 16);
+    std::vector<uint32_t> trial;
+    int best = -1;
+    uint32_t seq = 0x9E3779B1u;
+    for (int t = 0; t < 4096; ++t) {
+        const uint32_t mult = ((seq >> 8) | 1u) & 0xFFFFFFu;
+        seq = seq * 1664525u + 1013904223u;
+        const int longest = index_map_fill(m.colors, m.slots, m.rest_bits, mult, best < 0 ? kIndexMapMaxProbe : best - 1, trial);
+        if (longest < 0) continue;
+        best = longest;
+        m.mult = mult;
+        m.max_probe = longest;
+        m.table.swap(trial);
+        if (best <= 1 || (t >= 15 && best <= 3)) break;
+    }
+    return best >= 0;
+}
+
 }  // namespace dp

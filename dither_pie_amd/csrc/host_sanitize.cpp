@@ -15,6 +15,10 @@
 //   host_xxx mediancut <rgb.u8> <n> <depth>   the replay of CPython's set order + the counting-sort median cut; prints the
 //                                     palette and the first 2000 entries of the order (compared with the interpreter's own
 //                                     set and with the Python cut by the test)
+//   host_xxx indexmap <lists.bin> <n>   the colour -> index hash tables of the indexed output (index_map_build): the file holds
+//                                     n records {int32 K, int32 Q, K x 3 colour bytes, Q x 3 query bytes}; per record prints
+//                                     the map's figures, the index index_map_lookup reports for each of the K colours
+//                                     and how many of the Q queries (absent colours, by the test's construction) it finds
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -426,13 +430,55 @@ static int run_mediancut(const char *path, long n, int depth)
     return 0;
 }
 
+// ---- index maps ----------------------------------------------------------------------------------------------------
+static int run_indexmap(const char *path, const int n_lists)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int l = 0; l < n_lists; ++l) {
+        int32_t head[2];
+        if (fread(head, sizeof(int32_t), 2, f) != 2 || head[0] < 1 || head[0] > DP_MAX_COLORS || head[1] < 0) {
+            fprintf(stderr, "bad record %d in %s\n", l, path);
+            return 2;
+        }
+        const int K = head[0], Q = head[1];
+        std::vector<uint8_t> colours((size_t)K * 3), queries((size_t)Q * 3 + 1);
+        if (fread(colours.data(), 3, (size_t)K, f) != (size_t)K || fread(queries.data(), 3, (size_t)Q, f) != (size_t)Q) {
+            fprintf(stderr, "short record %d in %s\n", l, path);
+            return 2;
+        }
+        IndexMapHost m;
+        if (!index_map_build(colours.data(), K, m)) {
+            printf("map %d K=%d failed\n", l, K);
+            continue;
+        }
+        int used = 0;
+        for (uint32_t w : m.table) used += w != kIndexMapEmpty;
+        printf("map %d K=%d slots=%d rest_bits=%d max_probe=%d bound=%d mult=%u used=%d\nidx", l, K, m.slots, m.rest_bits, m.max_probe,
+               kIndexMapMaxProbe, m.mult, used);
+        for (int j = 0; j < K; ++j) printf(" %d", index_map_lookup(m, m.colors[(size_t)j]));
+        int hits = 0;
+        for (int q = 0; q < Q; ++q) {
+            const uint8_t *c = queries.data() + 3 * (size_t)q;
+            hits += index_map_lookup(m, (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16)) >= 0;
+        }
+        printf("\nabsent_hits=%d of %d\n", hits, Q);
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
+    if (std::string(argv[1]) == "indexmap") return run_indexmap(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

@@ -267,6 +267,7 @@ class _LRU(OrderedDict):
 # device handles are process-local and never stored on the (picklable) ditherer objects
 _PALETTES = _LRU(32)
 _THRESHOLDS = _LRU(32)
+_INDEX_MAPS = _LRU(32)
 
 
 def drop_device_caches():
@@ -275,6 +276,8 @@ def drop_device_caches():
         _PALETTES.clear()
     with _THRESHOLDS._lock:
         _THRESHOLDS.clear()
+    with _INDEX_MAPS._lock:
+        _INDEX_MAPS.clear()
     OstromoukhovDitherStrategy._coef_cache.clear()
 
 
@@ -287,6 +290,22 @@ def _device_palette(pal_f32, out_colors, lut_in):
     from . import backend
     key = (_device_index(), pal_f32.tobytes(), out_colors.tobytes(), None if lut_in is None else lut_in.tobytes())
     return _PALETTES.get_or_make(key, lambda: backend.Palette(pal_f32, out_colors, lut_in))
+
+
+def _device_index_map(out_colors):
+    """The index map of a palette's output colours (backend.IndexMap), per device and colour list."""
+    from . import backend
+    key = (_device_index(), out_colors.tobytes())
+    return _INDEX_MAPS.get_or_make(key, lambda: backend.IndexMap(out_colors))
+
+
+def _indexed(frames_rgb, palette, use_gamma, out):
+    """Dithered RGB frames in HBM -> (index planes, palette_u8 [K,3]) on the frames' stream: the colours are the
+    out_colors prepare_palette yields, which is what every mode writes."""
+    from . import backend
+    out_colors = prepare_palette(palette, use_gamma)[1]
+    planes = backend.to_indices(frames_rgb, _device_index_map(out_colors), out=out)
+    return planes, out_colors.copy()
 
 
 def _device_thresholds_matrix(matrix):
@@ -971,6 +990,13 @@ class HalftoneDitherStrategy(BaseDitherStrategy):
             pal = _device_palette(*prepare_palette(palette, use_gamma))
             return self._run(frames_u8_cuda, pal, out=out)
 
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8 up to 256 colours, torch.int16 above."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
+
 
 # ------------------------------------------------------------------------------------- Wavelet
 class WaveletDitherStrategy(BaseDitherStrategy):
@@ -1029,6 +1055,13 @@ class WaveletDitherStrategy(BaseDitherStrategy):
         with torch.cuda.device(frames_u8_cuda.device):
             pal = _device_palette(*prepare_palette(palette, use_gamma))
             return self._run(frames_u8_cuda, pal, out=out)
+
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8 up to 256 colours, torch.int16 above."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
 
 
 # ------------------------------------------------------------------------------------- ImageDitherer
@@ -1113,6 +1146,49 @@ class ImageDitherer:
         with torch.cuda.device(frames.device):  # palette, thresholds and launches on the device that holds the frames
             pal = _device_palette(*prepare_palette(self.palette, self.use_gamma))
             return strategy._run(frames, pal, y0=y0, x0=x0, out=out)
+
+    def apply_dithering_frames_indexed(self, frames, y0: int = 0, x0: int = 0, out=None):
+        """apply_dithering_frames() as palette-index planes: uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> (planes [N,H,W]
+        (or [H,W]), palette_u8 [K,3] numpy) with palette_u8[planes] == apply_dithering_frames(frames).  One byte per
+        pixel (torch.uint8) up to 256 colours, two (torch.int16) above.  palette_u8 is the out_colors of
+        prepare_palette: under use_gamma the sRGB bytes the RGB output carries, so two entries may be equal; a pixel
+        then gets the lowest of the equal indices.  The dither and the index pass run on the same stream, frames stay
+        in HBM; `out` receives the planes."""
+        import torch
+        rgb = self.apply_dithering_frames(frames, y0=y0, x0=x0)
+        with torch.cuda.device(frames.device):
+            return _indexed(rgb, self.palette, self.use_gamma, out)
+
+    def apply_dithering_indexed(self, image):
+        """PIL image -> PIL 'P' image whose palette is the out_colors of this ditherer's palette and whose
+        convert("RGB") equals apply_dithering(image): what PNG-8 / GIF are saved from, without Pillow re-quantising an
+        image whose indices the GPU already knew.  Host-in as apply_dithering (Pillow's own four-byte layout into the
+        pinned buffer); the way back is one byte per pixel -- a 'P' image's own layout -- into a reused pinned buffer,
+        copied once into storage the image owns (the staging buffer is overwritten by the next call).  ValueError above
+        256 colours (a 'P' image holds 256 entries; apply_dithering_frames_indexed serves those)."""
+        import torch
+        from PIL import Image
+        rgb = image if image.mode == "RGB" else image.convert("RGB")
+        w, h = rgb.size
+        if self.palette is None:
+            self._ensure_palette(np.asarray(rgb))
+        if len(self.palette) > 256:
+            raise ValueError(f"a 'P' image holds at most 256 colours, the palette has {len(self.palette)}: "
+                             "use apply_dithering_frames_indexed")
+        pin_in, pin_out = _pinned_pair(h * w * 4)
+        if w > 0 and h > 0 and _pil_rgbx_into(rgb, pin_in.numpy()):
+            dev_in = pin_in.view(h, w, 4).cuda(non_blocking=True)[..., :3].contiguous()
+        else:
+            host_in = pin_in[:h * w * 3]
+            np.copyto(host_in.numpy(), np.frombuffer(rgb.tobytes(), dtype=np.uint8))
+            dev_in = host_in.view(h, w, 3).cuda(non_blocking=True)
+        planes, colours = self.apply_dithering_frames_indexed(dev_in)
+        host_out = pin_out[:h * w]
+        host_out.view(h, w).copy_(planes, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out = Image.frombytes("P", (w, h), host_out.numpy())   # (a copy into the image's own storage)
+        out.putpalette(colours.reshape(-1).tolist(), "RGB")
+        return out
 
     def prepare(self, device=None, accel=True):
         """Create the device-side palette now (and, with accel=True, its search accelerator: ~3.5 ms once) instead of on

@@ -30,7 +30,7 @@ from PIL import Image
 
 from .dithering_lib import ImageDitherer, PixelizeMethod
 
-__all__ = ["VideoProcessor", "pixelize_regular", "NeuralPixelizer", "process_frames"]
+__all__ = ["VideoProcessor", "pixelize_regular", "NeuralPixelizer", "process_frames", "process_frames_indexed"]
 
 
 def _even_dimensions(orig_w: int, orig_h: int, max_size: int) -> Tuple[int, int]:
@@ -106,6 +106,25 @@ def process_frames(frames, ditherer: ImageDitherer, pixelize_method: Optional[st
         nw, nh = _final_size(x.shape[2], x.shape[1], final_resize_multiplier)
         x = backend.resize_nearest(x, nh, nw)
     return x
+
+
+def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
+                           final_resize_multiplier: Optional[int] = None):
+    """process_frames() as palette-index planes: uint8 CUDA tensor [N,H,W,3] -> (planes [N,H',W'], palette_u8 [K,3]) with
+    palette_u8[planes] == process_frames(...).  The final up-scale runs on the index plane (the same NEAREST coordinates),
+    so the index pass looks up the small frames only."""
+    from . import backend
+    if pixelize_method in (PixelizeMethod.NEURAL.value, "neural"):
+        raise NotImplementedError("neural pixelization is outside the MI355X backend's scope")
+    x = frames
+    if pixelize_method in (PixelizeMethod.REGULAR.value, "regular"):
+        tw, th = _even_dimensions(x.shape[2], x.shape[1], max_size)
+        x = backend.resize_nearest(x, th, tw)
+    planes, colours = ditherer.apply_dithering_frames_indexed(x)
+    if final_resize_multiplier:
+        nw, nh = _final_size(planes.shape[2], planes.shape[1], final_resize_multiplier)
+        planes = backend.resize_nearest_plane(planes, nh, nw)
+    return planes, colours
 
 
 def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_method: Optional[str] = None,
