@@ -104,6 +104,17 @@ _SIGS_INDEXED = {
     "dp_resize_nearest_plane_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
 }
 EXPORTS_INDEXED = tuple(_SIGS_INDEXED)
+# include/ditherpie_hip_clip.h: clip-wide palettes (distinct colours over a stream of buffers, rank sample of a histogram);
+# a table of its own for the same reason.
+_SIGS_CLIP = {
+    "dp_distinct_stream_state_bytes": (_sz, []),
+    "dp_distinct_stream_workspace_bytes": (_sz, [_i64]),
+    "dp_distinct_stream_reset": (_i, [_vp, _vp, _vp]),
+    "dp_distinct_stream_add_u8": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dp_hist_sample_workspace_bytes": (_sz, []),
+    "dp_hist_sample_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+}
+EXPORTS_CLIP = tuple(_SIGS_CLIP)
 
 
 def build(force=False):
@@ -144,7 +155,7 @@ def load():
                 if got != ABI_VERSION:
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
-                for name, (res, args) in list(_SIGS.items()) + list(_SIGS_INDEXED.items()):
+                for name, (res, args) in list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items()):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -610,7 +610,61 @@ def distinct_first(px):
     return out[:k]
 
 
+class DistinctStream:
+    """The distinct colours of a STREAM of pixel buffers in order of first occurrence (dp_distinct_stream_*,
+    include/ditherpie_hip_clip.h): after any sequence of add() calls, colours() equals distinct_first() of the
+    concatenated buffers, however the stream was cut.  Resident state: a bitmap of one bit per colour (2 MiB), the list
+    (48 MiB: every colour there is) and its length.  Calls into one object are ordered on one stream: add(), colours() and
+    reset() run on the caller's current stream, and a caller that changes streams orders them itself."""
+
+    LIST_BYTES = 3 << 24
+
+    def __init__(self, device=None):
+        require_gpu()
+        dev = torch.device(device or "cuda")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        L = _lib.load()
+        self.state = torch.empty(L.dp_distinct_stream_state_bytes(), dtype=torch.uint8, device=dev)
+        self.list = torch.empty(self.LIST_BYTES, dtype=torch.uint8, device=dev)
+        self.count = torch.empty(1, dtype=torch.int64, device=dev)
+        self.reset()
+
+    @property
+    def device(self):
+        return self.state.device
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            check(_lib.load().dp_distinct_stream_reset(self.state.data_ptr(), self.count.data_ptr(), _stream()))
+        return self
+
+    def add(self, px):
+        if not (isinstance(px, torch.Tensor) and px.is_cuda and px.dtype == torch.uint8 and px.shape[-1] == 3):
+            raise TypeError("px must be a CUDA uint8 tensor [...,3]")
+        if px.device != self.device:
+            raise ValueError(f"the stream's state lives on {self.device}, pixels on {px.device}")
+        px = px.contiguous()
+        n = px.numel() // 3
+        if n == 0:
+            return self
+        L = _lib.load()
+        with torch.cuda.device(px.device), _Launch(px.device, L.dp_distinct_stream_workspace_bytes(n)) as ws:
+            check(L.dp_distinct_stream_add_u8(px.data_ptr(), n, self.state.data_ptr(), self.list.data_ptr(), self.count.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream()))
+        return self
+
+    def __len__(self):
+        return int(self.count.item())
+
+    def colours(self):
+        """-> uint8 tensor [n_distinct, 3] on the device (a view of the list: add() appends behind it, reset() reuses it).
+        One host synchronisation (the count)."""
+        return self.list[:3 * len(self)].view(-1, 3)
+
+
 KMEANS_HIST_MAX_K = 256   # dp_kmeans_hist_step: one thread per centre in the list build
+HIST_SAMPLE_MAX_RANKS = 16384   # dp_hist_sample_u8 (the sample limit of dp_kmeans_plusplus_u8)
 
 
 class ColourHistogram:
@@ -646,6 +700,33 @@ class ColourHistogram:
         dp_kmeans_hist_build_u8; add() refuses such totals up front, a direct caller of the C ABI must look)."""
         word = self.buf[(1 << 26) + 4 * 8193:(1 << 26) + 4 * 8194].view(torch.int32)
         return bool(int(word.item()) != 0)
+
+    def sample(self, ranks):
+        """The colours of the pixels with the zero-based `ranks` (int64, at most HIST_SAMPLE_MAX_RANKS of them; numpy array,
+        sequence or tensor) when the histogram's pixels are laid out in its own slot order, every colour repeated count
+        times (dp_hist_sample_u8) -> uint8 tensor [len(ranks), 3] on the device.  A sample of the colour multiset: it does
+        not depend on the order the pixels were added in.  ValueError when a rank is < 0 or >= the number of pixels (the
+        device counts them: one host synchronisation)."""
+        dev = self.buf.device
+        if isinstance(ranks, torch.Tensor):
+            r = ranks.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        else:
+            r = torch.from_numpy(np.ascontiguousarray(np.asarray(ranks, dtype=np.int64).reshape(-1))).to(dev)
+        n = r.numel()
+        if n > HIST_SAMPLE_MAX_RANKS:
+            raise ValueError(f"at most {HIST_SAMPLE_MAX_RANKS} ranks per call, not {n}")
+        out = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        L = _lib.load()
+        with torch.cuda.device(dev), _Launch(dev, L.dp_hist_sample_workspace_bytes()) as ws:
+            check(L.dp_hist_sample_u8(self.buf.data_ptr(), r.data_ptr(), n, out.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream()))
+            n_bad = int(bad.item())
+        if n_bad:
+            raise ValueError(f"{n_bad} of {n} ranks lie outside [0, {self.n}): the histogram holds {self.n} pixels")
+        return out
 
     def step_into(self, centers, totals, want_sq=True, mean=None):
         """One Lloyd pass over the histogram into the planar totals buffer (see kmeans_step_into)."""

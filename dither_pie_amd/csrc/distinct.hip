@@ -14,6 +14,16 @@
 //                        ballot words (no second look at the table).
 // 3 B/pixel read three times + two random 4-byte table accesses per pixel; bit-exact by construction (integers, min is
 // order-independent).
+//
+// The same passes over a STREAM of buffers (dp_distinct_stream_add_u8, include/ditherpie_hip_clip.h; the kernels' STREAM
+// instances): a caller-kept bitmap of one bit per colour (2 MiB) says which colours an earlier buffer has emitted already.
+//   first_index_kernel   a pixel whose bit is set drops out before the LDS table (one 4-byte bitmap read per run of one
+//                        colour in a lane): a buffer without new colours sends no atomic to the 64 MB table at all.
+//   first_flags_kernel   first occurrence iff the bit is clear AND first[colour] == i; the table is read for clear bits only.
+//   block_scan_kernel    the list's length so far becomes the emit base (kept in the workspace), the total is ADDED to it.
+//   emit_kernel          appends at that base and sets the bit of every colour it writes (agent-scope atomic OR; nothing
+//                        reads the bitmap before the next call on the stream).
+// Nothing depends on how much of the bitmap stays in L2: it is read through plain loads and is correct from HBM.
 #include <algorithm>
 
 #include "dp_internal.h"
@@ -23,6 +33,7 @@ namespace dp {
 namespace {
 
 constexpr size_t kFirstTableBytes = (size_t)4 << 24;
+constexpr size_t kSeenBytes = (size_t)1 << 21;   // the stream form's "seen" set: one bit per colour
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kBlockPx = 2048;  // pixels per compaction block (one wave, 8 rounds of 256)
 
@@ -49,7 +60,11 @@ constexpr int kFB = 256;
 constexpr int kFSlots = 4096;
 constexpr int kFMaxWindow = 16;
 
-__global__ __launch_bounds__(kFB) void first_index_kernel(const uint8_t *__restrict__ px, const int64_t n, uint32_t *__restrict__ first)
+__device__ __forceinline__ bool seen_bit(const uint32_t *__restrict__ seen, const uint32_t colour) { return (seen[colour >> 5] >> (colour & 31u)) & 1u; }
+
+template <bool STREAM>
+__global__ __launch_bounds__(kFB) void first_index_kernel(const uint8_t *__restrict__ px, const int64_t n, uint32_t *__restrict__ first,
+                                                          const uint32_t *__restrict__ seen)
 {
     __shared__ uint32_t s_key[kFSlots];
     __shared__ uint32_t s_min[kFSlots];
@@ -64,6 +79,9 @@ __global__ __launch_bounds__(kFB) void first_index_kernel(const uint8_t *__restr
     const bool aligned = ((uintptr_t)px & 3) == 0;
     int window = 1, in_window = 0;
     auto insert = [&](const uint32_t colour, const uint32_t idx) {
+        if constexpr (STREAM) {
+            if (seen_bit(seen, colour)) return;
+        }
         uint32_t slot = (colour * 0x9E3779B1u) >> 20;
 #pragma unroll 1
         for (int probe = 0; probe < 8; ++probe) {
@@ -123,8 +141,10 @@ __global__ __launch_bounds__(kFB) void first_index_kernel(const uint8_t *__restr
 }
 
 // one wave per block of kBlockPx pixels; flags: [block][round 0..7][q 0..3] 64-bit ballots (bit = lane), pixel = 256 round + 4 lane + q
+template <bool STREAM>
 __global__ __launch_bounds__(64) void first_flags_kernel(const uint8_t *__restrict__ px, const int64_t n, const uint32_t *__restrict__ first,
-                                                         unsigned long long *__restrict__ flags, uint32_t *__restrict__ block_counts)
+                                                         unsigned long long *__restrict__ flags, uint32_t *__restrict__ block_counts,
+                                                         const uint32_t *__restrict__ seen)
 {
     const int lane = threadIdx.x;
     const bool aligned = ((uintptr_t)px & 3) == 0;
@@ -138,7 +158,11 @@ __global__ __launch_bounds__(64) void first_flags_kernel(const uint8_t *__restri
         load4(px, n, gi, aligned, c, cnt);
         uint32_t f[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) f[q] = q < cnt ? first[c[q]] : kNone - 1u;
+        for (int q = 0; q < 4; ++q) {
+            bool look = q < cnt;
+            if constexpr (STREAM) look = look && !seen_bit(seen, c[q]);
+            f[q] = look ? first[c[q]] : kNone - 1u;   // (no pixel index equals kNone - 1: n < 2^32 - 16)
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned long long m = __ballot(q < cnt && f[q] == (uint32_t)(gi * 4 + q));
@@ -149,7 +173,10 @@ __global__ __launch_bounds__(64) void first_flags_kernel(const uint8_t *__restri
     if (lane == 0) block_counts[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(1024) void block_scan_kernel(uint32_t *__restrict__ block_counts, const int64_t n_blocks, long long *__restrict__ n_distinct)
+// STREAM: *base_out = the list's length before this buffer (what emit_kernel appends at), *n_distinct += this buffer's total
+template <bool STREAM>
+__global__ __launch_bounds__(1024) void block_scan_kernel(uint32_t *__restrict__ block_counts, const int64_t n_blocks, long long *__restrict__ n_distinct,
+                                                          long long *__restrict__ base_out)
 {
     __shared__ uint32_t s_part[16];
     __shared__ unsigned long long s_carry;
@@ -179,16 +206,27 @@ __global__ __launch_bounds__(1024) void block_scan_kernel(uint32_t *__restrict__
         if (t == 0) s_carry = carry + chunk;
         __syncthreads();
     }
-    if (t == 0) *n_distinct = (long long)s_carry;
+    if (t == 0) {
+        if constexpr (STREAM) {
+            const long long before = *n_distinct;
+            *base_out = before;
+            *n_distinct = before + (long long)s_carry;
+        } else {
+            *n_distinct = (long long)s_carry;
+        }
+    }
 }
 
+template <bool STREAM>
 __global__ __launch_bounds__(64) void emit_kernel(const uint8_t *__restrict__ px, const int64_t n, const unsigned long long *__restrict__ flags,
-                                                  const uint32_t *__restrict__ block_base, uint8_t *__restrict__ out)
+                                                  const uint32_t *__restrict__ block_base, uint8_t *__restrict__ out,
+                                                  const long long *__restrict__ list_base, uint32_t *__restrict__ seen)
 {
     const int lane = threadIdx.x;
     const bool aligned = ((uintptr_t)px & 3) == 0;
     const int64_t gbase = (int64_t)blockIdx.x * (kBlockPx / 4);
     size_t at = block_base[blockIdx.x];
+    if constexpr (STREAM) at += (size_t)*list_base;
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll 1
     for (int round = 0; round < kBlockPx / 256; ++round) {
@@ -209,6 +247,7 @@ __global__ __launch_bounds__(64) void emit_kernel(const uint8_t *__restrict__ px
                 o[0] = (uint8_t)c[q];
                 o[1] = (uint8_t)(c[q] >> 8);
                 o[2] = (uint8_t)(c[q] >> 16);
+                if constexpr (STREAM) __hip_atomic_fetch_or(&seen[c[q] >> 5], 1u << (c[q] & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 ++rank;
             }
         }
@@ -242,10 +281,51 @@ int launch_distinct_first(const uint8_t *px, int64_t n, uint8_t *out, long long 
     const int64_t groups = (n + 3) / 4;
     const unsigned blocks = (unsigned)std::min<int64_t>((groups + kFB - 1) / kFB, (int64_t)cus * 4);
     ProfMark *pm = prof_begin(s);
-    hipLaunchKernelGGL(first_index_kernel, dim3(blocks), dim3(kFB), 0, s, px, n, first);
-    hipLaunchKernelGGL(first_flags_kernel, dim3((unsigned)nb), dim3(64), 0, s, px, n, first, flags, block_counts);
-    hipLaunchKernelGGL(block_scan_kernel, dim3(1), dim3(1024), 0, s, block_counts, nb, n_distinct);
-    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nb), dim3(64), 0, s, px, n, flags, block_counts, out);
+    hipLaunchKernelGGL(first_index_kernel<false>, dim3(blocks), dim3(kFB), 0, s, px, n, first, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(first_flags_kernel<false>, dim3((unsigned)nb), dim3(64), 0, s, px, n, first, flags, block_counts, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(block_scan_kernel<false>, dim3(1), dim3(1024), 0, s, block_counts, nb, n_distinct, (long long *)nullptr);
+    hipLaunchKernelGGL(emit_kernel<false>, dim3((unsigned)nb), dim3(64), 0, s, px, n, flags, block_counts, out, (const long long *)nullptr,
+                       (uint32_t *)nullptr);
+    prof_end(pm, s);
+    DP_HIP(hipGetLastError());
+    return DP_OK;
+}
+
+// ---- the stream form: one bit per colour kept by the caller between buffers ----
+size_t distinct_stream_state_bytes() { return kSeenBytes; }
+
+// first-index table | flags | block bases | the list's length before this buffer (one word in a 256-byte tail)
+size_t distinct_stream_ws_bytes(int64_t n)
+{
+    return kFirstTableBytes + flags_bytes(n) + (((size_t)n_blocks_of(n) * sizeof(uint32_t) + 255) & ~(size_t)255) + 256;
+}
+
+int launch_distinct_stream_reset(void *state, long long *n_distinct, hipStream_t s)
+{
+    DP_HIP(hipMemsetAsync(state, 0, kSeenBytes, s));
+    DP_HIP(hipMemsetAsync(n_distinct, 0, sizeof(long long), s));
+    return DP_OK;
+}
+
+int launch_distinct_stream_add(const uint8_t *px, int64_t n, void *state, uint8_t *list, long long *n_distinct, void *ws, hipStream_t s)
+{
+    if (n == 0) return DP_OK;
+    uint32_t *seen = static_cast<uint32_t *>(state);
+    uint32_t *first = static_cast<uint32_t *>(ws);
+    unsigned long long *flags = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(ws) + kFirstTableBytes);
+    uint32_t *block_counts = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(flags) + flags_bytes(n));
+    const int64_t nb = n_blocks_of(n);
+    long long *list_base = reinterpret_cast<long long *>(reinterpret_cast<uint8_t *>(block_counts) + (((size_t)nb * sizeof(uint32_t) + 255) & ~(size_t)255));
+    DP_HIP(hipMemsetAsync(first, 0xff, kFirstTableBytes, s));
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const int64_t groups = (n + 3) / 4;
+    const unsigned blocks = (unsigned)std::min<int64_t>((groups + kFB - 1) / kFB, (int64_t)cus * 4);
+    ProfMark *pm = prof_begin(s);
+    hipLaunchKernelGGL(first_index_kernel<true>, dim3(blocks), dim3(kFB), 0, s, px, n, first, (const uint32_t *)seen);
+    hipLaunchKernelGGL(first_flags_kernel<true>, dim3((unsigned)nb), dim3(64), 0, s, px, n, first, flags, block_counts, (const uint32_t *)seen);
+    hipLaunchKernelGGL(block_scan_kernel<true>, dim3(1), dim3(1024), 0, s, block_counts, nb, n_distinct, list_base);
+    hipLaunchKernelGGL(emit_kernel<true>, dim3((unsigned)nb), dim3(64), 0, s, px, n, flags, block_counts, list, (const long long *)list_base, seen);
     prof_end(pm, s);
     DP_HIP(hipGetLastError());
     return DP_OK;

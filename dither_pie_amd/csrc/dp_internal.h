@@ -213,6 +213,12 @@ int launch_kmeans_step(const uint8_t *px, int64_t n, const double *centers, cons
                        int64_t *sumsq, hipStream_t s);
 size_t distinct_first_ws_bytes(int64_t n);
 int launch_distinct_first(const uint8_t *px, int64_t n, uint8_t *out, long long *n_distinct, void *ws, hipStream_t s);
+size_t distinct_stream_state_bytes();
+size_t distinct_stream_ws_bytes(int64_t n);
+int launch_distinct_stream_reset(void *state, long long *n_distinct, hipStream_t s);
+int launch_distinct_stream_add(const uint8_t *px, int64_t n, void *state, uint8_t *list, long long *n_distinct, void *ws, hipStream_t s);
+size_t hist_sample_ws_bytes();
+int launch_hist_sample(const void *hist, const long long *ranks, int n_ranks, uint8_t *out, unsigned long long *n_bad, void *ws, hipStream_t s);
 size_t kmeans_hist_bytes();
 size_t kmeans_hist_ws_bytes(int64_t n);
 int launch_kmeans_hist_build(const uint8_t *px, int64_t n, void *hist, int accumulate, void *ws, hipStream_t s);

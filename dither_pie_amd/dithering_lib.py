@@ -843,6 +843,13 @@ class ColorReducer:
         distinct = ColorReducer._distinct_of_image(rgb)
         if distinct is None:
             distinct = ColorReducer._distinct_in_order(np.frombuffer(rgb.tobytes(), dtype=np.uint8).reshape(-1, 3))
+        return ColorReducer._median_cut_of_distinct(distinct, num_colors)
+
+    @staticmethod
+    def _median_cut_of_distinct(distinct: np.ndarray, num_colors: int) -> List[Tuple[int, int, int]]:
+        """The tail of reduce_colors: `distinct` holds the image's distinct colours ([n,3] uint8) in order of first
+        occurrence -- the order they enter the reference's set -- however they were found (one image, or a clip's frames
+        streamed through backend.DistinctStream)."""
         distinct = np.ascontiguousarray(distinct)
         n = max(int(num_colors), 1)
         depth = int(math.log2(n)) if n > 1 else 0
@@ -868,6 +875,23 @@ class ColorReducer:
         histogram) with exact integer sums, seeded from `random_state` (dither_pie_amd/kmeans.py: parity definition)."""
         from .kmeans import kmeans_palette_from_image
         return kmeans_palette_from_image(img, num_colors, random_state)
+
+    @staticmethod
+    def reduce_colors_frames(frames, num_colors: int, use_gamma: bool = False, every: int = 1) -> List[Tuple[int, int, int]]:
+        """reduce_colors over a CLIP that is resident on the GPU (uint8 CUDA tensor [N,H,W,3]): one palette fitted to every
+        `every`-th frame.  Equal to the reference's reduce_colors(image, n) with `image` the taken frames stacked top to
+        bottom (linearised first under use_gamma).  clip_palette.ClipPalette is the streaming form."""
+        from .clip_palette import ClipPalette
+        return ClipPalette(use_gamma=use_gamma, device=frames.device).add(frames, every=every).median_cut(num_colors)
+
+    @staticmethod
+    def generate_kmeans_palette_frames(frames, num_colors: int, random_state=42, use_gamma: bool = False,
+                                       every: int = 1) -> List[Tuple[int, int, int]]:
+        """A k-means palette of a CLIP that is resident on the GPU: a pure function of the colour multiset of every
+        `every`-th frame (clip_palette.ClipPalette.kmeans: seeds by pixel rank in histogram order, Lloyd over the
+        histogram)."""
+        from .clip_palette import ClipPalette
+        return ClipPalette(use_gamma=use_gamma, device=frames.device).add(frames, every=every).kmeans(num_colors, random_state)
 
     @staticmethod
     def generate_uniform_palette(num_colors: int) -> List[Tuple[int, int, int]]:

@@ -134,7 +134,8 @@ def lloyd(px, init_centers, max_iter=300, tol=1e-4, group=None, step_fn=None, sk
     the totals are sums of count x colour, so labels and int64 totals are those of the passes over the pixels, bit for bit,
     at 16 KB per occupied cell of the colour cube per pass instead of 3 B per pixel.  True / False force the choice.
     hist: a backend.ColourHistogram of exactly these pixels that the caller has built already (fit_palette builds it on a second
-    stream while the seeding runs).
+    stream while the seeding runs).  px=None with a histogram: the pixels are not resident at all (a clip accumulated batch by
+    batch, clip_palette.ClipPalette); K <= 256.
     fuse: None -- with the histogram and no other rank to exchange totals with, an iteration is ONE launch
     (dp_kmeans_hist_iterate: the pass, and the centre update by the workgroup that finishes last); False keeps the three
     steps pass / all-reduce / update (what a sharded fit runs).
@@ -154,9 +155,18 @@ def lloyd(px, init_centers, max_iter=300, tol=1e-4, group=None, step_fn=None, sk
     if step_fn is not None:
         return _lloyd_host(px, init_centers, max_iter, tol, group, step_fn, sklearn_ties)
     from . import backend
-    flat = px.reshape(-1, 3)
-    if not flat.is_contiguous():
-        flat = flat.contiguous()
+    if px is None:
+        # a clip (clip_palette.ClipPalette): the pixels were accumulated into `hist` batch by batch and are not resident;
+        # every pass runs over the histogram
+        if hist is None or hist.n <= 0 or histogram is False:
+            raise ValueError("lloyd without pixels needs a non-empty ColourHistogram")
+        if np.shape(init_centers)[0] > backend.KMEANS_HIST_MAX_K:
+            raise ValueError(f"Lloyd over a histogram takes at most {backend.KMEANS_HIST_MAX_K} centres")
+        flat = torch.empty((hist.n, 0), dtype=torch.uint8, device=hist.buf.device)   # carries the pixel count and the device only
+    else:
+        flat = px.reshape(-1, 3)
+        if not flat.is_contiguous():
+            flat = flat.contiguous()
     dev = flat.device
     if isinstance(init_centers, torch.Tensor):
         centers = init_centers.to(device=dev, dtype=torch.float64).reshape(-1, 3).contiguous().clone()

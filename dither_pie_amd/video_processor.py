@@ -395,6 +395,147 @@ class VideoProcessor:
             n = f.write(mv)
             mv = mv[len(mv) if n is None else n:]
 
+    def _open_decoder(self, input_path, w, h):
+        """The decode half of the pipes path: ffmpeg writing rgb24 frames of exactly w x h to a (widened) pipe.  The byte
+        stream is sliced into frames of that size, so the decoder's output size is made explicit."""
+        dec = subprocess.Popen(["ffmpeg", "-v", "error", "-i", input_path, "-f", "rawvideo", "-pix_fmt",
+                                "rgb24", "-s", f"{w}x{h}", "pipe:1"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                               bufsize=0)
+        self._widen_pipe(dec.stdout)
+        return dec
+
+    @staticmethod
+    def _decoder_reader(dec, batch_size, frame_bytes, w, h, stats, max_frames=None):
+        """The reader stage's work: read_batch(view) -> (whole frames read, bytes read) fills `view` from the decoder until it
+        holds a batch or the stream ends.  max_frames: stop after that many frames of the stream (the last batch comes out
+        short, which ends the stage as the end of the stream does)."""
+        import time
+        left = {"frames": None if max_frames is None else max(int(max_frames), 0)}
+
+        def read_batch(view):
+            t0 = time.perf_counter()
+            got, want = 0, batch_size * frame_bytes
+            if left["frames"] is not None:
+                want = min(want, left["frames"] * frame_bytes)
+            while got < want:  # a pipe read returns at most the pipe's capacity at a time
+                n = dec.stdout.readinto(view[got:want])
+                if not n:
+                    break
+                got += n
+            stats["read_s"] += time.perf_counter() - t0
+            if got % frame_bytes:
+                raise RuntimeError(f"decoder stream is not a whole number of {w}x{h} rgb24 frames "
+                                   f"({got % frame_bytes} bytes left over)")
+            if left["frames"] is not None:
+                left["frames"] -= got // frame_bytes
+            return got // frame_bytes, got
+        return read_batch
+
+    def scan_palette(self, video_path, source, num_colors, every=1, max_frames=None, use_gamma=False, random_state=42):
+        """One palette fitted to the whole clip, ready for ImageDitherer(palette=...): the DECODE half of the rawvideo pipes
+        path (the same decoder command line, reader thread, rotating pinned slots and failure policy as
+        _stream_through_pipes; no encoder) feeding every `every`-th frame into a clip_palette.ClipPalette.
+        source: "median_cut" (the reference's reduce_colors on the taken frames stacked top to bottom) or "kmeans" (a pure
+        function of the clip's colour multiset; clip_palette's parity definitions).  max_frames: look at the first that
+        many frames of the stream only.  Failure policy: a batch that fails is retried frame by frame and a frame that
+        keeps failing is left out of the palette; a device failure, a malformed stream or a decoder that exits with an
+        error raises, as in the pipes path.  Progress goes through progress_callback."""
+        import time
+        import torch
+        from .clip_palette import ClipPalette
+        if source not in ("median_cut", "kmeans"):
+            raise ValueError(f"source must be 'median_cut' or 'kmeans', not {source!r}")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        self._report_progress(0.0, "Initializing the palette scan...")
+        info = self.get_video_info(video_path)
+        if not getattr(self, "_probe_ok", True):
+            raise RuntimeError("could not probe the video's frame size: the decoder stream cannot be sliced into frames")
+        w, h = int(info["width"]), int(info["height"])
+        if self._probe_rotation(video_path) in (90, 270):
+            w, h = h, w
+        frame_bytes = w * h * 3
+        total_hint = info.get("frame_count") or 0
+        if max_frames is not None:
+            total_hint = min(total_hint, int(max_frames)) if total_hint else int(max_frames)
+        dev = self._devices()[0]   # histograms add, but one accumulator lives on one device
+        dev = torch.device("cuda", dev) if isinstance(dev, int) else torch.device(dev)
+        batch_size = max(1, min(15, self.PIPE_SLOT_BYTES // max(frame_bytes, 1)))
+        with torch.cuda.device(dev):
+            gpu_stream = torch.cuda.Stream()
+            with torch.cuda.stream(gpu_stream):
+                clip = ClipPalette(use_gamma=use_gamma, device=dev)
+        token = {}
+
+        def run(x):
+            # H2D and both accumulators on the scan's own stream; what comes back is one byte per frame, so that the
+            # stages downstream (D2H behind the kernels, one event per slot, the slot's way back to the reader) run unchanged
+            with torch.cuda.device(dev), torch.cuda.stream(gpu_stream):
+                clip.add(x.cuda(non_blocking=True), every=every)
+                t = token.get("t")
+                if t is None:
+                    t = token["t"] = torch.zeros((batch_size, 1, 1, 1), dtype=torch.uint8, device=dev)
+                return t[:x.shape[0]]
+
+        def to_host(t):
+            with torch.cuda.device(dev), torch.cuda.stream(gpu_stream):
+                return t.cpu()
+
+        stats = {"mode": "scan", "slots": self.PIPE_SLOTS, "batch_frames": batch_size, "read_s": 0.0, "gpu_submit_s": 0.0,
+                 "gpu_wait_s": 0.0, "write_s": 0.0, "frames": 0}
+        self.last_scan_stats = stats
+        state = {"skipped": 0}
+
+        def emit(out_host, n_frames, per_frame, may_splice=False):
+            if out_host is None:   # a batch that was retried frame by frame: the frames that kept failing are not in the palette
+                state["skipped"] += sum(1 for o in per_frame if o is None)
+            return False
+
+        def progress(done):
+            frac = done / total_hint if total_hint else 0.5
+            self._report_progress(0.05 + 0.85 * min(frac, 1.0), f"Scanned {done}/{total_hint or '?'} frames")
+
+        def new_out(shape):
+            return torch.empty((batch_size,) + tuple(shape), dtype=torch.uint8, pin_memory=True)
+
+        self._report_progress(0.05, "Starting the decoder...")
+        dec = self._open_decoder(video_path, w, h)
+        read_batch = self._decoder_reader(dec, batch_size, frame_bytes, w, h, stats, max_frames)
+        done, stopped_early = 0, False
+        t_wall = time.perf_counter()
+        try:
+            done = self._pipe_overlapped(batch_size, frame_bytes, (h, w), (1, 1), run, to_host, gpu_stream, {"out": None}, read_batch,
+                                         emit, progress, lambda shape: new_out((1, 1, 1)), stats, dec, lambda: 0, state)
+            stopped_early = max_frames is not None and done >= int(max_frames)
+        finally:
+            if stopped_early:
+                try:
+                    dec.kill()   # the rest of the stream is not wanted
+                except Exception:  # noqa: BLE001
+                    pass
+            if dec.stdout:
+                dec.stdout.close()
+            rc_dec = dec.wait()
+            gpu_stream.synchronize()
+            state.pop("slots", None)
+            stats["frames"] = done
+            stats["skipped"] = state["skipped"]
+            stats["wall_s"] = time.perf_counter() - t_wall
+        if rc_dec != 0 and not stopped_early:
+            raise RuntimeError(f"ffmpeg failed (decoder {rc_dec})")
+        if done == 0:
+            raise ValueError("No frames extracted from video")
+        if clip.n_pixels == 0:
+            raise RuntimeError("no frame of the video could be scanned")
+        if state["skipped"]:
+            print(f"Left {state['skipped']} failed frames out of the palette", file=sys.stderr)
+        self._report_progress(0.9, "Fitting the palette...")
+        self.last_clip_palette = clip
+        with torch.cuda.device(dev):
+            palette = clip.median_cut(num_colors) if source == "median_cut" else clip.kmeans(num_colors, random_state)
+        self._report_progress(1.0, "Palette scan complete!")
+        return palette
+
     def _stream_through_pipes(self, input_path, output_path, ditherer, method, max_size, batch_size,
                               final_resize_multiplier, info, run=None, overlap=True) -> int:
         """decode -> GPU -> encode through two ffmpeg rawvideo pipes; returns the number of frames written.
@@ -456,11 +597,7 @@ class VideoProcessor:
                     return t.cpu()
             return t.cpu()
 
-        # the byte stream is sliced into frames of exactly w x h: the decoder's output size is made explicit
-        dec = subprocess.Popen(["ffmpeg", "-v", "error", "-i", input_path, "-f", "rawvideo", "-pix_fmt",
-                                "rgb24", "-s", f"{w}x{h}", "pipe:1"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                               bufsize=0)
-        self._widen_pipe(dec.stdout)
+        dec = self._open_decoder(input_path, w, h)
         state = {"enc": None, "last_good": None, "leading": 0, "substituted": 0, "written": 0, "piped": 0}
         stats = {"mode": "overlapped" if overlap else "serial", "slots": self.PIPE_SLOTS if overlap else 1, "batch_frames": batch_size,
                  "read_s": 0.0, "gpu_submit_s": 0.0, "gpu_wait_s": 0.0, "write_s": 0.0, "frames": 0}
@@ -477,20 +614,7 @@ class VideoProcessor:
             self._widen_pipe(enc.stdin)
             return enc
 
-        def read_batch(view):
-            """-> (whole frames read, bytes read): fills `view` from the decoder until it is full or the stream ends"""
-            t0 = time.perf_counter()
-            got, want = 0, batch_size * frame_bytes
-            while got < want:  # a pipe read returns at most the pipe's capacity at a time
-                n = dec.stdout.readinto(view[got:want])
-                if not n:
-                    break
-                got += n
-            stats["read_s"] += time.perf_counter() - t0
-            if got % frame_bytes:
-                raise RuntimeError(f"decoder stream is not a whole number of {w}x{h} rgb24 frames "
-                                   f"({got % frame_bytes} bytes left over)")
-            return got // frame_bytes, got
+        read_batch = self._decoder_reader(dec, batch_size, frame_bytes, w, h, stats)
 
         splicer = _PipeSplicer() if (overlap and self.PIPE_ZERO_COPY) else None
 
