@@ -115,6 +115,13 @@ _SIGS_CLIP = {
     "dp_hist_sample_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 EXPORTS_CLIP = tuple(_SIGS_CLIP)
+# include/ditherpie_hip_scene.h: scene-cut detection (frame signatures and their distances); a table of its own for the same
+# reason.
+_SIGS_SCENE = {
+    "dp_frame_signatures_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "dp_signature_distances": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+}
+EXPORTS_SCENE = tuple(_SIGS_SCENE)
 
 
 def build(force=False):
@@ -155,7 +162,8 @@ def load():
                 if got != ABI_VERSION:
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
-                for name, (res, args) in list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items()):
+                for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
+                                          + list(_SIGS_SCENE.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

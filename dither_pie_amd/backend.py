@@ -663,6 +663,80 @@ class DistinctStream:
         return self.list[:3 * len(self)].view(-1, 3)
 
 
+SCENE_BINS = 4096   # dp_frame_signatures_u8: the 16^3 cells of the colour cube
+SCENE_MAX_FRAMES = 65535   # ... frames per call
+
+
+def _signatures_into(f, sig):
+    n, h, w = f.shape[0], f.shape[1], f.shape[2]
+    L = _lib.load()
+    for a in range(0, n, SCENE_MAX_FRAMES):
+        b = min(n, a + SCENE_MAX_FRAMES)
+        check(L.dp_frame_signatures_u8(f[a:b].data_ptr(), b - a, h, w, sig[a:b].data_ptr(), _stream()))
+
+
+def frame_signatures(frames):
+    """The coarse colour signature of every frame (dp_frame_signatures_u8, include/ditherpie_hip_scene.h): uint8 CUDA tensor
+    [N,H,W,3] (or [H,W,3]) -> torch.int32 tensor [N,4096] on the device, row f the number of pixels of frame f in each 16^3
+    cell bin = (r>>4)<<8 | (g>>4)<<4 | (b>>4).  The library's counts are uint32; torch has no such type, so the tensor holds
+    their bit patterns as int32: equal to the counts for every frame of fewer than 2^31 pixels (a larger one can read
+    negative in a bin that holds 2^31 pixels or more; .to(torch.int64) & 0xFFFFFFFF widens it).  Asynchronous on the
+    current stream."""
+    f = _frames(frames)
+    if f.shape[1] < 1 or f.shape[2] < 1:
+        raise ValueError("frames must have at least one pixel")
+    sig = torch.empty((f.shape[0], SCENE_BINS), dtype=torch.int32, device=f.device)
+    if f.shape[0]:
+        with torch.cuda.device(f.device):
+            _signatures_into(f, sig)
+    return sig
+
+
+class SceneStream:
+    """The distance of every frame of a STREAM of frame batches to the frame before it (dp_frame_signatures_u8 +
+    dp_signature_distances): add(frames) -> int64 tensor [N] on the device, distances[i] = sum over the 4096 cells of
+    |signature[i] - signature[i-1]|, in 0 ... 2 H W.  The last signature is carried across calls (resident, 16 KB), so the
+    distances do not depend on how the stream was cut into batches; the very first frame, and the first after reset(), has
+    distance 0.  Calls into one object are ordered on one stream (the caller's current one)."""
+
+    def __init__(self, device=None):
+        require_gpu()
+        dev = torch.device(device or "cuda")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.prev = torch.zeros(SCENE_BINS, dtype=torch.int32, device=dev)
+        self._has_prev = False
+        self._n_px = None
+
+    def reset(self):
+        """Forget the carried signature (and the geometry it belongs to): the next frame's distance is 0."""
+        self._has_prev = False
+        self._n_px = None
+        return self
+
+    def add(self, frames):
+        f = _frames(frames)
+        if f.device != self.device:
+            raise ValueError(f"the scene stream lives on {self.device}, frames on {f.device}")
+        n, n_px = f.shape[0], f.shape[1] * f.shape[2]
+        if n_px < 1:
+            raise ValueError("frames must have at least one pixel")
+        if self._has_prev and n_px != self._n_px:
+            raise ValueError(f"frames of {n_px} pixels follow frames of {self._n_px}: signatures of different sizes do not "
+                             "compare; call reset() first")
+        dist = torch.empty(n, dtype=torch.int64, device=self.device)
+        if n == 0:
+            return dist
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            sig = torch.empty((n, SCENE_BINS), dtype=torch.int32, device=self.device)
+            _signatures_into(f, sig)
+            check(L.dp_signature_distances(sig.data_ptr(), n, self.prev.data_ptr(), 1 if self._has_prev else 0, dist.data_ptr(), _stream()))
+        self._has_prev, self._n_px = True, n_px
+        return dist
+
+
 KMEANS_HIST_MAX_K = 256   # dp_kmeans_hist_step: one thread per centre in the list build
 HIST_SAMPLE_MAX_RANKS = 16384   # dp_hist_sample_u8 (the sample limit of dp_kmeans_plusplus_u8)
 

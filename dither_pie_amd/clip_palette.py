@@ -91,6 +91,19 @@ class ClipPalette:
         self._taken_frames += take.shape[0]
         return self
 
+    def reset(self):
+        """Forget every frame: the distinct stream is cleared (dp_distinct_stream_reset), the histogram starts over with the
+        next add (its first build defines every slice of the table) and the frame counters -- `every` counts from the next
+        frame offered -- go back to zero.  The object then behaves as a fresh one; its 114 MB of device buffers are kept.
+        Runs on the caller's current stream, as add() does.  Returns self."""
+        import torch
+        with torch.cuda.device(self.device):
+            self._distinct.reset()
+        self._hist.n = 0
+        self._seen_frames = 0
+        self._taken_frames = 0
+        return self
+
     @property
     def n_pixels(self):
         return self._hist.n

@@ -326,17 +326,22 @@ class VideoProcessor:
         text = str(e)
         return isinstance(e, RuntimeError) and any(k in text for k in ("HIP error", "CUDA error", "hipError", "out of memory"))
 
-    def _batch_with_retries(self, host_frames, run, to_host=None):
+    def _batch_with_retries(self, host_frames, run, to_host=None, first_index=None):
         """The reference's failure policy for one batch (video_processor.py:304-346): the whole batch in one go; if that
         raises, every frame on its own, up to ATTEMPTS times; a frame that keeps failing is reported as None and the
         caller substitutes a neighbour.  run(frames [k,H,W,3]) -> [k,H',W',3]; to_host(frame tensor) -> host tensor (the
         default is .cpu() on the current stream; a caller whose run() works on a stream of its own passes its own).
+        first_index: the stream index of host_frames[0] for a batch function that needs to know where in the stream it is
+        (scene palettes): run is then called as run(frames, first=...), frame i of a retried batch with first_index + i --
+        stated with every call, so that retries cannot desynchronise it.
         -> (out tensor [n,...] or None, per-frame list or None): exactly one of the two is set."""
         if to_host is None:
             def to_host(t):
                 return t.cpu()
+        def call(frames, i):
+            return run(frames) if first_index is None else run(frames, first=first_index + i)
         try:
-            return run(host_frames), None
+            return call(host_frames, 0), None
         except Exception as e:  # noqa: BLE001 - "a frame that errors must not abort the video"
             if self._device_is_gone(e):
                 raise   # not a frame's fault: process_video_streaming reports failure instead of substituting frames
@@ -346,7 +351,7 @@ class VideoProcessor:
             o = None
             for attempt in range(self.ATTEMPTS):
                 try:
-                    o = to_host(run(host_frames[i:i + 1])[0])
+                    o = to_host(call(host_frames[i:i + 1], i)[0])
                     break
                 except Exception as e:  # noqa: BLE001
                     if self._device_is_gone(e):
@@ -431,23 +436,17 @@ class VideoProcessor:
             return got // frame_bytes, got
         return read_batch
 
-    def scan_palette(self, video_path, source, num_colors, every=1, max_frames=None, use_gamma=False, random_state=42):
-        """One palette fitted to the whole clip, ready for ImageDitherer(palette=...): the DECODE half of the rawvideo pipes
-        path (the same decoder command line, reader thread, rotating pinned slots and failure policy as
-        _stream_through_pipes; no encoder) feeding every `every`-th frame into a clip_palette.ClipPalette.
-        source: "median_cut" (the reference's reduce_colors on the taken frames stacked top to bottom) or "kmeans" (a pure
-        function of the clip's colour multiset; clip_palette's parity definitions).  max_frames: look at the first that
-        many frames of the stream only.  Failure policy: a batch that fails is retried frame by frame and a frame that
-        keeps failing is left out of the palette; a device failure, a malformed stream or a decoder that exits with an
-        error raises, as in the pipes path.  Progress goes through progress_callback."""
+    def _scan_decoded(self, video_path, max_frames, setup, what, noun, indexed=False):
+        """The DECODE half of the rawvideo pipes path, shared by scan_palette and scan_scenes: the same decoder command line,
+        reader thread, rotating pinned slots and failure policy as _stream_through_pipes, no encoder.  setup(dev, gpu_stream,
+        h, w, stats) -> feed(frames_on_device, first): called once on the scan's device and stream, it makes the
+        accumulators; feed then gets every batch (or, after a failed batch, every frame on its own) on that stream, with
+        the stream index of its first frame when `indexed` and None otherwise.  -> (frames decoded, device); fills
+        self.last_scan_stats.  A frame that keeps failing is counted in stats["skipped"]; a device failure, a malformed
+        stream or a decoder that exits with an error raises."""
         import time
         import torch
-        from .clip_palette import ClipPalette
-        if source not in ("median_cut", "kmeans"):
-            raise ValueError(f"source must be 'median_cut' or 'kmeans', not {source!r}")
-        if max_frames is not None and int(max_frames) < 1:
-            raise ValueError("max_frames must be >= 1")
-        self._report_progress(0.0, "Initializing the palette scan...")
+        self._report_progress(0.0, f"Initializing the {what}...")
         info = self.get_video_info(video_path)
         if not getattr(self, "_probe_ok", True):
             raise RuntimeError("could not probe the video's frame size: the decoder stream cannot be sliced into frames")
@@ -461,17 +460,20 @@ class VideoProcessor:
         dev = self._devices()[0]   # histograms add, but one accumulator lives on one device
         dev = torch.device("cuda", dev) if isinstance(dev, int) else torch.device(dev)
         batch_size = max(1, min(15, self.PIPE_SLOT_BYTES // max(frame_bytes, 1)))
+        stats = {"mode": "scan", "slots": self.PIPE_SLOTS, "batch_frames": batch_size, "read_s": 0.0, "gpu_submit_s": 0.0,
+                 "gpu_wait_s": 0.0, "write_s": 0.0, "frames": 0}
+        self.last_scan_stats = stats
         with torch.cuda.device(dev):
             gpu_stream = torch.cuda.Stream()
             with torch.cuda.stream(gpu_stream):
-                clip = ClipPalette(use_gamma=use_gamma, device=dev)
+                feed = setup(dev, gpu_stream, h, w, stats)
         token = {}
 
-        def run(x):
-            # H2D and both accumulators on the scan's own stream; what comes back is one byte per frame, so that the
+        def run(x, first=None):
+            # H2D and the accumulators on the scan's own stream; what comes back is one byte per frame, so that the
             # stages downstream (D2H behind the kernels, one event per slot, the slot's way back to the reader) run unchanged
             with torch.cuda.device(dev), torch.cuda.stream(gpu_stream):
-                clip.add(x.cuda(non_blocking=True), every=every)
+                feed(x.cuda(non_blocking=True), first)
                 t = token.get("t")
                 if t is None:
                     t = token["t"] = torch.zeros((batch_size, 1, 1, 1), dtype=torch.uint8, device=dev)
@@ -481,13 +483,10 @@ class VideoProcessor:
             with torch.cuda.device(dev), torch.cuda.stream(gpu_stream):
                 return t.cpu()
 
-        stats = {"mode": "scan", "slots": self.PIPE_SLOTS, "batch_frames": batch_size, "read_s": 0.0, "gpu_submit_s": 0.0,
-                 "gpu_wait_s": 0.0, "write_s": 0.0, "frames": 0}
-        self.last_scan_stats = stats
         state = {"skipped": 0}
 
         def emit(out_host, n_frames, per_frame, may_splice=False):
-            if out_host is None:   # a batch that was retried frame by frame: the frames that kept failing are not in the palette
+            if out_host is None:   # a batch that was retried frame by frame: the frames that kept failing are left out
                 state["skipped"] += sum(1 for o in per_frame if o is None)
             return False
 
@@ -505,7 +504,8 @@ class VideoProcessor:
         t_wall = time.perf_counter()
         try:
             done = self._pipe_overlapped(batch_size, frame_bytes, (h, w), (1, 1), run, to_host, gpu_stream, {"out": None}, read_batch,
-                                         emit, progress, lambda shape: new_out((1, 1, 1)), stats, dec, lambda: 0, state)
+                                         emit, progress, lambda shape: new_out((1, 1, 1)), stats, dec, lambda: 0, state,
+                                         indexed_run=indexed)
             stopped_early = max_frames is not None and done >= int(max_frames)
         finally:
             if stopped_early:
@@ -525,10 +525,35 @@ class VideoProcessor:
             raise RuntimeError(f"ffmpeg failed (decoder {rc_dec})")
         if done == 0:
             raise ValueError("No frames extracted from video")
+        if state["skipped"]:
+            print(f"Left {state['skipped']} failed frames out of the {noun}", file=sys.stderr)
+        return done, dev
+
+    def scan_palette(self, video_path, source, num_colors, every=1, max_frames=None, use_gamma=False, random_state=42):
+        """One palette fitted to the whole clip, ready for ImageDitherer(palette=...): the DECODE half of the rawvideo pipes
+        path (the same decoder command line, reader thread, rotating pinned slots and failure policy as
+        _stream_through_pipes; no encoder) feeding every `every`-th frame into a clip_palette.ClipPalette.
+        source: "median_cut" (the reference's reduce_colors on the taken frames stacked top to bottom) or "kmeans" (a pure
+        function of the clip's colour multiset; clip_palette's parity definitions).  max_frames: look at the first that
+        many frames of the stream only.  Failure policy: a batch that fails is retried frame by frame and a frame that
+        keeps failing is left out of the palette; a device failure, a malformed stream or a decoder that exits with an
+        error raises, as in the pipes path.  Progress goes through progress_callback."""
+        import torch
+        from .clip_palette import ClipPalette
+        if source not in ("median_cut", "kmeans"):
+            raise ValueError(f"source must be 'median_cut' or 'kmeans', not {source!r}")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        made = {}
+
+        def setup(dev, gpu_stream, h, w, stats):
+            clip = made["clip"] = ClipPalette(use_gamma=use_gamma, device=dev)
+            return lambda x, first: clip.add(x, every=every)
+
+        done, dev = self._scan_decoded(video_path, max_frames, setup, "palette scan", "palette")
+        clip = made["clip"]
         if clip.n_pixels == 0:
             raise RuntimeError("no frame of the video could be scanned")
-        if state["skipped"]:
-            print(f"Left {state['skipped']} failed frames out of the palette", file=sys.stderr)
         self._report_progress(0.9, "Fitting the palette...")
         self.last_clip_palette = clip
         with torch.cuda.device(dev):
@@ -536,8 +561,97 @@ class VideoProcessor:
         self._report_progress(1.0, "Palette scan complete!")
         return palette
 
+    def scan_scenes(self, video_path, source=None, num_colors=16, threshold=0.4, min_scene_frames=8, every=1, max_frames=None,
+                    use_gamma=False, random_state=42):
+        """Where the clip cuts, and one palette per scene -> list of scenes.Scene(start, end, palette), in stream order and
+        tiling frames 0 ... n-1; hand it to process_video_streaming(..., scene_palettes=...).  One decode-only pass built as
+        scan_palette is (the same decoder line, reader thread, rotating slots, failure policy and progress milestones; it
+        fills last_scan_stats too).  Per batch: the frames' colour signatures and the distances of consecutive signatures on
+        the device (backend.SceneStream), the N distances read back -- one small synchronising copy per batch --,
+        scenes.scene_cuts, the batch split at the cuts (scenes.split_at), every piece into ONE clip_palette.ClipPalette; at
+        each cut the finished scene's palette is fitted and the accumulator reset.
+        source: "median_cut" / "kmeans" as in scan_palette -- a scene's palette is what a fresh
+        ClipPalette(use_gamma).add(frames[start:end], every) gives for that source; None: boundaries only, every palette is
+        None and no accumulator is made.  every: every that-many-th frame of each scene, counted from the scene's first
+        frame.  Frame i starts a scene when its distance exceeds threshold * 2 * H * W and the open scene holds at least
+        min_scene_frames frames (scenes.scene_cuts).  threshold=0.4 and min_scene_frames=8 are design choices -- "two fifths
+        of the pixels changed their 16^3 cell, and no scene shorter than a third of a second at 24 fps" -- NOT tuned
+        values: there was no footage to tune them on.
+        Failure policy: a frame that keeps failing stays in the scene that is open, does not update the carried signature
+        and is left out of the palette (last_scan_stats["skipped"]); a scene of which no frame could be scanned has palette
+        None.  last_scan_stats gains "signature_s" (signatures, distances and their read-back) and "palette_s" (the fits at
+        the cuts), both part of gpu_submit_s, and "scenes"."""
+        import time
+        import torch
+        from . import backend
+        from .clip_palette import ClipPalette
+        from .scenes import Scene, _check_cut_parameters, scene_cuts, split_at
+        if source not in (None, "median_cut", "kmeans"):
+            raise ValueError(f"source must be None, 'median_cut' or 'kmeans', not {source!r}")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        _check_cut_parameters(threshold, min_scene_frames)
+        if int(every) < 1:
+            raise ValueError("every must be >= 1")
+        if source is not None and int(num_colors) < 1:
+            raise ValueError("num_colors must be >= 1")
+        if source == "kmeans" and int(num_colors) > backend.KMEANS_HIST_MAX_K:
+            raise ValueError(f"a clip k-means palette has at most {backend.KMEANS_HIST_MAX_K} colours, not {num_colors}")
+        scenes = []
+        made = {"clip": None}
+        cur = {"open": 0, "carry": 0, "starts": set()}
+
+        def fit(clip):
+            return clip.median_cut(num_colors) if source == "median_cut" else clip.kmeans(num_colors, random_state)
+
+        def close(end, stats):
+            """the open scene ends in front of stream frame `end`"""
+            clip, palette = made["clip"], None
+            if clip is not None:
+                if clip.n_pixels:
+                    t0 = time.perf_counter()
+                    palette = fit(clip)
+                    stats["palette_s"] += time.perf_counter() - t0
+                clip.reset()
+            scenes.append(Scene(cur["open"], end, palette))
+            cur["open"] = end
+
+        def setup(dev, gpu_stream, h, w, stats):
+            stats.update(signature_s=0.0, palette_s=0.0, scenes=0)
+            made["stats"] = stats
+            sig = backend.SceneStream(dev)
+            clip = made["clip"] = ClipPalette(use_gamma=use_gamma, device=dev) if source is not None else None
+            taken = {"first": 0, "n": 0}   # the batch whose distances were taken last: a retry of its frames must not take them again
+
+            def feed(x, first):
+                n = x.shape[0]
+                if not (taken["first"] <= first and first + n <= taken["first"] + taken["n"]):
+                    t0 = time.perf_counter()
+                    dist = sig.add(x).cpu().tolist()
+                    stats["signature_s"] += time.perf_counter() - t0
+                    cuts, cur["carry"] = scene_cuts(dist, h * w, threshold, min_scene_frames, cur["carry"])
+                    cur["starts"].update(first + c for c in cuts)
+                    taken.update(first=first, n=n)
+                for lo, hi in split_at(first, n, cur["starts"]):
+                    if lo in cur["starts"] and lo != cur["open"]:
+                        close(lo, stats)
+                    if clip is not None:
+                        clip.add(x[lo - first:hi - first], every=every)
+            return feed
+
+        done, dev = self._scan_decoded(video_path, max_frames, setup, "scene scan", "scene palettes", indexed=True)
+        self._report_progress(0.9, "Fitting the last scene's palette...")
+        with torch.cuda.device(dev):
+            if done > cur["open"]:
+                close(done, made["stats"])
+        made["stats"]["scenes"] = len(scenes)
+        if source is not None and all(s.palette is None for s in scenes):
+            raise RuntimeError("no frame of the video could be scanned")
+        self._report_progress(1.0, "Scene scan complete!")
+        return scenes
+
     def _stream_through_pipes(self, input_path, output_path, ditherer, method, max_size, batch_size,
-                              final_resize_multiplier, info, run=None, overlap=True) -> int:
+                              final_resize_multiplier, info, run=None, overlap=True, scene_palettes=None) -> int:
         """decode -> GPU -> encode through two ffmpeg rawvideo pipes; returns the number of frames written.
         Failure policy as in the reference: a batch that fails is retried frame by frame, a frame that still fails is
         replaced by the nearest good output frame (the previous one first, video_processor.py:53-96) and the video goes
@@ -551,9 +665,29 @@ class VideoProcessor:
         video costs max(decode, GPU, encode) per batch instead of their sum (the reference overlaps nothing either: it
         extracts every PNG, then processes, then encodes, video_processor.py:204-217, 304-346, 361-382).
         overlap=False: the serial loop of rounds 2-4 (read -> H2D -> kernels -> D2H -> write per batch), kept as the
-        byte-for-byte A/B partner of the overlapped path.  Both fill self.last_pipe_stats."""
+        byte-for-byte A/B partner of the overlapped path.  Both fill self.last_pipe_stats.
+
+        scene_palettes (a list of scenes.Scene, from scan_scenes): every batch is cut at the scene starts that fall inside it
+        (scenes.split_at) and each piece runs through process_frames with a shallow copy of `ditherer` that carries its
+        scene's palette; the pieces' outputs go into one batch tensor, so the stages downstream see what they see without
+        it.  The batch function is told the stream index of its first frame with every call (_batch_with_retries), also
+        when a failed batch is retried frame by frame.  Frames past the last scene's end use the last scene's palette.
+        ValueError before the decoder starts: scenes.check_scene_palettes, or a `run` of the caller's beside the list."""
         import time
         import torch
+        scene_run = scene_palettes is not None
+        if scene_run:
+            import copy
+            from .scenes import check_scene_palettes, scene_of, split_at
+            if run is not None:
+                raise ValueError("scene_palettes go with the product batch function, not with a run of the caller's")
+            scene_list = check_scene_palettes(scene_palettes)
+            cut_points = [int(sc.start) for sc in scene_list[1:]]
+            scene_ditherers = []
+            for sc in scene_list:
+                d = copy.copy(ditherer)
+                d.palette = [tuple(c) for c in sc.palette]
+                scene_ditherers.append(d)
         w, h, fps = int(info["width"]), int(info["height"]), info["fps"]
         if self._probe_rotation(input_path) in (90, 270):
             w, h = h, w  # ffprobe reports the coded size; the decoder below rotates as the reference's extraction does
@@ -591,6 +725,34 @@ class VideoProcessor:
                         with torch.cuda.stream(gpu_stream):
                             return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier)
                     return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier)
+
+            def one_palette(y, d):
+                return process_frames(y, d, method, max_size, final_resize_multiplier)
+
+            def run_scenes(x, first=0):   # the same, piece by piece with the palette of the piece's scene
+                n = x.shape[0]
+                pieces = [(lo - first, hi - first, scene_ditherers[scene_of(scene_list, lo)]) for lo, hi in split_at(first, n, cut_points)]
+                if len(devs) > 1 and n > 1:
+                    from . import sharding
+                    out = target["out"]
+                    parts = [sharding.process_on_devices(x[a:b], lambda y, d=d: one_palette(y, d), devs,
+                                                         out=None if out is None else out[a:b]) for a, b, d in pieces]
+                    return out[:n] if out is not None else (parts[0] if len(parts) == 1 else torch.cat(parts))
+                with torch.cuda.device(devs[0]), torch.cuda.stream(gpu_stream if gpu_stream is not None else torch.cuda.current_stream()):
+                    xd = x.cuda(non_blocking=True)
+                    if len(pieces) == 1:
+                        return one_palette(xd, pieces[0][2])
+                    out = None
+                    for a, b, d in pieces:
+                        y = one_palette(xd[a:b], d)
+                        if out is None:
+                            out = torch.empty((n,) + tuple(y.shape[1:]), dtype=y.dtype, device=y.device)
+                        out[a:b] = y
+                    return out
+
+            if scene_run:
+                run = run_scenes
+
         def to_host(t):
             if gpu_stream is not None and t.is_cuda:   # the copy goes behind the kernels, on their stream
                 with torch.cuda.device(t.device), torch.cuda.stream(gpu_stream):
@@ -687,7 +849,7 @@ class VideoProcessor:
         try:
             if overlap:
                 done = self._pipe_overlapped(batch_size, frame_bytes, (h, w), out_geom, run, to_host, gpu_stream, target, read_batch, emit,
-                                             progress, new_out, stats, dec, consumed_bytes, state)
+                                             progress, new_out, stats, dec, consumed_bytes, state, indexed_run=scene_run)
             else:
                 stage = torch.empty(batch_size * frame_bytes, dtype=torch.uint8, pin_memory=pin)
                 view = memoryview(stage.numpy())
@@ -699,7 +861,7 @@ class VideoProcessor:
                         break
                     host_frames = stage[:n_frames * frame_bytes].view(n_frames, h, w, 3)
                     t0 = time.perf_counter()
-                    out, per_frame = self._batch_with_retries(host_frames, run, to_host)
+                    out, per_frame = self._batch_with_retries(host_frames, run, to_host, done if scene_run else None)
                     if out is not None:  # one copy into the pinned buffer
                         if out_host is None:
                             out_host = new_out(out.shape[1:])
@@ -743,10 +905,11 @@ class VideoProcessor:
         return done
 
     def _pipe_overlapped(self, batch_size, frame_bytes, in_geom, out_geom, run, to_host, gpu_stream, target, read_batch, emit, progress,
-                         new_out, stats, dec, consumed_bytes, state) -> int:
+                         new_out, stats, dec, consumed_bytes, state, indexed_run=False) -> int:
         """The three concurrent stages of _stream_through_pipes (see there).  Slots rotate free -> filled -> submitted ->
         free; every blocking queue operation polls an abort flag, so an error in any stage (a dead encoder, a device that
-        is gone, a malformed stream) ends the other two instead of leaving them blocked on a queue."""
+        is gone, a malformed stream) ends the other two instead of leaving them blocked on a queue.  indexed_run: run takes
+        the stream index of its first frame (_batch_with_retries: first_index)."""
         import queue
         import threading
         import time
@@ -846,7 +1009,7 @@ class VideoProcessor:
                 host_frames = slot.inp[:n_frames * frame_bytes].view(n_frames, h, w, 3)
                 t0 = time.perf_counter()
                 target["out"] = slot.out
-                out, per_frame = self._batch_with_retries(host_frames, run, to_host)
+                out, per_frame = self._batch_with_retries(host_frames, run, to_host, done if indexed_run else None)
                 event, out_host = None, None
                 if out is not None and out.is_cuda:
                     # D2H into the slot's pinned buffer behind the kernels, on their stream; one event, no host wait
@@ -889,13 +1052,27 @@ class VideoProcessor:
 
     def process_video_streaming(self, input_path: str, output_path: str, ditherer: ImageDitherer,
                                 pixelize_func=None, batch_size: int = 15,
-                                final_resize_multiplier: Optional[int] = None, use_pipes: bool = True) -> bool:
+                                final_resize_multiplier: Optional[int] = None, use_pipes: bool = True,
+                                scene_palettes=None) -> bool:
         """video_processor.py:172-390; pixelize_func is the reference's tuple (method_str, max_size) or None.
-        use_pipes (an addition): rawvideo pipes instead of the reference's PNG files on disk."""
+        use_pipes (an addition): rawvideo pipes instead of the reference's PNG files on disk.
+        scene_palettes (an addition; pipes path only): the list scan_scenes returns -- the palette switches at the scene
+        boundaries (_stream_through_pipes).  None: one palette, the ditherer's, as ever.  ValueError, before anything is
+        started: an empty list, overlapping scenes, a scene whose palette is None, use_pipes=False."""
+        if scene_palettes is not None:
+            from .scenes import check_scene_palettes
+            if not use_pipes:
+                raise ValueError("scene_palettes need the pipes path (use_pipes=True)")
+            scene_palettes = check_scene_palettes(scene_palettes)
         if use_pipes:
             info = self.get_video_info(input_path)
             if not getattr(self, "_probe_ok", True):
                 use_pipes = False  # frame size unknown: the PNG-file exchange below does not depend on it
+                if scene_palettes is not None:
+                    self._report_progress(1.0, "Error: could not probe the video's frame size")
+                    print("Video processing error: scene palettes need the pipes path, and the frame size could not be probed",
+                          file=sys.stderr)
+                    return False
         if use_pipes:
             try:
                 # the reference's milestones (0.0, 0.05, 0.1 ... 0.9, 1.0; video_processor.py:199-384) with messages that
@@ -905,7 +1082,8 @@ class VideoProcessor:
                 method, max_size = (None, 64) if pixelize_func is None else pixelize_func
                 self._report_progress(0.1, "Processing frames...")
                 self._stream_through_pipes(input_path, output_path, ditherer, method, max_size, max(1, batch_size),
-                                           final_resize_multiplier, info)   # reports 0.9 before it waits for the encoder
+                                           final_resize_multiplier, info,   # reports 0.9 before it waits for the encoder
+                                           scene_palettes=scene_palettes)
                 self._report_progress(1.0, "Video processing complete!")
                 return True
             except Exception as e:  # noqa: BLE001
