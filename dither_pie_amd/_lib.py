@@ -122,6 +122,16 @@ _SIGS_SCENE = {
     "dp_signature_distances": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
 }
 EXPORTS_SCENE = tuple(_SIGS_SCENE)
+# include/ditherpie_hip_gif.h: animated GIF output (inter-frame deltas, LZW image data on the device and its host statement);
+# a table of its own for the same reason.
+_SIGS_GIF = {
+    "dp_index_delta_u8": (_i, [_vp, _i, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    "dp_gif_lzw_bound_bytes": (_sz, [_i, _i, _i64]),
+    "dp_gif_lzw_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
+    "dp_gif_lzw_encode_u8": (_i, [_vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dp_gif_lzw_host_u8": (_i, [_vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp]),
+}
+EXPORTS_GIF = tuple(_SIGS_GIF)
 
 
 def build(force=False):
@@ -163,7 +173,7 @@ def load():
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
-                                          + list(_SIGS_SCENE.items())):
+                                          + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -997,6 +997,166 @@ def resize_nearest_plane(planes, oh, ow):
     return out if planes.dim() == 3 else out[0]
 
 
+GIF_MAX_FRAMES = 65535      # dp_index_delta_u8, dp_gif_lzw_encode_u8: frames per call
+GIF_CHUNK_PX = 32768        # the default chunk of dp_gif_lzw_encode_u8 (file size against parallelism)
+
+
+def _planes_u8(planes):
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dtype == torch.uint8):
+        raise TypeError("planes must be a CUDA uint8 tensor (one-byte indices)")
+    if planes.dim() not in (2, 3):
+        raise ValueError("planes must be [N,H,W] or [H,W]")
+    p = (planes if planes.dim() == 3 else planes.unsqueeze(0)).contiguous()
+    if p.shape[1] < 1 or p.shape[2] < 1:
+        raise ValueError("planes must have at least one pixel")
+    return p
+
+
+def _check_transparent(transparent):
+    t = int(transparent)
+    if not 0 <= t <= 255:
+        raise ValueError(f"transparent must be in 0 ... 255, not {transparent!r}")
+    return t
+
+
+def _delta_into(p, prev, has_prev, transparent, out, changed):
+    n, n_px = p.shape[0], p.shape[1] * p.shape[2]
+    L = _lib.load()
+    for a in range(0, n, GIF_MAX_FRAMES):
+        b = min(n, a + GIF_MAX_FRAMES)
+        check(L.dp_index_delta_u8(p[a:b].data_ptr(), b - a, n_px, prev.data_ptr(), 1 if (has_prev or a) else 0, transparent,
+                                  out[a:b].data_ptr(), changed[a:b].data_ptr(), _stream()))
+
+
+def index_delta(planes, prev, transparent, out=None):
+    """Inter-frame deltas of one-byte index planes (dp_index_delta_u8, include/ditherpie_hip_gif.h): uint8 CUDA planes [N,H,W]
+    -> (out [N,H,W] uint8, changed [N] int64 on the device).  out[f] holds `transparent` where planes[f] equals planes[f-1]
+    and planes[f] elsewhere; frame 0 is compared with `prev` ([H,W] uint8 on the same device) or, with prev=None, copied
+    through.  changed[f] counts the pixels that differ (H W for a frame 0 without prev).  A given `prev` is UPDATED: after the
+    call it holds planes[-1], which is what the next batch of the same stream compares with (DeltaStream does the
+    bookkeeping).  `out` must not be the planes themselves.  Asynchronous on the current stream."""
+    p = _planes_u8(planes)
+    t = _check_transparent(transparent)
+    n, h, w = p.shape
+    if prev is not None:
+        if not (isinstance(prev, torch.Tensor) and prev.is_cuda and prev.dtype == torch.uint8 and prev.is_contiguous()):
+            raise TypeError("prev must be a contiguous CUDA uint8 tensor")
+        if prev.device != p.device or prev.numel() != h * w:
+            raise ValueError(f"prev must hold one plane of {h} x {w} on {p.device}")
+    res = _check_buffer(out, p.device, (n, h, w), torch.uint8, "out")
+    changed = torch.empty(n, dtype=torch.int64, device=p.device)
+    if n:
+        with torch.cuda.device(p.device):
+            carried = prev if prev is not None else torch.empty(h * w, dtype=torch.uint8, device=p.device)
+            _delta_into(p, carried, prev is not None, t, res, changed)
+    return res, changed
+
+
+class DeltaStream:
+    """Inter-frame deltas over a STREAM of plane batches: add(planes, transparent) -> (out, changed) as index_delta, with the
+    last plane carried across calls (resident, H W bytes), so the result does not depend on how the stream was cut into
+    batches; the very first frame, and the first after reset(), goes out whole.  Calls into one object are ordered on one
+    stream (the caller's current one)."""
+
+    def __init__(self, device=None):
+        require_gpu()
+        dev = torch.device(device or "cuda")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.prev = None
+        self._has_prev = False
+
+    def reset(self):
+        """Forget the carried plane: the next frame goes out whole."""
+        self._has_prev = False
+        return self
+
+    def add(self, planes, transparent):
+        p = _planes_u8(planes)
+        if p.device != self.device:
+            raise ValueError(f"the delta stream lives on {self.device}, planes on {p.device}")
+        t = _check_transparent(transparent)
+        n, h, w = p.shape
+        if self._has_prev and self.prev.numel() != h * w:
+            raise ValueError(f"planes of {h * w} pixels follow planes of {self.prev.numel()}: call reset() first")
+        out = torch.empty_like(p)
+        changed = torch.empty(n, dtype=torch.int64, device=self.device)
+        if n == 0:
+            return out, changed
+        with torch.cuda.device(self.device):
+            if self.prev is None or self.prev.numel() != h * w:
+                self.prev = torch.empty(h * w, dtype=torch.uint8, device=self.device)
+            _delta_into(p, self.prev, self._has_prev, t, out, changed)
+        self._has_prev = True
+        return out, changed
+
+    def carry(self, plane):
+        """Make `plane` ([H,W] uint8 on the stream's device) the plane the next frame is compared with, without computing a
+        delta: for a caller that writes some frames whole."""
+        p = _planes_u8(plane)
+        if p.device != self.device or p.shape[0] != 1:
+            raise ValueError(f"carry takes one plane on {self.device}")
+        self.prev = p[0].reshape(-1).clone()
+        self._has_prev = True
+        return self
+
+
+def gif_lzw_stride(h, w, chunk_px=None):
+    """The bytes dp_gif_lzw_encode_u8 may write per frame (dp_gif_lzw_bound_bytes): the row length of gif_lzw's payload."""
+    return int(_lib.load().dp_gif_lzw_bound_bytes(int(h), int(w), int(chunk_px or GIF_CHUNK_PX)))
+
+
+def gif_lzw(planes, min_code_size, chunk_px=None):
+    """The GIF image data of one-byte index planes (dp_gif_lzw_encode_u8): uint8 CUDA planes [N,H,W] -> (payload [N, stride]
+    uint8, sizes [N] int64), both on the device.  payload[f, :sizes[f]] is frame f's min_code_size byte, LZW sub-blocks and
+    terminator, to be written verbatim behind an image descriptor; the bytes past sizes[f] are unspecified.  An index
+    >= 1 << min_code_size is the caller's error (it is encoded by its low bits).  chunk_px: pixels a wave compresses on its
+    own (default GIF_CHUNK_PX).  The device encoder is the only one here: the host statement is gif_lzw_host, by name.
+    Asynchronous on the current stream."""
+    p = _planes_u8(planes)
+    mcs, chunk = int(min_code_size), int(GIF_CHUNK_PX if chunk_px is None else chunk_px)
+    if not 2 <= mcs <= 8:
+        raise ValueError(f"min_code_size must be in 2 ... 8, not {min_code_size!r}")
+    if chunk < 1:
+        raise ValueError(f"chunk_px must be >= 1, not {chunk_px!r}")
+    n, h, w = p.shape
+    L = _lib.load()
+    stride = int(L.dp_gif_lzw_bound_bytes(h, w, chunk))
+    if stride == 0:
+        raise ValueError(f"planes of {h} x {w} are more than the encoder takes (h * w < 2^31)")
+    payload = torch.empty((n, stride), dtype=torch.uint8, device=p.device)
+    sizes = torch.empty(n, dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        for a in range(0, n, GIF_MAX_FRAMES):
+            b = min(n, a + GIF_MAX_FRAMES)
+            need = int(L.dp_gif_lzw_workspace_bytes(b - a, h, w, chunk))
+            with _Launch(p.device, need) as ws:
+                check(L.dp_gif_lzw_encode_u8(p[a:b].data_ptr(), b - a, h, w, mcs, chunk, payload[a:b].data_ptr(), stride, sizes[a:b].data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream()))
+    return payload, sizes
+
+
+def gif_lzw_host(planes, min_code_size, chunk_px=None):
+    """The same bytes from the host statement (dp_gif_lzw_host_u8), no device involved: numpy uint8 planes [N,H,W] ->
+    [bytes per frame].  What the device encoder is tested against, and what GifWriter runs on when asked to (encoder="host")."""
+    p = np.ascontiguousarray(planes, dtype=np.uint8)
+    if p.ndim == 2:
+        p = p[None]
+    if p.ndim != 3 or p.shape[1] < 1 or p.shape[2] < 1:
+        raise ValueError("planes must be [N,H,W] or [H,W] with at least one pixel")
+    mcs, chunk = int(min_code_size), int(GIF_CHUNK_PX if chunk_px is None else chunk_px)
+    n, h, w = p.shape
+    if n == 0:
+        return []
+    L = _lib.load()
+    stride = int(L.dp_gif_lzw_bound_bytes(h, w, max(chunk, 1)))
+    out = np.empty((n, max(stride, 1)), np.uint8)
+    sizes = np.zeros(n, np.int64)
+    check(L.dp_gif_lzw_host_u8(_np_ptr(p), n, h, w, mcs, chunk, _np_ptr(out), stride, _np_ptr(sizes)))
+    return [out[f, :int(sizes[f])].tobytes() for f in range(n)]
+
+
 def profile_enable(on=True):
     check(_lib.load().dp_profile_enable(1 if on else 0))
 

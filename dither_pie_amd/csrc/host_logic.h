@@ -1488,4 +1488,104 @@ inline bool index_map_build(const uint8_t *colors_u8, const int K, IndexMapHost 
     return best >= 0;
 }
 
+// ---- GIF image data (gif.hip, include/ditherpie_hip_gif.h) -------------------------------------------------------------
+// The normative statement of the chunked LZW stream: the device kernels write the bytes this writes.  The dictionary is the
+// open-addressing table the chunk kernel keeps in LDS: a pair (prefix code, pixel) is the 20-bit key code << 8 | pixel, a
+// slot holds key << 12 | the code the pair got, 0xFFFFFFFF is an empty slot (no entry has prefix 4095: by the time code 4095
+// exists no code is free).  At most 4096 - 6 entries in 8192 slots, so a probe run ends at an empty slot; the loops are
+// bounded by the table size all the same.
+constexpr int kGifSlots = 8192;
+constexpr uint32_t kGifEmpty = 0xFFFFFFFFu;
+constexpr int kGifCodesPerClear = 4096 - 258 + 1;   // codes in front of a Clear inside a chunk, at least (min_code_size 8)
+
+inline uint32_t gif_slot_of(const uint32_t key) { return (key * 0x9E3779B1u) >> 19; }   // 13 bits
+
+inline int64_t gif_chunks(const int64_t n_px, const int64_t chunk_px) { return (n_px + std::min(chunk_px, n_px) - 1) / std::min(chunk_px, n_px); }
+
+// the worst-case size of one frame's image data (the derivation is in the header); n_px >= 1, chunk_px >= 1
+inline uint64_t gif_lzw_bound(const int64_t n_px, const int64_t chunk_px)
+{
+    const uint64_t codes = (uint64_t)n_px + (uint64_t)n_px / kGifCodesPerClear + (uint64_t)gif_chunks(n_px, chunk_px) + 1u;
+    const uint64_t d = (12u * codes + 7u) / 8u;
+    return 1u + d + (d + 254u) / 255u + 1u;
+}
+
+struct GifBits {
+    std::vector<uint8_t> data;
+    uint64_t acc = 0;
+    int n = 0;
+    void put(const uint32_t code, const int width)
+    {
+        acc |= (uint64_t)code << n;
+        n += width;
+        for (; n >= 8; n -= 8, acc >>= 8) data.push_back((uint8_t)(acc & 0xFFu));
+    }
+    void flush()
+    {
+        if (n > 0) data.push_back((uint8_t)(acc & 0xFFu));
+        n = 0;
+        acc = 0;
+    }
+};
+
+// One frame: n_px pixels -> `out` (cleared first): min_code_size byte, sub-blocks, terminator.
+inline void gif_lzw_encode(const uint8_t *px, const int64_t n_px, const int min_code_size, int64_t chunk_px, std::vector<uint8_t> &out)
+{
+    const uint32_t clear = 1u << min_code_size, eoi = clear + 1u, mask = clear - 1u;
+    chunk_px = std::min(chunk_px, n_px);
+    std::vector<uint32_t> table((size_t)kGifSlots);
+    GifBits bits;
+    int width = min_code_size + 1;
+    for (int64_t at = 0; at < n_px; at += chunk_px) {
+        const int64_t n = std::min(chunk_px, n_px - at);
+        bits.put(clear, width);
+        width = min_code_size + 1;
+        uint32_t next = clear + 2u;
+        std::fill(table.begin(), table.end(), kGifEmpty);
+        uint32_t cur = px[at] & mask;
+        for (int64_t i = 1; i < n; ++i) {
+            const uint32_t c = px[at + i] & mask, key = (cur << 8) | c;
+            uint32_t slot = gif_slot_of(key), found = kGifEmpty;
+            for (int probe = 0; probe < kGifSlots; ++probe, slot = (slot + 1u) & (uint32_t)(kGifSlots - 1)) {
+                const uint32_t e = table[slot];
+                if (e == kGifEmpty) break;
+                if ((e >> 12) == key) {
+                    found = e & 0xFFFu;
+                    break;
+                }
+            }
+            if (found != kGifEmpty) {
+                cur = found;
+                continue;
+            }
+            bits.put(cur, width);
+            if (next < 4096u) {
+                table[slot] = (key << 12) | next;   // (the run ended at an empty slot: the table is never full)
+                if (next == (1u << width) && width < 12) ++width;
+                ++next;
+            } else {
+                bits.put(clear, 12);
+                width = min_code_size + 1;
+                next = clear + 2u;
+                std::fill(table.begin(), table.end(), kGifEmpty);
+            }
+            cur = c;
+        }
+        bits.put(cur, width);
+        if (next < 4096u && next == (1u << width) && width < 12) ++width;   // the decoder's lagging entry
+    }
+    bits.put(eoi, width);
+    bits.flush();
+    const std::vector<uint8_t> &d = bits.data;
+    out.clear();
+    out.reserve(d.size() + d.size() / 255 + 3);
+    out.push_back((uint8_t)min_code_size);
+    for (size_t a = 0; a < d.size(); a += 255) {
+        const size_t len = std::min<size_t>(255, d.size() - a);
+        out.push_back((uint8_t)len);
+        out.insert(out.end(), d.begin() + (std::ptrdiff_t)a, d.begin() + (std::ptrdiff_t)(a + len));
+    }
+    out.push_back(0);
+}
+
 }  // namespace dp

@@ -19,6 +19,9 @@
 //                                     n records {int32 K, int32 Q, K x 3 colour bytes, Q x 3 query bytes}; per record prints
 //                                     the map's figures, the index index_map_lookup reports for each of the K colours
 //                                     and how many of the Q queries (absent colours, by the test's construction) it finds
+//   host_xxx giflzw <cases.bin> <n>   the host statement of the GIF image data (gif_lzw_encode): the file holds n records
+//                                     {int32 n_frames, h, w, min_code_size; int64 chunk_px; n_frames x h x w index bytes}; per
+//                                     frame prints its size and its bytes in hex (compared with tests/gif_ref.py by the test)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -471,14 +474,53 @@ static int run_indexmap(const char *path, const int n_lists)
     return 0;
 }
 
+// ---- GIF image data --------------------------------------------------------------------------------------------
+static int run_giflzw(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[4];
+        int64_t chunk = 0;
+        if (fread(head, sizeof(int32_t), 4, f) != 4 || fread(&chunk, sizeof(int64_t), 1, f) != 1 || head[0] < 0 || head[1] < 1 || head[2] < 1 ||
+            head[3] < 2 || head[3] > 8 || chunk < 1) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const size_t n_px = (size_t)head[1] * (size_t)head[2];
+        std::vector<uint8_t> plane(n_px), out;   // exactly n_px bytes: a read past the plane is a sanitizer report
+        const uint64_t bound = gif_lzw_bound((int64_t)n_px, chunk);
+        for (int k = 0; k < head[0]; ++k) {
+            if (fread(plane.data(), 1, n_px, f) != n_px) {
+                fprintf(stderr, "short record %d in %s\n", c, path);
+                return 2;
+            }
+            gif_lzw_encode(plane.data(), (int64_t)n_px, head[3], chunk, out);
+            if (out.size() > bound) {
+                printf("case %d frame %d: %zu bytes exceed the bound %llu\n", c, k, out.size(), (unsigned long long)bound);
+                return 1;
+            }
+            printf("frame %d %d %zu ", c, k, out.size());
+            for (uint8_t b : out) printf("%02x", b);
+            printf("\n");
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
     if (std::string(argv[1]) == "indexmap") return run_indexmap(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "giflzw") return run_giflzw(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

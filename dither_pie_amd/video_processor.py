@@ -17,6 +17,7 @@ same milestones (0.0, 0.05, 0.1 ... 0.9, 1.0).
 """
 from __future__ import annotations
 
+import os
 import shutil
 import subprocess
 import sys
@@ -649,6 +650,83 @@ class VideoProcessor:
             raise RuntimeError("no frame of the video could be scanned")
         self._report_progress(1.0, "Scene scan complete!")
         return scenes
+
+    def process_video_gif(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
+                          scene_palettes=None, delta=True, max_frames=None, chunk_px=None) -> int:
+        """The video as an animated GIF of palette indices (gif.GifWriter): decode -> GPU -> file, no encoder pipe and no RGB
+        frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded: the same decoder
+        line, reader thread and rotating pinned slots).  Per batch: process_frames_indexed -- piece by piece with each
+        scene's palette when scene_palettes (the list scan_scenes returns) is given, as _stream_through_pipes cuts its
+        batches --, the inter-frame delta and the LZW image data on the device, one copy of the compressed bytes to the host,
+        the container in Python.  A scene's palette that is not the first one travels as a local colour table, and the
+        delta starts over at every palette change.  Decoding a frame of the file gives process_frames of that frame (with
+        its scene's palette), exactly.  The file plays at gif.delay_cs(fps) centiseconds per frame.
+        One device: the first of `devices`; a list of several is refused (frames of one file are written in order by one
+        writer).  Failure policy: a batch that fails RAISES -- the rawvideo path's substitution of the nearest good frame is
+        not mirrored: a GIF with a silently substituted frame is worse than an error -- and so does a device failure, a
+        malformed stream or a decoder that exits with an error; the partial file is left as it is.
+        -> the number of frames written.  ValueError before the decoder starts: a bad scene list, several devices, a ditherer
+        of more than 256 colours where that is known up front, max_frames or chunk_px < 1."""
+        import copy
+        from .gif import GIF_MAX_COLOURS, GifWriter
+        if self.devices is not None and len(list(self.devices)) > 1:
+            raise ValueError(f"process_video_gif runs on one device, not on {len(list(self.devices))}: a GIF's frames are "
+                             "written in order by one writer; pass devices=[one]")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        if chunk_px is not None and int(chunk_px) < 1:
+            raise ValueError("chunk_px must be >= 1")
+        pieces_of = None
+        if scene_palettes is not None:
+            from .scenes import check_scene_palettes, scene_of, split_at
+            scene_list = check_scene_palettes(scene_palettes)
+            for sc in scene_list:
+                if len(sc.palette) > GIF_MAX_COLOURS:
+                    raise ValueError(f"the scene at frame {sc.start} has {len(sc.palette)} colours: a GIF colour table holds {GIF_MAX_COLOURS}")
+            cut_points = [int(sc.start) for sc in scene_list[1:]]
+            scene_ditherers = []
+            for sc in scene_list:
+                d = copy.copy(ditherer)
+                d.palette = [tuple(c) for c in sc.palette]
+                scene_ditherers.append(d)
+
+            def pieces_of(first, n):
+                return [(lo - first, hi - first, scene_ditherers[scene_of(scene_list, lo)]) for lo, hi in split_at(first, n, cut_points)]
+        info = self.get_video_info(input_path)
+        fps = info.get("fps") or 25.0
+        made = {}
+
+        class _BatchFailed(BaseException):   # past _batch_with_retries' `except Exception`: no frame-by-frame retry here
+            def __init__(self, error):
+                super().__init__(str(error))
+                self.error = error
+
+        def setup(dev, gpu_stream, h, w, stats):
+            oh, ow = output_size(h, w, pixelize_method, max_size, final_resize_multiplier)
+            writer = made["writer"] = GifWriter(made["file"], ow, oh, fps, 0, chunk_px)
+
+            def feed(x, first):
+                try:
+                    pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
+                    for a, b, d in pieces:
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
+                        writer.add(planes, colours, delta)
+                except Exception as e:  # noqa: BLE001
+                    raise _BatchFailed(e) from e
+            return feed
+
+        with open(output_path, "wb") as f:
+            made["file"] = f
+            try:
+                done, _ = self._scan_decoded(input_path, max_frames, setup, "GIF encode", "GIF", indexed=True)
+            except _BatchFailed as e:
+                raise e.error
+            finally:
+                if "writer" in made:
+                    made["writer"].close()
+        self.last_gif_stats = dict(self.last_scan_stats, mode="gif", bytes=os.path.getsize(output_path))
+        self._report_progress(1.0, "GIF complete!")
+        return made["writer"].n_frames
 
     def _stream_through_pipes(self, input_path, output_path, ditherer, method, max_size, batch_size,
                               final_resize_multiplier, info, run=None, overlap=True, scene_palettes=None) -> int:
