@@ -132,6 +132,16 @@ _SIGS_GIF = {
     "dp_gif_lzw_host_u8": (_i, [_vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp]),
 }
 EXPORTS_GIF = tuple(_SIGS_GIF)
+# include/ditherpie_hip_png.h: PNG-8 output (the zlib stream of index planes on the device and its host statement); a table
+# of its own for the same reason.
+_SIGS_PNG = {
+    "dp_png_filtered_bytes": (_sz, [_i, _i, _i]),
+    "dp_png_deflate_bound_bytes": (_sz, [_i, _i, _i, _i]),
+    "dp_png_deflate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "dp_png_deflate_encode_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dp_png_deflate_host_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+}
+EXPORTS_PNG = tuple(_SIGS_PNG)
 
 
 def build(force=False):
@@ -173,7 +183,7 @@ def load():
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
-                                          + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items())):
+                                          + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -1157,6 +1157,84 @@ def gif_lzw_host(planes, min_code_size, chunk_px=None):
     return [out[f, :int(sizes[f])].tobytes() for f in range(n)]
 
 
+PNG_MAX_FRAMES = 65535      # dp_png_deflate_encode_u8: frames per call
+PNG_SEG_BYTES = 8192        # the default segment of dp_png_deflate_encode_u8 (file size against parallelism)
+PNG_DEPTHS = (1, 2, 4, 8)
+
+
+def png_depth(k):
+    """The smallest PNG bit depth that holds the indices of a k-colour palette."""
+    k = int(k)
+    if k < 1 or k > 256:
+        raise ValueError(f"a PNG palette holds 1 ... 256 colours, not {k}")
+    return 1 if k <= 2 else 2 if k <= 4 else 4 if k <= 16 else 8
+
+
+def _png_args(depth, seg_bytes):
+    d, seg = int(depth), int(PNG_SEG_BYTES if seg_bytes is None else seg_bytes)
+    if d not in PNG_DEPTHS:
+        raise ValueError(f"depth must be one of {PNG_DEPTHS}, not {depth!r}")
+    if not 256 <= seg <= 32768:
+        raise ValueError(f"seg_bytes must be in 256 ... 32768, not {seg_bytes!r}")
+    return d, seg
+
+
+def png_deflate_stride(h, w, depth, seg_bytes=None):
+    """The bytes dp_png_deflate_encode_u8 may write per frame (dp_png_deflate_bound_bytes): the row length of png_deflate's
+    payload."""
+    d, seg = _png_args(depth, seg_bytes)
+    return int(_lib.load().dp_png_deflate_bound_bytes(int(h), int(w), d, seg))
+
+
+def png_deflate(planes, depth, seg_bytes=None):
+    """The zlib stream (the contents of a PNG's IDAT chunks) of one-byte index planes at bit depth `depth`, filter 0 on every
+    row (dp_png_deflate_encode_u8): uint8 CUDA planes [N,H,W] -> (payload [N, stride] uint8, sizes [N] int64), both on the
+    device.  payload[f, :sizes[f]] is frame f's stream; the bytes past sizes[f] are unspecified.  An index >= 1 << depth is
+    the caller's error (it is encoded by its low bits).  seg_bytes: filtered bytes a wave compresses on its own (default
+    PNG_SEG_BYTES).  The device encoder is the only one here: the host statement is png_deflate_host, by name.
+    Asynchronous on the current stream."""
+    p = _planes_u8(planes)
+    d, seg = _png_args(depth, seg_bytes)
+    n, h, w = p.shape
+    L = _lib.load()
+    stride = int(L.dp_png_deflate_bound_bytes(h, w, d, seg))
+    if stride == 0:
+        raise ValueError(f"planes of {h} x {w} are more than the encoder takes (filtered bytes < 2^31)")
+    payload = torch.empty((n, stride), dtype=torch.uint8, device=p.device)
+    sizes = torch.empty(n, dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        for a in range(0, n, PNG_MAX_FRAMES):
+            b = min(n, a + PNG_MAX_FRAMES)
+            need = int(L.dp_png_deflate_workspace_bytes(b - a, h, w, d, seg))
+            with _Launch(p.device, need) as ws:
+                check(L.dp_png_deflate_encode_u8(p[a:b].data_ptr(), b - a, h, w, d, seg, payload[a:b].data_ptr(), stride, sizes[a:b].data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _stream()))
+    return payload, sizes
+
+
+def png_deflate_host(planes, depth, seg_bytes=None):
+    """The same bytes from the host statement (dp_png_deflate_host_u8), no device involved: numpy uint8 planes [N,H,W] ->
+    [bytes per frame].  What the device encoder is tested against, and what png.encode_png runs on when asked to
+    (encoder="host")."""
+    p = np.ascontiguousarray(planes, dtype=np.uint8)
+    if p.ndim == 2:
+        p = p[None]
+    if p.ndim != 3 or p.shape[1] < 1 or p.shape[2] < 1:
+        raise ValueError("planes must be [N,H,W] or [H,W] with at least one pixel")
+    d, seg = _png_args(depth, seg_bytes)
+    n, h, w = p.shape
+    if n == 0:
+        return []
+    L = _lib.load()
+    stride = int(L.dp_png_deflate_bound_bytes(h, w, d, seg))
+    if stride == 0:
+        raise ValueError(f"planes of {h} x {w} are more than the encoder takes (filtered bytes < 2^31)")
+    out = np.empty((n, stride), np.uint8)
+    sizes = np.zeros(n, np.int64)
+    check(L.dp_png_deflate_host_u8(_np_ptr(p), n, h, w, d, seg, _np_ptr(out), stride, _np_ptr(sizes)))
+    return [out[f, :int(sizes[f])].tobytes() for f in range(n)]
+
+
 def profile_enable(on=True):
     check(_lib.load().dp_profile_enable(1 if on else 0))
 

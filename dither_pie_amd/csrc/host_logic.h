@@ -1588,4 +1588,213 @@ inline void gif_lzw_encode(const uint8_t *px, const int64_t n_px, const int min_
     out.push_back(0);
 }
 
+// ---- PNG-8 image data (png.hip, include/ditherpie_hip_png.h) ------------------------------------------------------------
+// The normative statement of the segmented zlib stream of one plane of palette indices: the device kernels write the bytes
+// this writes.  The pieces both sides need (the filtered byte at an offset, the trigram hash, the fixed-Huffman bits of a
+// token) are single functions compiled for host and device, so the two cannot drift apart in a table.
+//
+// Filtered bytes (never stored anywhere as a whole): row r is a filter byte 0 and ceil(w * depth / 8) packed bytes, the
+// leftmost pixel in the high-order bits, unused low bits of the last byte zero, an index taken & ((1 << depth) - 1).
+// Segments of seg_bytes filtered bytes (the last may be shorter) are compressed on their own, each into ONE data block:
+//   matcher   the candidate of position p (p + 2 < n) is the largest q < p of the segment with png_hash3 equal; its length
+//             is the number of equal bytes, at most min(258, n - p).  Greedy: at p a candidate of length >= 3 is taken and
+//             p advances by its length, else the byte is a literal.  The candidate is a function of the bytes alone.
+//   type      the smallest of stored and fixed-Huffman in bytes of the whole segment (block, and for every segment but the
+//             last the empty stored block 'pad to a byte, 00 00 FF FF' that realigns the stream); a tie goes to stored.
+//             Dynamic-Huffman blocks are not written yet: png_segment_choice is where a third cost would enter.
+// BFINAL is set on the data block of the last segment.  The stream is 78 01, the segments, Adler-32 big-endian.
+#if defined(__HIPCC__)
+#define DP_HD __host__ __device__
+#else
+#define DP_HD
+#endif
+
+constexpr int kPngSegMin = 256, kPngSegMax = 32768;
+constexpr int kPngHashBits = 12;
+constexpr uint32_t kPngNoCand = 0xFFFFu;
+constexpr uint32_t kAdlerMod = 65521u;
+constexpr int kPngStored = 0, kPngFixed = 1;   // block types in the order ties are resolved; dynamic would be 2
+
+DP_HD inline uint32_t png_hash3(const uint32_t b0, const uint32_t b1, const uint32_t b2)
+{
+    return ((b0 | (b1 << 8) | (b2 << 16)) * 0x9E3779B1u) >> (32 - kPngHashBits);
+}
+
+DP_HD inline uint32_t png_row_bytes(const int w, const int depth) { return 1u + (uint32_t)(((int64_t)w * depth + 7) / 8); }
+
+inline bool png_geometry_ok(const int h, const int w, const int depth, const int seg_bytes)
+{
+    if (h < 1 || w < 1 || !(depth == 1 || depth == 2 || depth == 4 || depth == 8) || seg_bytes < kPngSegMin || seg_bytes > kPngSegMax) return false;
+    return (int64_t)h * (int64_t)(1 + ((int64_t)w * depth + 7) / 8) < (int64_t(1) << 31);
+}
+inline int64_t png_filtered_size(const int h, const int w, const int depth) { return (int64_t)h * (int64_t)png_row_bytes(w, depth); }
+inline int64_t png_segments(const int64_t F, const int seg_bytes) { const int64_t s = std::min<int64_t>(seg_bytes, F); return (F + s - 1) / s; }
+// 2 header + every byte stored (5 bytes of block header per segment) + a 5-byte realigning block per segment + 4 trailer
+inline uint64_t png_deflate_bound(const int64_t F, const int seg_bytes) { return 2u + (uint64_t)F + 10u * (uint64_t)png_segments(F, seg_bytes) + 4u; }
+
+// the filtered byte at offset r * row_bytes + c of a plane (c < row_bytes)
+DP_HD inline uint32_t png_filtered_byte(const uint8_t *plane, const int w, const int depth, const uint32_t r, const uint32_t c)
+{
+    if (c == 0) return 0u;
+    const uint32_t ppb = 8u / (uint32_t)depth, mask = (1u << depth) - 1u;
+    const uint32_t x0 = (c - 1u) * ppb;
+    const uint8_t *row = plane + (size_t)r * (size_t)w;
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < ppb; ++k)   // <= 8
+        if (x0 + k < (uint32_t)w) v |= ((uint32_t)row[x0 + k] & mask) << (8u - (uint32_t)depth * (k + 1u));
+    return v;
+}
+
+struct PngBits {
+    uint32_t bits;   // LSB first, as they enter the stream
+    int nb;          // <= 31
+};
+
+DP_HD inline uint32_t png_rev(const uint32_t code, const int nb)   // Huffman codes enter the stream most significant bit first
+{
+    uint32_t r = 0;
+    for (int i = 0; i < nb; ++i) r |= ((code >> i) & 1u) << (nb - 1 - i);   // nb <= 9
+    return r;
+}
+
+DP_HD inline PngBits png_fixed_symbol(const uint32_t sym)   // RFC 1951 3.2.6
+{
+    PngBits t;
+    if (sym < 144u) { t.bits = png_rev(0x30u + sym, 8); t.nb = 8; }
+    else if (sym < 256u) { t.bits = png_rev(0x190u + (sym - 144u), 9); t.nb = 9; }
+    else if (sym < 280u) { t.bits = png_rev(sym - 256u, 7); t.nb = 7; }
+    else { t.bits = png_rev(0xC0u + (sym - 280u), 8); t.nb = 8; }
+    return t;
+}
+
+// length 3 ... 258 -> symbol 257 ... 285, extra bits and their value (RFC 1951 3.2.5, as arithmetic)
+DP_HD inline void png_length_code(const int len, uint32_t &sym, int &extra, uint32_t &val)
+{
+    const uint32_t l = (uint32_t)len - 3u;
+    if (len == 258) { sym = 285u; extra = 0; val = 0u; }
+    else if (l < 8u) { sym = 257u + l; extra = 0; val = 0u; }
+    else {
+        const int k = 31 - __builtin_clz(l);
+        extra = k - 2;
+        sym = 261u + 4u * (uint32_t)extra + ((l >> extra) & 3u);
+        val = l & ((1u << extra) - 1u);
+    }
+}
+
+// distance 1 ... 32768 -> code 0 ... 29, extra bits and their value
+DP_HD inline void png_dist_code(const int dist, uint32_t &code, int &extra, uint32_t &val)
+{
+    const uint32_t d = (uint32_t)dist - 1u;
+    if (d < 4u) { code = d; extra = 0; val = 0u; }
+    else {
+        const int k = 31 - __builtin_clz(d);
+        extra = k - 1;
+        code = 2u * (uint32_t)k + ((d >> extra) & 1u);
+        val = d & ((1u << extra) - 1u);
+    }
+}
+
+DP_HD inline PngBits png_fixed_literal(const uint32_t byte) { return png_fixed_symbol(byte); }
+
+DP_HD inline PngBits png_fixed_match(const int len, const int dist)   // <= 8 + 5 + 5 + 13 = 31 bits
+{
+    uint32_t sym, lval, dcode, dval;
+    int lextra, dextra;
+    png_length_code(len, sym, lextra, lval);
+    png_dist_code(dist, dcode, dextra, dval);
+    PngBits t = png_fixed_symbol(sym);
+    t.bits |= lval << t.nb;
+    t.nb += lextra;
+    t.bits |= png_rev(dcode, 5) << t.nb;
+    t.nb += 5;
+    t.bits |= dval << t.nb;
+    t.nb += dextra;
+    return t;
+}
+
+// The bytes of one segment for each block type (n data bytes; `bits` = the block's bits from its 3 header bits up to and
+// including end-of-block).  Every segment but the last carries the realigning empty stored block.
+DP_HD inline uint32_t png_stored_segment_bytes(const uint32_t n, const bool last) { return 5u + n + (last ? 0u : 5u); }
+DP_HD inline uint32_t png_huffman_segment_bytes(const uint64_t bits, const bool last) { return last ? (uint32_t)((bits + 7u) / 8u) : (uint32_t)((bits + 3u + 7u) / 8u) + 4u; }
+// the type written: the earliest of the smallest (one more argument when dynamic blocks arrive)
+DP_HD inline int png_segment_choice(const uint32_t stored_bytes, const uint32_t fixed_bytes) { return stored_bytes <= fixed_bytes ? kPngStored : kPngFixed; }
+
+// One plane -> `out` (cleared first): a complete zlib stream.  png_geometry_ok(h, w, depth, seg_bytes) is the caller's.
+inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, const int depth, const int seg_bytes, std::vector<uint8_t> &out)
+{
+    const uint32_t rb = png_row_bytes(w, depth);
+    const int64_t F = png_filtered_size(h, w, depth);
+    const int64_t seg = std::min<int64_t>(seg_bytes, F), n_seg = png_segments(F, seg_bytes);
+    out.clear();
+    out.push_back(0x78);
+    out.push_back(0x01);
+    std::vector<uint8_t> s((size_t)seg);
+    std::vector<uint32_t> cand((size_t)seg), heads((size_t)1 << kPngHashBits);
+    uint32_t A = 1, B = 0;
+    for (int64_t j = 0; j < n_seg; ++j) {
+        const int64_t at = j * seg;
+        const uint32_t n = (uint32_t)std::min<int64_t>(seg, F - at);
+        const bool last = j == n_seg - 1;
+        uint64_t s1 = 0, s2 = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t o = (uint32_t)(at + i), r = o / rb;
+            s[i] = (uint8_t)png_filtered_byte(plane, w, depth, r, o - r * rb);
+            s1 += s[i];
+            s2 += (uint64_t)(n - i) * s[i];
+        }
+        B = (uint32_t)((B + (uint64_t)n * A + s2 % kAdlerMod) % kAdlerMod);
+        A = (uint32_t)((A + s1) % kAdlerMod);
+        // candidates: a function of the bytes alone
+        std::fill(heads.begin(), heads.end(), kPngNoCand);
+        for (uint32_t p = 0; p + 2 < n; ++p) {
+            const uint32_t hsh = png_hash3(s[p], s[p + 1], s[p + 2]);
+            cand[p] = heads[hsh];
+            heads[hsh] = p;
+        }
+        GifBits bits;   // (an LSB-first bit writer)
+        uint64_t nbits = 3;
+        bits.put((last ? 1u : 0u) | (1u << 1), 3);
+        for (uint32_t p = 0; p < n;) {
+            uint32_t len = 0, q = kPngNoCand;
+            if (p + 2 < n && (q = cand[p]) != kPngNoCand) {
+                const uint32_t maxlen = std::min<uint32_t>(258u, n - p);
+                while (len < maxlen && s[q + len] == s[p + len]) ++len;
+            }
+            PngBits t;
+            if (len >= 3) {
+                t = png_fixed_match((int)len, (int)(p - q));
+                p += len;
+            } else {
+                t = png_fixed_literal(s[p]);
+                ++p;
+            }
+            bits.put(t.bits, t.nb);
+            nbits += (uint64_t)t.nb;
+        }
+        bits.put(0, 7);   // end of block: symbol 256
+        nbits += 7;
+        const uint32_t stored_bytes = png_stored_segment_bytes(n, last), fixed_bytes = png_huffman_segment_bytes(nbits, last);
+        if (png_segment_choice(stored_bytes, fixed_bytes) == kPngStored) {
+            out.push_back(last ? 1 : 0);
+            out.push_back((uint8_t)(n & 0xFFu));
+            out.push_back((uint8_t)(n >> 8));
+            out.push_back((uint8_t)(~n & 0xFFu));
+            out.push_back((uint8_t)((~n >> 8) & 0xFFu));
+            out.insert(out.end(), s.begin(), s.begin() + (std::ptrdiff_t)n);
+            if (!last) out.insert(out.end(), {0x00, 0x00, 0x00, 0xFF, 0xFF});
+        } else {
+            if (!last) {
+                bits.put(0, 3);
+                bits.flush();
+                for (const uint8_t b : {0x00, 0x00, 0xFF, 0xFF}) bits.data.push_back(b);
+            } else {
+                bits.flush();
+            }
+            out.insert(out.end(), bits.data.begin(), bits.data.end());
+        }
+    }
+    const uint32_t adler = (B << 16) | A;
+    for (int k = 3; k >= 0; --k) out.push_back((uint8_t)(adler >> (8 * k)));
+}
+
 }  // namespace dp

@@ -22,6 +22,9 @@
 //   host_xxx giflzw <cases.bin> <n>   the host statement of the GIF image data (gif_lzw_encode): the file holds n records
 //                                     {int32 n_frames, h, w, min_code_size; int64 chunk_px; n_frames x h x w index bytes}; per
 //                                     frame prints its size and its bytes in hex (compared with tests/gif_ref.py by the test)
+//   host_xxx pngdeflate <cases.bin> <n>   the host statement of the PNG-8 image data (png_deflate_encode): n records of
+//                                     int32 frames, h, w, depth, seg_bytes and frames * h * w index bytes; every frame prints
+//                                     its size and its zlib stream in hex (inflated and compared by the test)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -512,15 +515,52 @@ static int run_giflzw(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- PNG-8 image data ------------------------------------------------------------------------------------------
+static int run_pngdeflate(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[5];   // frames, h, w, depth, seg_bytes
+        if (fread(head, sizeof(int32_t), 5, f) != 5 || head[0] < 0 || !png_geometry_ok(head[1], head[2], head[3], head[4])) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const size_t n_px = (size_t)head[1] * (size_t)head[2];
+        std::vector<uint8_t> plane(n_px), out;   // exactly n_px bytes: a read past the plane is a sanitizer report
+        const uint64_t bound = png_deflate_bound(png_filtered_size(head[1], head[2], head[3]), head[4]);
+        for (int k = 0; k < head[0]; ++k) {
+            if (fread(plane.data(), 1, n_px, f) != n_px) {
+                fprintf(stderr, "short record %d in %s\n", c, path);
+                return 2;
+            }
+            png_deflate_encode(plane.data(), head[1], head[2], head[3], head[4], out);
+            if (out.size() > bound) {
+                printf("case %d frame %d: %zu bytes exceed the bound %llu\n", c, k, out.size(), (unsigned long long)bound);
+                return 1;
+            }
+            printf("frame %d %d %zu ", c, k, out.size());
+            for (uint8_t b : out) printf("%02x", b);
+            printf("\n");
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
     if (std::string(argv[1]) == "indexmap") return run_indexmap(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "giflzw") return run_giflzw(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "pngdeflate") return run_pngdeflate(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

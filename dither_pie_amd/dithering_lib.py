@@ -1214,6 +1214,30 @@ class ImageDitherer:
         out.putpalette(colours.reshape(-1).tolist(), "RGB")
         return out
 
+    def apply_dithering_png(self, image, seg_bytes=None) -> bytes:
+        """PIL image -> the bytes of a PNG-8 file whose decoding equals apply_dithering(image), exactly.  Host-in as
+        apply_dithering_indexed; the index plane never comes back: it is compressed where it lies (png.encode_png: the
+        zlib stream on the device, the container and its CRCs in Python) and only the compressed stream crosses to the
+        host.  ValueError above 256 colours."""
+        from . import png
+        rgb = image if image.mode == "RGB" else image.convert("RGB")
+        w, h = rgb.size
+        if w < 1 or h < 1:
+            raise ValueError("a PNG has at least one pixel")
+        if self.palette is None:
+            self._ensure_palette(np.asarray(rgb))
+        if len(self.palette) > 256:
+            raise ValueError(f"a PNG palette holds at most 256 colours, the palette has {len(self.palette)}")
+        pin_in, _ = _pinned_pair(h * w * 4)
+        if _pil_rgbx_into(rgb, pin_in.numpy()):
+            dev_in = pin_in.view(h, w, 4).cuda(non_blocking=True)[..., :3].contiguous()
+        else:
+            host_in = pin_in[:h * w * 3]
+            np.copyto(host_in.numpy(), np.frombuffer(rgb.tobytes(), dtype=np.uint8))
+            dev_in = host_in.view(h, w, 3).cuda(non_blocking=True)
+        planes, colours = self.apply_dithering_frames_indexed(dev_in)
+        return png.encode_png(planes, colours, seg_bytes)[0]
+
     def prepare(self, device=None, accel=True):
         """Create the device-side palette now (and, with accel=True, its search accelerator: ~3.5 ms once) instead of on
         first use / once enough pixels have been served -- for long-running jobs (a video) that know what is coming.

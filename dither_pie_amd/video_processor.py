@@ -128,6 +128,16 @@ def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Opt
     return planes, colours
 
 
+def process_frames_png(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
+                       final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None):
+    """process_frames() as PNG-8 files: uint8 CUDA tensor [N,H,W,3] -> [bytes of one PNG file per frame]; decoding file i
+    gives process_frames(...)[i], exactly.  process_frames_indexed, then png.encode_png: the planes are compressed on the
+    device and only the compressed streams come back.  ValueError above 256 colours."""
+    from . import png
+    planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier)
+    return png.encode_png(planes, colours, seg_bytes)
+
+
 def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_method: Optional[str] = None,
                           max_size: int = 64, final_resize_multiplier: Optional[int] = None) -> bool:
     """One PNG in place; True on success, False (with a message on stderr) on any error
@@ -727,6 +737,82 @@ class VideoProcessor:
         self.last_gif_stats = dict(self.last_scan_stats, mode="gif", bytes=os.path.getsize(output_path))
         self._report_progress(1.0, "GIF complete!")
         return made["writer"].n_frames
+
+    def process_video_pngs(self, input_path, out_pattern, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
+                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1) -> int:
+        """The video as a sequence of PNG-8 files out_pattern % start, out_pattern % (start + 1), ... (the 'frame_%05d.png'
+        of a frame directory): decode -> GPU -> files, no encoder pipe and no RGB frames on the way out.  Built on the
+        decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as process_video_gif is.  Per batch:
+        process_frames_indexed -- piece by piece with each scene's palette when scene_palettes (the list scan_scenes
+        returns) is given --, the zlib streams on the device, one copy of the compressed bytes to the host, the containers
+        in Python.  Decoding file i gives process_frames of frame i (with its scene's palette), exactly.
+        One device: the first of `devices`; a list of several is refused.  Failure policy as process_video_gif: a batch that
+        fails RAISES, and so does a device failure, a malformed stream or a decoder that exits with an error; the files
+        written so far are left as they are.
+        -> the number of files written.  ValueError before the decoder starts: a bad scene list, several devices, a ditherer
+        or scene of more than 256 colours where that is known up front, max_frames < 1, seg_bytes outside 256 ... 32768, a
+        pattern that does not format an integer."""
+        import copy
+        from .png import PNG_MAX_COLOURS, encode_png
+        if self.devices is not None and len(list(self.devices)) > 1:
+            raise ValueError(f"process_video_pngs runs on one device, not on {len(list(self.devices))}: the files are "
+                             "numbered in order by one writer; pass devices=[one]")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        if seg_bytes is not None and not 256 <= int(seg_bytes) <= 32768:
+            raise ValueError("seg_bytes must be in 256 ... 32768")
+        try:
+            if str(out_pattern) % 1 == str(out_pattern) % 2:
+                raise TypeError("no field")
+        except (TypeError, ValueError):
+            raise ValueError(f"out_pattern must format a frame number (as 'frame_%05d.png'), not {out_pattern!r}") from None
+        if getattr(ditherer, "palette", None) is not None and len(ditherer.palette) > PNG_MAX_COLOURS:
+            raise ValueError(f"the ditherer has {len(ditherer.palette)} colours: a PNG palette holds {PNG_MAX_COLOURS}")
+        pieces_of = None
+        if scene_palettes is not None:
+            from .scenes import check_scene_palettes, scene_of, split_at
+            scene_list = check_scene_palettes(scene_palettes)
+            for sc in scene_list:
+                if len(sc.palette) > PNG_MAX_COLOURS:
+                    raise ValueError(f"the scene at frame {sc.start} has {len(sc.palette)} colours: a PNG palette holds {PNG_MAX_COLOURS}")
+            cut_points = [int(sc.start) for sc in scene_list[1:]]
+            scene_ditherers = []
+            for sc in scene_list:
+                d = copy.copy(ditherer)
+                d.palette = [tuple(c) for c in sc.palette]
+                scene_ditherers.append(d)
+
+            def pieces_of(first, n):
+                return [(lo - first, hi - first, scene_ditherers[scene_of(scene_list, lo)]) for lo, hi in split_at(first, n, cut_points)]
+        made = {"written": 0, "bytes": 0}
+
+        class _BatchFailed(BaseException):   # past _batch_with_retries' `except Exception`: no frame-by-frame retry here
+            def __init__(self, error):
+                super().__init__(str(error))
+                self.error = error
+
+        def setup(dev, gpu_stream, h, w, stats):
+            def feed(x, first):
+                try:
+                    pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
+                    for a, b, d in pieces:
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
+                        for k, data in enumerate(encode_png(planes, colours, seg_bytes)):
+                            with open(str(out_pattern) % (int(start) + first + a + k), "wb") as f:
+                                f.write(data)
+                            made["written"] += 1
+                            made["bytes"] += len(data)
+                except Exception as e:  # noqa: BLE001
+                    raise _BatchFailed(e) from e
+            return feed
+
+        try:
+            self._scan_decoded(input_path, max_frames, setup, "PNG encode", "PNG sequence", indexed=True)
+        except _BatchFailed as e:
+            raise e.error
+        self.last_png_stats = dict(self.last_scan_stats, mode="png", bytes=made["bytes"])
+        self._report_progress(1.0, "PNG sequence complete!")
+        return made["written"]
 
     def _stream_through_pipes(self, input_path, output_path, ditherer, method, max_size, batch_size,
                               final_resize_multiplier, info, run=None, overlap=True, scene_palettes=None) -> int:
