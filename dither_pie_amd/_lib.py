@@ -142,6 +142,16 @@ _SIGS_PNG = {
     "dp_png_deflate_host_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
 }
 EXPORTS_PNG = tuple(_SIGS_PNG)
+# include/ditherpie_hip_png_dyn.h: dynamic-Huffman blocks for the PNG-8 output and the code construction on its own; a table of
+# its own for the same reason.
+_SIGS_PNG_DYN = {
+    "dp_png_deflate_dyn_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "dp_png_deflate_dyn_encode_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dp_png_deflate_dyn_host_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "dp_png_code_lengths_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "dp_png_code_lengths_host": (_i, [_vp, _i, _i, _i, _vp]),
+}
+EXPORTS_PNG_DYN = tuple(_SIGS_PNG_DYN)
 
 
 def build(force=False):
@@ -183,7 +193,8 @@ def load():
                     raise DitherPieError(-1, f"{LIB_PATH} reports ABI version {got}, this binding was written for "
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
-                                          + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())):
+                                          + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
+                                          + list(_SIGS_PNG_DYN.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -1160,6 +1160,8 @@ def gif_lzw_host(planes, min_code_size, chunk_px=None):
 PNG_MAX_FRAMES = 65535      # dp_png_deflate_encode_u8: frames per call
 PNG_SEG_BYTES = 8192        # the default segment of dp_png_deflate_encode_u8 (file size against parallelism)
 PNG_DEPTHS = (1, 2, 4, 8)
+PNG_BLOCKS = ("fixed", "dynamic")   # block types beside stored: "dynamic" adds dynamic-Huffman blocks (ditherpie_hip_png_dyn.h)
+PNG_CODE_MAX_COUNT = 1 << 20        # dp_png_code_lengths_*: the largest count of a histogram
 
 
 def png_depth(k):
@@ -1179,6 +1181,12 @@ def _png_args(depth, seg_bytes):
     return d, seg
 
 
+def _png_blocks(blocks):
+    if blocks not in PNG_BLOCKS:
+        raise ValueError(f"blocks must be one of {PNG_BLOCKS}, not {blocks!r}")
+    return blocks == "dynamic"
+
+
 def png_deflate_stride(h, w, depth, seg_bytes=None):
     """The bytes dp_png_deflate_encode_u8 may write per frame (dp_png_deflate_bound_bytes): the row length of png_deflate's
     payload."""
@@ -1186,17 +1194,21 @@ def png_deflate_stride(h, w, depth, seg_bytes=None):
     return int(_lib.load().dp_png_deflate_bound_bytes(int(h), int(w), d, seg))
 
 
-def png_deflate(planes, depth, seg_bytes=None):
+def png_deflate(planes, depth, seg_bytes=None, blocks="fixed"):
     """The zlib stream (the contents of a PNG's IDAT chunks) of one-byte index planes at bit depth `depth`, filter 0 on every
     row (dp_png_deflate_encode_u8): uint8 CUDA planes [N,H,W] -> (payload [N, stride] uint8, sizes [N] int64), both on the
     device.  payload[f, :sizes[f]] is frame f's stream; the bytes past sizes[f] are unspecified.  An index >= 1 << depth is
     the caller's error (it is encoded by its low bits).  seg_bytes: filtered bytes a wave compresses on its own (default
-    PNG_SEG_BYTES).  The device encoder is the only one here: the host statement is png_deflate_host, by name.
-    Asynchronous on the current stream."""
+    PNG_SEG_BYTES).  blocks: "fixed" writes stored and fixed-Huffman blocks, "dynamic" dynamic-Huffman blocks as well
+    (dp_png_deflate_dyn_encode_u8: smaller streams, a larger workspace).  The device encoder is the only one here: the host
+    statement is png_deflate_host, by name.  Asynchronous on the current stream."""
+    dyn = _png_blocks(blocks)
     p = _planes_u8(planes)
     d, seg = _png_args(depth, seg_bytes)
     n, h, w = p.shape
     L = _lib.load()
+    ws_bytes, encode = ((L.dp_png_deflate_dyn_workspace_bytes, L.dp_png_deflate_dyn_encode_u8) if dyn else
+                        (L.dp_png_deflate_workspace_bytes, L.dp_png_deflate_encode_u8))
     stride = int(L.dp_png_deflate_bound_bytes(h, w, d, seg))
     if stride == 0:
         raise ValueError(f"planes of {h} x {w} are more than the encoder takes (filtered bytes < 2^31)")
@@ -1205,17 +1217,18 @@ def png_deflate(planes, depth, seg_bytes=None):
     with torch.cuda.device(p.device):
         for a in range(0, n, PNG_MAX_FRAMES):
             b = min(n, a + PNG_MAX_FRAMES)
-            need = int(L.dp_png_deflate_workspace_bytes(b - a, h, w, d, seg))
+            need = int(ws_bytes(b - a, h, w, d, seg))
             with _Launch(p.device, need) as ws:
-                check(L.dp_png_deflate_encode_u8(p[a:b].data_ptr(), b - a, h, w, d, seg, payload[a:b].data_ptr(), stride, sizes[a:b].data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _stream()))
+                check(encode(p[a:b].data_ptr(), b - a, h, w, d, seg, payload[a:b].data_ptr(), stride, sizes[a:b].data_ptr(), ws.data_ptr(),
+                             ws.numel(), _stream()))
     return payload, sizes
 
 
-def png_deflate_host(planes, depth, seg_bytes=None):
-    """The same bytes from the host statement (dp_png_deflate_host_u8), no device involved: numpy uint8 planes [N,H,W] ->
-    [bytes per frame].  What the device encoder is tested against, and what png.encode_png runs on when asked to
-    (encoder="host")."""
+def png_deflate_host(planes, depth, seg_bytes=None, blocks="fixed"):
+    """The same bytes from the host statement (dp_png_deflate_host_u8, or dp_png_deflate_dyn_host_u8 for blocks="dynamic"), no
+    device involved: numpy uint8 planes [N,H,W] -> [bytes per frame].  What the device encoder is tested against, and what
+    png.encode_png runs on when asked to (encoder="host")."""
+    dyn = _png_blocks(blocks)
     p = np.ascontiguousarray(planes, dtype=np.uint8)
     if p.ndim == 2:
         p = p[None]
@@ -1231,8 +1244,50 @@ def png_deflate_host(planes, depth, seg_bytes=None):
         raise ValueError(f"planes of {h} x {w} are more than the encoder takes (filtered bytes < 2^31)")
     out = np.empty((n, stride), np.uint8)
     sizes = np.zeros(n, np.int64)
-    check(L.dp_png_deflate_host_u8(_np_ptr(p), n, h, w, d, seg, _np_ptr(out), stride, _np_ptr(sizes)))
+    host = L.dp_png_deflate_dyn_host_u8 if dyn else L.dp_png_deflate_host_u8
+    check(host(_np_ptr(p), n, h, w, d, seg, _np_ptr(out), stride, _np_ptr(sizes)))
     return [out[f, :int(sizes[f])].tobytes() for f in range(n)]
+
+
+def _code_length_args(shape, max_len):
+    L = int(max_len)
+    if len(shape) != 2 or not 2 <= shape[1] <= 286:
+        raise ValueError("counts must be [n_alphabets, n_symbols] with 2 ... 286 symbols")
+    if not 1 <= L <= 15 or (1 << L) < shape[1]:
+        raise ValueError(f"max_len must be in 1 ... 15 with 2^max_len >= {shape[1]} symbols, not {max_len!r}")
+    return L
+
+
+def png_code_lengths(counts, max_len):
+    """Length-limited Huffman code lengths as the PNG encoder builds them (dp_png_code_lengths_u8, one wave per histogram):
+    CUDA counts [A, M] (or [M]) of integers 0 ... PNG_CODE_MAX_COUNT -> uint8 lengths of the same shape, on the device.  A
+    count outside that range is the caller's error.  Asynchronous on the current stream."""
+    if not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype.is_floating_point:
+        raise ValueError("counts must be a CUDA tensor of integers")
+    one = counts.ndim == 1
+    c = (counts[None] if one else counts).to(torch.int32).contiguous()
+    L = _code_length_args(tuple(c.shape), max_len)
+    out = torch.empty(c.shape, dtype=torch.uint8, device=c.device)
+    if c.shape[0] == 0:                                                 # (an empty tensor has no address to pass)
+        return out
+    with torch.cuda.device(c.device):
+        check(_lib.load().dp_png_code_lengths_u8(c.data_ptr(), c.shape[0], c.shape[1], L, out.data_ptr(), _stream()))
+    return out[0] if one else out
+
+
+def png_code_lengths_host(counts, max_len):
+    """The same from the host statement (dp_png_code_lengths_host): array-like counts [A, M] (or [M]) -> numpy uint8 lengths."""
+    c = np.asarray(counts)
+    one = c.ndim == 1
+    c = c[None] if one else c
+    L = _code_length_args(c.shape, max_len)
+    if c.size and (c.min() < 0 or c.max() > PNG_CODE_MAX_COUNT):
+        raise ValueError(f"counts must be in 0 ... {PNG_CODE_MAX_COUNT}")
+    c = np.ascontiguousarray(c, dtype=np.uint32)
+    out = np.zeros(c.shape, np.uint8)
+    if c.shape[0]:
+        check(_lib.load().dp_png_code_lengths_host(_np_ptr(c), c.shape[0], c.shape[1], L, _np_ptr(out)))
+    return out[0] if one else out
 
 
 def profile_enable(on=True):

@@ -1601,7 +1601,8 @@ inline void gif_lzw_encode(const uint8_t *px, const int64_t n_px, const int min_
 //             p advances by its length, else the byte is a literal.  The candidate is a function of the bytes alone.
 //   type      the smallest of stored and fixed-Huffman in bytes of the whole segment (block, and for every segment but the
 //             last the empty stored block 'pad to a byte, 00 00 FF FF' that realigns the stream); a tie goes to stored.
-//             Dynamic-Huffman blocks are not written yet: png_segment_choice is where a third cost would enter.
+//             png_deflate_encode_dyn (below) adds one dynamic-Huffman block over the same tokens as a third candidate;
+//             png_deflate_encode writes stored and fixed blocks only, and its bytes do not change.
 // BFINAL is set on the data block of the last segment.  The stream is 78 01, the segments, Adler-32 big-endian.
 #if defined(__HIPCC__)
 #define DP_HD __host__ __device__
@@ -1613,7 +1614,7 @@ constexpr int kPngSegMin = 256, kPngSegMax = 32768;
 constexpr int kPngHashBits = 12;
 constexpr uint32_t kPngNoCand = 0xFFFFu;
 constexpr uint32_t kAdlerMod = 65521u;
-constexpr int kPngStored = 0, kPngFixed = 1;   // block types in the order ties are resolved; dynamic would be 2
+constexpr int kPngStored = 0, kPngFixed = 1, kPngDynamic = 2;   // block types in the order ties are resolved
 
 DP_HD inline uint32_t png_hash3(const uint32_t b0, const uint32_t b1, const uint32_t b2)
 {
@@ -1716,11 +1717,301 @@ DP_HD inline PngBits png_fixed_match(const int len, const int dist)   // <= 8 + 
 // including end-of-block).  Every segment but the last carries the realigning empty stored block.
 DP_HD inline uint32_t png_stored_segment_bytes(const uint32_t n, const bool last) { return 5u + n + (last ? 0u : 5u); }
 DP_HD inline uint32_t png_huffman_segment_bytes(const uint64_t bits, const bool last) { return last ? (uint32_t)((bits + 7u) / 8u) : (uint32_t)((bits + 3u + 7u) / 8u) + 4u; }
-// the type written: the earliest of the smallest (one more argument when dynamic blocks arrive)
+// the type written: the earliest of the smallest
 DP_HD inline int png_segment_choice(const uint32_t stored_bytes, const uint32_t fixed_bytes) { return stored_bytes <= fixed_bytes ? kPngStored : kPngFixed; }
 
+DP_HD inline int png_segment_choice(const uint32_t stored_bytes, const uint32_t fixed_bytes, const uint32_t dynamic_bytes)
+{
+    const int two = png_segment_choice(stored_bytes, fixed_bytes);
+    return dynamic_bytes < (two == kPngStored ? stored_bytes : fixed_bytes) ? kPngDynamic : two;
+}
+
+// ---- Dynamic-Huffman blocks (include/ditherpie_hip_png_dyn.h) --------------------------------------------------------------
+// One dynamic block (BTYPE 10) over the tokens of a segment is the third candidate of png_segment_choice.  Everything that
+// decides a bit is a DP_HD function here, run by the host statement and by the device alike; the device replaces only the
+// sort of rule (b) and the sums of the size by wave-parallel ones (png.hip).
+//
+// Code lengths of an alphabet with counts c[0 .. m) and limit L (15 for literal/length and distance, 7 for the code-length
+// alphabet):
+//   (a) while fewer than two symbols have a count, the lowest-numbered symbol with count 0 gets count 1
+//   (b) the used symbols ascending by (count, symbol): one 32-bit key count << 9 | symbol each (counts <= 2^20)
+//   (c) two-queue Huffman merge: the front leaf is taken when its weight is <= the front internal node's; internal nodes in
+//       creation order; a leaf's depth is its length
+//   (d) num[d] = leaves per depth, depths above L counted at L; total = sum num[i] << (L - i); while total > 2^L:
+//       num[L]--, for the largest i < L with num[i] > 0: num[i]--, num[i + 1] += 2; total--   (at most once per symbol)
+//   (e) lengths from num in sorted order: the first num[L] symbols get L, the next num[L - 1] get L - 1, ...
+//   (f) canonical codes, RFC 1951 3.2.2
+// Loops: the merge n - 1 <= 285 rounds, depths and (e) <= 286, (d) <= 286 rounds of <= 15, codes <= 286.
+constexpr int kPngLit = 286, kPngDist = 30, kPngCl = 19;
+constexpr int kPngLens = kPngLit + kPngDist;       // the two length lists, the distance list at kPngLit
+constexpr uint32_t kPngMaxCount = 1u << 20;
+constexpr uint32_t kPngUnusedKey = 0xC0000000u;    // keys of unused symbols sort behind every used one
+
+struct PngCodeScratch {
+    uint32_t keys[kPngLit];     // by symbol
+    uint32_t sorted[kPngLit];   // ascending, the used ones first
+    uint32_t w[kPngLit];        // weights of the internal nodes, then their depths
+    uint16_t lp[kPngLit];       // the internal node a leaf hangs on
+    uint16_t ip[kPngLit];       // ... an internal node hangs on
+};
+
+DP_HD inline uint32_t png_code_key(const uint32_t count, const uint32_t sym)
+{
+    const uint32_t c = count < kPngMaxCount ? count : kPngMaxCount;
+    return c ? (c << 9) | sym : kPngUnusedKey | sym;
+}
+
+// rule (a) on the keys (the counts themselves stay what was counted); -> the number of used symbols.  m >= 2.
+DP_HD inline int png_pad_keys(uint32_t *keys, const int m)
+{
+    int used = 0;
+    for (int s = 0; s < m; ++s) used += keys[s] < kPngUnusedKey;
+    for (int s = 0; s < m && used < 2; ++s)
+        if (keys[s] >= kPngUnusedKey) {
+            keys[s] = png_code_key(1u, (uint32_t)s);
+            ++used;
+        }
+    return used;
+}
+
+// rules (c), (d), (e) on the sorted keys of n >= 2 used symbols out of m; 2^L >= n
+DP_HD inline void png_code_lengths_sorted(const uint32_t *sorted, const int n, const int m, const int L, uint8_t *lengths, uint32_t *w,
+                                          uint16_t *lp, uint16_t *ip)
+{
+    for (int s = 0; s < m; ++s) lengths[s] = 0;
+    int li = 0, ni = 0;
+    for (int k = 0; k < n - 1; ++k) {   // node k is made of the two lightest
+        uint32_t sum = 0;
+        for (int two = 0; two < 2; ++two) {
+            if (li < n && (ni >= k || (sorted[li] >> 9) <= w[ni])) {
+                lp[li] = (uint16_t)k;
+                sum += sorted[li] >> 9;
+                ++li;
+            } else {
+                ip[ni] = (uint16_t)k;
+                sum += w[ni];
+                ++ni;
+            }
+        }
+        w[k] = sum;
+    }
+    w[n - 2] = 0;   // the root; from here on w[] holds depths
+    for (int k = n - 3; k >= 0; --k) w[k] = w[ip[k]] + 1u;
+    uint32_t num[16];
+    for (int d = 0; d < 16; ++d) num[d] = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t d = w[lp[i]] + 1u;
+        ++num[d < (uint32_t)L ? d : (uint32_t)L];
+    }
+    uint32_t total = 0;
+    for (int i = 1; i <= L; ++i) total += num[i] << (L - i);
+    for (int round = 0; round < n && total > (1u << L); ++round) {
+        --num[L];
+        for (int i = L - 1; i > 0; --i)
+            if (num[i]) {
+                --num[i];
+                num[i + 1] += 2;
+                break;
+            }
+        --total;
+    }
+    int at = 0;
+    for (int d = L; d > 0; --d)
+        for (uint32_t k = 0; k < num[d] && at < n; ++k, ++at) lengths[sorted[at] & 511u] = (uint8_t)d;
+}
+
+// rule (f): codes[s] = the code as it enters the stream (first bit lowest) | length << 16
+DP_HD inline void png_canonical_codes(const uint8_t *lengths, const int m, uint32_t *codes)
+{
+    uint32_t count[16], next[16];
+    for (int b = 0; b < 16; ++b) count[b] = 0;
+    for (int s = 0; s < m; ++s) ++count[lengths[s] & 15];
+    count[0] = 0;
+    uint32_t code = 0;
+    next[0] = 0;
+    for (int b = 1; b < 16; ++b) {
+        code = (code + count[b - 1]) << 1;
+        next[b] = code;
+    }
+    for (int s = 0; s < m; ++s) {
+        const int nb = lengths[s] & 15;
+        codes[s] = nb ? png_rev(next[nb]++, nb) | ((uint32_t)nb << 16) : 0u;
+    }
+}
+
+// HLIT = max(257, the highest literal/length symbol with a length + 1); HDIST = the highest distance symbol with one + 1
+DP_HD inline int png_hlit(const uint8_t *lit)
+{
+    int n = kPngLit;
+    while (n > 257 && lit[n - 1] == 0) --n;
+    return n;
+}
+DP_HD inline int png_hdist(const uint8_t *dist)
+{
+    int n = kPngDist;
+    while (n > 1 && dist[n - 1] == 0) --n;
+    return n;
+}
+
+DP_HD inline int png_cl_extra(const uint32_t sym) { return sym == 16u ? 2 : sym == 17u ? 3 : sym == 18u ? 7 : 0; }
+
+// The two length lists as one sequence (runs cross the boundary), run-length coded greedily: a run of r zeros at i is symbol
+// 18 over min(r, 138) when r >= 11, symbol 17 over r when r >= 3, else one literal 0; a run of a length v is the literal v and,
+// while the rest is >= 3, symbol 16 over min(rest, 6) -- a rest of 1 or 2 is met again as a run of its own.
+// seq[k] = symbol | extra value << 5; cl_counts[19] receives the histogram; -> the number of entries (<= hlit + hdist).
+DP_HD inline int png_cl_sequence(const uint8_t *lit, const int hlit, const uint8_t *dist, const int hdist, uint16_t *seq, uint32_t *cl_counts)
+{
+    for (int s = 0; s < kPngCl; ++s) cl_counts[s] = 0;
+    const int total = hlit + hdist;
+    int nseq = 0;
+    for (int i = 0; i < total;) {   // <= 316
+        const uint32_t v = i < hlit ? lit[i] : dist[i - hlit];
+        int r = 1;
+        while (i + r < total && (i + r < hlit ? lit[i + r] : dist[i + r - hlit]) == v) ++r;
+        uint32_t sym, val = 0;
+        int covered;
+        if (v == 0 && r >= 11) { covered = r < 138 ? r : 138; sym = 18u; val = (uint32_t)covered - 11u; }
+        else if (v == 0 && r >= 3) { covered = r; sym = 17u; val = (uint32_t)r - 3u; }
+        else { covered = 1; sym = v; }
+        seq[nseq++] = (uint16_t)(sym | (val << 5));
+        ++cl_counts[sym];
+        i += covered;
+        if (v != 0)
+            for (int rest = r - 1; rest >= 3;) {
+                const int k = rest < 6 ? rest : 6;
+                seq[nseq++] = (uint16_t)(16u | ((uint32_t)(k - 3) << 5));
+                ++cl_counts[16];
+                i += k;
+                rest -= k;
+            }
+    }
+    return nseq;
+}
+
+DP_HD inline uint32_t png_cl_order(const int i)   // RFC 1951 3.2.7: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
+{
+    return i < 3 ? 16u + (uint32_t)i : i == 3 ? 0u : (i & 1) ? 8u - (uint32_t)((i - 3) / 2) : 8u + (uint32_t)((i - 4) / 2);
+}
+
+DP_HD inline int png_hclen(const uint8_t *cl)   // max(4, 1 + the last index of the order whose symbol has a length)
+{
+    int n = kPngCl;
+    while (n > 4 && cl[png_cl_order(n - 1)] == 0) --n;
+    return n;
+}
+
+// the bits of one entry of the code-length sequence: its code, then its extra bits (<= 7 + 7)
+DP_HD inline PngBits png_cl_entry(const uint32_t entry, const uint32_t *cl_codes)
+{
+    const uint32_t sym = entry & 31u, c = cl_codes[sym];
+    PngBits t;
+    t.nb = (int)(c >> 16);
+    t.bits = (c & 0xFFFFu) | ((entry >> 5) << t.nb);
+    t.nb += png_cl_extra(sym);
+    return t;
+}
+
+// A token as one word (the device's token area holds these): a literal is its byte; a match is bit 31, the length in bits
+// 0 ... 8 and the distance - 1 in bits 9 ... 23.
+DP_HD inline uint32_t png_token_literal(const uint32_t byte) { return byte; }
+DP_HD inline uint32_t png_token_match(const int len, const int dist) { return 0x80000000u | (uint32_t)len | ((uint32_t)(dist - 1) << 9); }
+
+DP_HD inline PngBits png_fixed_token(const uint32_t word)
+{
+    return (word >> 31) ? png_fixed_match((int)(word & 511u), (int)((word >> 9) & 0x7FFFu) + 1) : png_fixed_literal(word & 255u);
+}
+
+struct PngBits64 {
+    uint64_t bits;   // LSB first
+    int nb;          // <= 15 + 5 + 15 + 13 = 48
+};
+
+DP_HD inline PngBits64 png_dynamic_token(const uint32_t word, const uint32_t *lit_codes, const uint32_t *dist_codes)
+{
+    PngBits64 t;
+    if (!(word >> 31)) {
+        const uint32_t c = lit_codes[word & 255u];
+        t.bits = c & 0xFFFFu;
+        t.nb = (int)(c >> 16);
+        return t;
+    }
+    uint32_t sym, lval, dcode, dval;
+    int lextra, dextra;
+    png_length_code((int)(word & 511u), sym, lextra, lval);
+    png_dist_code((int)((word >> 9) & 0x7FFFu) + 1, dcode, dextra, dval);
+    const uint32_t lc = lit_codes[sym], dc = dist_codes[dcode];
+    t.bits = lc & 0xFFFFu;
+    t.nb = (int)(lc >> 16);
+    t.bits |= (uint64_t)lval << t.nb;
+    t.nb += lextra;
+    t.bits |= (uint64_t)(dc & 0xFFFFu) << t.nb;
+    t.nb += (int)(dc >> 16);
+    t.bits |= (uint64_t)dval << t.nb;
+    t.nb += dextra;
+    return t;
+}
+
+// what a token adds to the histograms (hist[0 .. 286) literal/length, hist[286 .. 316) distance) and to the two bit totals
+DP_HD inline void png_token_symbols(const uint32_t word, uint32_t &lit_sym, int &dist_sym, int &extra_bits, int &fixed_bits)
+{
+    if (!(word >> 31)) {
+        lit_sym = word & 255u;
+        dist_sym = -1;
+        extra_bits = 0;
+        fixed_bits = lit_sym < 144u ? 8 : 9;
+        return;
+    }
+    uint32_t lval, dcode, dval;
+    int lextra, dextra;
+    png_length_code((int)(word & 511u), lit_sym, lextra, lval);
+    png_dist_code((int)((word >> 9) & 0x7FFFu) + 1, dcode, dextra, dval);
+    dist_sym = (int)dcode;
+    extra_bits = lextra + dextra;
+    fixed_bits = (lit_sym < 280u ? 7 : 8) + 5 + extra_bits;
+}
+
+// rule (a) ... (e) for one alphabet on the host (the device sorts with the wave: png.hip)
+inline void png_code_lengths(const uint32_t *counts, const int m, const int L, uint8_t *lengths, PngCodeScratch &sc)
+{
+    for (int s = 0; s < m; ++s) sc.keys[s] = png_code_key(counts[s], (uint32_t)s);
+    const int n = png_pad_keys(sc.keys, m);
+    std::copy(sc.keys, sc.keys + m, sc.sorted);
+    std::sort(sc.sorted, sc.sorted + m);
+    png_code_lengths_sorted(sc.sorted, n, m, L, lengths, sc.w, sc.lp, sc.ip);
+}
+
+// Everything a dynamic block's header says, and the block's bits from its three header bits through end-of-block, from the
+// histograms (hist[256] == 1), the extra-bit total and the code lengths alone.
+struct PngDynPlan {
+    uint8_t lens[kPngLens + kPngCl];   // literal/length, distance at kPngLit, code-length alphabet at kPngLens
+    uint32_t codes[kPngLens + kPngCl];
+    uint16_t seq[kPngLens];
+    int hlit, hdist, hclen, nseq;
+    uint64_t bits;
+};
+
+inline void png_dynamic_plan(const uint32_t *hist, const uint64_t extra_bits, PngDynPlan &p, PngCodeScratch &sc)
+{
+    uint32_t cl_counts[kPngCl];
+    png_code_lengths(hist, kPngLit, 15, p.lens, sc);
+    png_code_lengths(hist + kPngLit, kPngDist, 15, p.lens + kPngLit, sc);
+    p.hlit = png_hlit(p.lens);
+    p.hdist = png_hdist(p.lens + kPngLit);
+    p.nseq = png_cl_sequence(p.lens, p.hlit, p.lens + kPngLit, p.hdist, p.seq, cl_counts);
+    png_code_lengths(cl_counts, kPngCl, 7, p.lens + kPngLens, sc);
+    p.hclen = png_hclen(p.lens + kPngLens);
+    p.bits = 3u + 5u + 5u + 4u + 3u * (uint64_t)p.hclen + extra_bits;
+    for (int k = 0; k < p.nseq; ++k) p.bits += (uint64_t)p.lens[kPngLens + (p.seq[k] & 31u)] + (uint64_t)png_cl_extra(p.seq[k] & 31u);
+    for (int s = 0; s < kPngLens; ++s) p.bits += (uint64_t)hist[s] * p.lens[s];
+    png_canonical_codes(p.lens, kPngLit, p.codes);
+    png_canonical_codes(p.lens + kPngLit, kPngDist, p.codes + kPngLit);
+    png_canonical_codes(p.lens + kPngLens, kPngCl, p.codes + kPngLens);
+}
+
 // One plane -> `out` (cleared first): a complete zlib stream.  png_geometry_ok(h, w, depth, seg_bytes) is the caller's.
-inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, const int depth, const int seg_bytes, std::vector<uint8_t> &out)
+// dynamic == false: stored and fixed blocks (png_deflate_encode); true: the third candidate as well (png_deflate_encode_dyn).
+inline void png_deflate_encode_blocks(const uint8_t *plane, const int h, const int w, const int depth, const int seg_bytes, const bool dynamic,
+                                      std::vector<uint8_t> &out)
 {
     const uint32_t rb = png_row_bytes(w, depth);
     const int64_t F = png_filtered_size(h, w, depth);
@@ -1729,7 +2020,11 @@ inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, c
     out.push_back(0x78);
     out.push_back(0x01);
     std::vector<uint8_t> s((size_t)seg);
-    std::vector<uint32_t> cand((size_t)seg), heads((size_t)1 << kPngHashBits);
+    std::vector<uint32_t> cand((size_t)seg), heads((size_t)1 << kPngHashBits), toks;
+    std::vector<uint32_t> hist((size_t)kPngLens);
+    PngCodeScratch sc;
+    PngDynPlan plan;
+    toks.reserve((size_t)seg);
     uint32_t A = 1, B = 0;
     for (int64_t j = 0; j < n_seg; ++j) {
         const int64_t at = j * seg;
@@ -1751,30 +2046,41 @@ inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, c
             cand[p] = heads[hsh];
             heads[hsh] = p;
         }
-        GifBits bits;   // (an LSB-first bit writer)
-        uint64_t nbits = 3;
-        bits.put((last ? 1u : 0u) | (1u << 1), 3);
+        toks.clear();
+        std::fill(hist.begin(), hist.end(), 0u);
+        uint64_t fixed_bits = 3, extra_bits = 0;
         for (uint32_t p = 0; p < n;) {
             uint32_t len = 0, q = kPngNoCand;
             if (p + 2 < n && (q = cand[p]) != kPngNoCand) {
                 const uint32_t maxlen = std::min<uint32_t>(258u, n - p);
                 while (len < maxlen && s[q + len] == s[p + len]) ++len;
             }
-            PngBits t;
+            uint32_t word;
             if (len >= 3) {
-                t = png_fixed_match((int)len, (int)(p - q));
+                word = png_token_match((int)len, (int)(p - q));
                 p += len;
             } else {
-                t = png_fixed_literal(s[p]);
+                word = png_token_literal(s[p]);
                 ++p;
             }
-            bits.put(t.bits, t.nb);
-            nbits += (uint64_t)t.nb;
+            uint32_t lit_sym;
+            int dist_sym, eb, fb;
+            png_token_symbols(word, lit_sym, dist_sym, eb, fb);
+            ++hist[lit_sym];
+            if (dist_sym >= 0) ++hist[(size_t)kPngLit + (size_t)dist_sym];
+            extra_bits += (uint64_t)eb;
+            fixed_bits += (uint64_t)fb;
+            toks.push_back(word);
         }
-        bits.put(0, 7);   // end of block: symbol 256
-        nbits += 7;
-        const uint32_t stored_bytes = png_stored_segment_bytes(n, last), fixed_bytes = png_huffman_segment_bytes(nbits, last);
-        if (png_segment_choice(stored_bytes, fixed_bytes) == kPngStored) {
+        fixed_bits += 7;   // end of block: symbol 256
+        const uint32_t stored_bytes = png_stored_segment_bytes(n, last), fixed_bytes = png_huffman_segment_bytes(fixed_bits, last);
+        int type = png_segment_choice(stored_bytes, fixed_bytes);
+        if (dynamic) {
+            hist[256] = 1;
+            png_dynamic_plan(hist.data(), extra_bits, plan, sc);
+            type = png_segment_choice(stored_bytes, fixed_bytes, png_huffman_segment_bytes(plan.bits, last));
+        }
+        if (type == kPngStored) {
             out.push_back(last ? 1 : 0);
             out.push_back((uint8_t)(n & 0xFFu));
             out.push_back((uint8_t)(n >> 8));
@@ -1782,19 +2088,51 @@ inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, c
             out.push_back((uint8_t)((~n >> 8) & 0xFFu));
             out.insert(out.end(), s.begin(), s.begin() + (std::ptrdiff_t)n);
             if (!last) out.insert(out.end(), {0x00, 0x00, 0x00, 0xFF, 0xFF});
-        } else {
-            if (!last) {
-                bits.put(0, 3);
-                bits.flush();
-                for (const uint8_t b : {0x00, 0x00, 0xFF, 0xFF}) bits.data.push_back(b);
-            } else {
-                bits.flush();
-            }
-            out.insert(out.end(), bits.data.begin(), bits.data.end());
+            continue;
         }
+        GifBits bits;   // (an LSB-first bit writer)
+        bits.put((last ? 1u : 0u) | ((uint32_t)type << 1), 3);
+        if (type == kPngFixed) {
+            for (const uint32_t word : toks) {
+                const PngBits t = png_fixed_token(word);
+                bits.put(t.bits, t.nb);
+            }
+            bits.put(0, 7);
+        } else {
+            bits.put((uint32_t)(plan.hlit - 257) | ((uint32_t)(plan.hdist - 1) << 5) | ((uint32_t)(plan.hclen - 4) << 10), 14);
+            for (int i = 0; i < plan.hclen; ++i) bits.put(plan.lens[kPngLens + png_cl_order(i)], 3);
+            for (int k = 0; k < plan.nseq; ++k) {
+                const PngBits t = png_cl_entry(plan.seq[k], plan.codes + kPngLens);
+                bits.put(t.bits, t.nb);
+            }
+            for (const uint32_t word : toks) {
+                const PngBits64 t = png_dynamic_token(word, plan.codes, plan.codes + kPngLit);
+                bits.put((uint32_t)(t.bits & 0xFFFFFFu), t.nb < 24 ? t.nb : 24);
+                if (t.nb > 24) bits.put((uint32_t)(t.bits >> 24), t.nb - 24);
+            }
+            bits.put(plan.codes[256] & 0xFFFFu, (int)(plan.codes[256] >> 16));
+        }
+        if (!last) {
+            bits.put(0, 3);
+            bits.flush();
+            for (const uint8_t b : {0x00, 0x00, 0xFF, 0xFF}) bits.data.push_back(b);
+        } else {
+            bits.flush();
+        }
+        out.insert(out.end(), bits.data.begin(), bits.data.end());
     }
     const uint32_t adler = (B << 16) | A;
     for (int k = 3; k >= 0; --k) out.push_back((uint8_t)(adler >> (8 * k)));
+}
+
+inline void png_deflate_encode(const uint8_t *plane, const int h, const int w, const int depth, const int seg_bytes, std::vector<uint8_t> &out)
+{
+    png_deflate_encode_blocks(plane, h, w, depth, seg_bytes, false, out);
+}
+
+inline void png_deflate_encode_dyn(const uint8_t *plane, const int h, const int w, const int depth, const int seg_bytes, std::vector<uint8_t> &out)
+{
+    png_deflate_encode_blocks(plane, h, w, depth, seg_bytes, true, out);
 }
 
 }  // namespace dp

@@ -25,6 +25,7 @@
 //   host_xxx pngdeflate <cases.bin> <n>   the host statement of the PNG-8 image data (png_deflate_encode): n records of
 //                                     int32 frames, h, w, depth, seg_bytes and frames * h * w index bytes; every frame prints
 //                                     its size and its zlib stream in hex (inflated and compared by the test)
+//   host_xxx pngdyn <cases.bin> <n>   the same with dynamic-Huffman blocks as a third candidate (png_deflate_encode_dyn)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -516,7 +517,7 @@ static int run_giflzw(const char *path, const int n_cases)
 }
 
 // ---- PNG-8 image data ------------------------------------------------------------------------------------------
-static int run_pngdeflate(const char *path, const int n_cases)
+static int run_pngdeflate(const char *path, const int n_cases, const bool dynamic)
 {
     FILE *f = fopen(path, "rb");
     if (!f) {
@@ -537,7 +538,7 @@ static int run_pngdeflate(const char *path, const int n_cases)
                 fprintf(stderr, "short record %d in %s\n", c, path);
                 return 2;
             }
-            png_deflate_encode(plane.data(), head[1], head[2], head[3], head[4], out);
+            png_deflate_encode_blocks(plane.data(), head[1], head[2], head[3], head[4], dynamic, out);
             if (out.size() > bound) {
                 printf("case %d frame %d: %zu bytes exceed the bound %llu\n", c, k, out.size(), (unsigned long long)bound);
                 return 1;
@@ -554,13 +555,14 @@ static int run_pngdeflate(const char *path, const int n_cases)
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
     if (std::string(argv[1]) == "indexmap") return run_indexmap(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "giflzw") return run_giflzw(argv[2], atoi(argv[3]));
-    if (std::string(argv[1]) == "pngdeflate") return run_pngdeflate(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "pngdeflate") return run_pngdeflate(argv[2], atoi(argv[3]), false);
+    if (std::string(argv[1]) == "pngdyn") return run_pngdeflate(argv[2], atoi(argv[3]), true);
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

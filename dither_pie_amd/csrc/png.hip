@@ -19,8 +19,7 @@
 //                      6. The segment's size as stored and as fixed Huffman decide (png_segment_choice); a stored segment
 //                         overwrites its slot from LDS.  The slot then holds the segment's final bytes, realigning block
 //                         included, and rec[] its length and Adler sums.
-//                      Dynamic-Huffman blocks are not written yet.  They enter as a counting pass over the same steps
-//                      (histograms in LDS, 1.3 KiB), a code construction, and step 5 with the constructed codes.
+//                      This kernel writes stored and fixed blocks only; png_segment_dyn_kernel below adds dynamic ones.
 //                      LDS: 32784 (segment) + 8192 (heads) + 288 (stage) = 41264 bytes, so 3 workgroups per CU of the 160
 //                      KiB, 768 segments in flight on 256 CUs.  One 1080p frame at depth 8 is 64 segments of 32 KiB: a
 //                      quarter of the CUs, one wave each, and the serial part of a segment (steps 2 ... 5, <= 512 steps) is
@@ -36,9 +35,36 @@
 // png_pack_kernel      grid (blocks per frame, frames): a workgroup copies one segment's slot to its place in `out`, byte by
 //                      byte (segments are byte-aligned: no shifting), grid stride over the frame's segments.  Plain
 //                      stores, no atomics, nothing read from `out`.  Loops: n_seg / gridDim.x, slot bytes / 256.
+//
+// Dynamic-Huffman blocks (include/ditherpie_hip_png_dyn.h, host_logic.h: png_deflate_encode_dyn).  png_layout_kernel and
+// png_pack_kernel are reused as they are; png_segment_kernel is untouched (a second kernel, not a branch in its step loop).
+// png_segment_dyn_kernel   one wave per segment, as above.
+//                      Pass 1: steps 1 ... 4 as above; instead of emitting, a step counts its tokens into LDS histograms
+//                         (286 + 30 counters, integer LDS atomics: 64 lanes meet on one counter only where 64 equal literals
+//                         follow each other without a match, which the matcher turns into one token after three bytes), adds
+//                         up the fixed-Huffman bits and the extra bits per lane, and writes one 32-bit word per token,
+//                         compacted by the step's prefix count, to the segment's token area (4 * seg bytes of workspace).
+//                      Build: per alphabet (literal/length, distance, then the code-length alphabet over the run-length
+//                         coded lengths) the keys count << 9 | symbol are rank-sorted by the wave (each lane counts the
+//                         keys below its own: <= 5 keys a lane x 286 broadcast reads), lane 0 runs the host's merge, limit
+//                         and assignment (png_code_lengths_sorted: <= 285 merges, <= 286 depths, <= 286 fix-up rounds of
+//                         <= 15) and the run-length coding (png_cl_sequence: <= 316 lengths).
+//                      Choose: the dynamic block's bits are summed by the wave from the histograms, the extra bits and the
+//                         lengths (316 symbols and <= 316 sequence entries, 5 a lane); png_segment_choice with three sizes.
+//                      Pass 2: only the chosen type is written.  Stored: the bytes from LDS.  Fixed or dynamic: the block
+//                         header (one step: 14 bits and HCLEN x 3), the code-length sequence (<= 5 steps), the token words
+//                         64 a step (<= seg / 64 steps ... <= 512), end-of-block, the realigning block.  A dynamic token is
+//                         up to 15 + 5 + 15 + 13 = 48 bits, so the stage is 128 words (31 carried bits + 64 x 48 = 97 words,
+//                         and a token's three-word span ends at word 97) and a step moves up to 97 words, two a lane.
+//                         Slot writes stay clipped at slot_words; token writes at the token area's seg words.
+//                      LDS: 32784 (segment) + 8192 (heads) + 512 (stage) + 1264 (histograms) + 1340 (codes) + 336
+//                      (lengths) + 632 (sequence) + 80 (code-length counts) + 4576 (builder) = 49716 bytes <= 54613: three
+//                      workgroups per CU as before.
+// png_code_lengths_kernel  dp_png_code_lengths_u8: one wave per histogram, grid stride; the same wave_code_lengths.
 #include "dp_internal.h"
 
 #include "../../include/ditherpie_hip_png.h"
+#include "../../include/ditherpie_hip_png_dyn.h"
 
 namespace dp {
 namespace {
@@ -310,6 +336,339 @@ __global__ __launch_bounds__(kPackThreads) void png_pack_kernel(const SegRec *__
     }
 }
 
+// ---- dynamic-Huffman blocks ---------------------------------------------------------------------------------------------
+constexpr int kDynStageWords = 128;
+
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, const uint32_t lane)
+{
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = __shfl_up(v, off);
+        if (lane >= (uint32_t)off) v += up;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return __shfl(v, 0);
+}
+
+// Rules (a) ... (e) by one wave (a workgroup of 64): sc.keys[0 .. m) hold png_code_key(count, symbol) and are visible to the
+// wave; lengths[0 .. m) (LDS) receive the result, visible on return.
+__device__ void wave_code_lengths(PngCodeScratch &sc, const int m, const int L, uint8_t *lengths, const uint32_t lane)
+{
+    int used = 0;
+    for (int s0 = 0; s0 < m; s0 += 64) {   // <= 5
+        const int s = s0 + (int)lane;
+        used += __popcll(__ballot(s < m && sc.keys[s] < kPngUnusedKey));
+    }
+    if (used < 2) {
+        __syncthreads();
+        if (lane == 0) png_pad_keys(sc.keys, m);
+        used = 2;
+        __syncthreads();
+    }
+    for (int s = (int)lane; s < m; s += 64) {   // <= 5 keys a lane, every key read by all lanes at once (a broadcast)
+        const uint32_t key = sc.keys[s];
+        int rank = 0;
+        for (int j = 0; j < m; ++j) rank += sc.keys[j] < key;   // <= 286 (keys are distinct: the symbol is in them)
+        sc.sorted[rank] = key;
+    }
+    __syncthreads();
+    if (lane == 0) png_code_lengths_sorted(sc.sorted, used, m, L, lengths, sc.w, sc.lp, sc.ip);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void png_code_lengths_kernel(const uint32_t *__restrict__ counts, const int n_alphabets, const int m, const int L,
+                                                              uint8_t *__restrict__ lengths)
+{
+    __shared__ PngCodeScratch sc;
+    __shared__ uint8_t lens[kPngLit + 2];
+    const uint32_t lane = threadIdx.x;
+    for (int a = (int)blockIdx.x; a < n_alphabets; a += (int)gridDim.x) {
+        __syncthreads();
+        for (int s = (int)lane; s < m; s += 64) sc.keys[s] = png_code_key(counts[(size_t)a * (size_t)m + (size_t)s], (uint32_t)s);
+        __syncthreads();
+        wave_code_lengths(sc, m, L, lens, lane);
+        for (int s = (int)lane; s < m; s += 64) lengths[(size_t)a * (size_t)m + (size_t)s] = lens[s];
+    }
+}
+
+__global__ __launch_bounds__(64) void png_segment_dyn_kernel(const uint8_t *__restrict__ planes, const int h, const int w, const int depth,
+                                                             const uint32_t rb, const uint32_t F, const uint32_t seg, const int n_seg,
+                                                             const int total_segs, uint8_t *__restrict__ slots, const long long slot_bytes,
+                                                             uint32_t *__restrict__ token_area, SegRec *__restrict__ rec)
+{
+    __shared__ uint32_t s_w[kSegWords];
+    __shared__ uint16_t heads[kHeads];
+    __shared__ uint32_t stage[kDynStageWords];
+    __shared__ uint32_t hist[kPngLens];
+    __shared__ uint32_t codes[kPngLens + kPngCl];
+    __shared__ uint8_t lens[kPngLens + kPngCl + 1];
+    __shared__ uint16_t seq[kPngLens];
+    __shared__ uint32_t cl_counts[kPngCl + 1];
+    __shared__ PngCodeScratch sc;
+    __shared__ int s_head[4];   // hlit, hdist, hclen, nseq
+    static_assert(sizeof(uint32_t) * (kSegWords + kDynStageWords + 2 * kPngLens + 2 * kPngCl + 1) + sizeof(uint16_t) * (kHeads + kPngLens) +
+                          (kPngLens + kPngCl + 1) + sizeof(PngCodeScratch) + 16 <= 54613,
+                  "three workgroups per CU");
+    uint8_t *s_b = reinterpret_cast<uint8_t *>(s_w);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slot_words = (uint32_t)(slot_bytes >> 2);
+    const size_t plane_bytes = (size_t)h * (size_t)w;
+
+    for (int id = (int)blockIdx.x; id < total_segs; id += (int)gridDim.x) {
+        const int f = id / n_seg, j = id - f * n_seg;
+        const uint32_t at = (uint32_t)j * seg;
+        const uint32_t n = seg < F - at ? seg : F - at;
+        const bool last = j == n_seg - 1;
+        const uint8_t *__restrict__ plane = planes + (size_t)f * plane_bytes;
+        uint8_t *__restrict__ slot_b = slots + (size_t)id * (size_t)slot_bytes;
+        uint32_t *__restrict__ slot = reinterpret_cast<uint32_t *>(slot_b);
+        uint32_t *tokens = token_area + (size_t)id * (size_t)seg;   // seg words (read back in pass 2: not __restrict__)
+
+        __syncthreads();   // (the segment before is done with the arrays)
+        unsigned long long s1 = 0, s2 = 0;
+#pragma unroll 4
+        for (uint32_t i = lane; i < n; i += 64u) {   // <= 512
+            const uint32_t o = at + i, r = o / rb;
+            const uint32_t b = png_filtered_byte(plane, w, depth, r, o - r * rb);
+            s_b[i] = (uint8_t)b;
+            s1 += b;
+            s2 += (unsigned long long)(n - i) * b;
+        }
+        for (uint32_t i = lane; i < (uint32_t)kHeads; i += 64u) heads[i] = (uint16_t)kPngNoCand;
+        for (uint32_t i = lane; i < (uint32_t)kPngLens; i += 64u) hist[i] = 0u;   // <= 5
+        for (int off = 32; off > 0; off >>= 1) {
+            s1 += __shfl_down(s1, off);
+            s2 += __shfl_down(s2, off);
+        }
+        __syncthreads();
+
+        // ---- pass 1: tokens, histograms, bit totals
+        uint32_t skip = 0;    // the first position the matches taken so far do not cover (uniform)
+        uint32_t ntok = 0;    // tokens written so far (uniform)
+        unsigned long long my_fixed = 0, my_extra = 0;
+        for (uint32_t base = 0; base < n; base += 64u) {   // <= 512
+            const uint32_t p = base + lane;
+            const uint32_t cnt = n - base < 64u ? n - base : 64u;
+            const bool valid = p + 2u < n;
+            const uint32_t b0 = p < n ? s_b[p] : 0u;
+            const uint32_t hv = valid ? png_hash3(b0, s_b[p + 1u], s_b[p + 2u]) : 0x10000u + lane;   // (no other lane's value)
+            uint32_t q = valid ? (uint32_t)heads[hv & (uint32_t)(kHeads - 1)] : kPngNoCand;
+            bool later = false;
+#pragma unroll
+            for (int k = 0; k < 64; ++k) {
+                const uint32_t hk = (uint32_t)__builtin_amdgcn_readlane((int)hv, k);
+                if (hk == hv) {
+                    if ((uint32_t)k < lane) q = base + (uint32_t)k;
+                    else if ((uint32_t)k > lane) later = true;
+                }
+            }
+            __syncthreads();   // (every lane has read the heads)
+            if (valid && !later) heads[hv] = (uint16_t)p;
+
+            uint32_t len = 0;
+            if (skip < base + cnt && valid && q != kPngNoCand && p >= skip) {
+                const uint32_t maxlen = n - p < 258u ? n - p : 258u;
+                for (uint32_t k = 0; k < maxlen; k += 4u) {   // <= 65
+                    const uint32_t x = lds_read_u32_at(s_w, q + k) ^ lds_read_u32_at(s_w, p + k);
+                    if (x) {
+                        len = k + ((uint32_t)__builtin_ctz(x) >> 3);
+                        break;
+                    }
+                    len = k + 4u;
+                }
+                len = len < maxlen ? len : maxlen;
+            }
+            const unsigned long long M = __ballot(len >= 3u);
+
+            const uint32_t start = skip > base ? (skip - base < 64u ? skip - base : 64u) : 0u;
+            uint32_t pos = start;
+            unsigned long long sel = 0, cov = 0;
+            for (int it = 0; it < 22 && pos < cnt; ++it) {
+                const unsigned long long rest = M >> pos;
+                if (!rest) break;
+                pos += (uint32_t)__builtin_ctzll(rest);
+                const uint32_t L = (uint32_t)__shfl((int)len, (int)pos);
+                sel |= 1ull << pos;
+                cov |= low_mask(pos + L) & ~low_mask(pos + 1u);
+                pos += L;
+                skip = base + pos;
+            }
+            const unsigned long long T = low_mask(cnt) & ~low_mask(start) & ~cov;
+            const bool is_tok = (T >> lane) & 1ull, is_match = (sel >> lane) & 1ull;
+
+            if (is_tok) {
+                const uint32_t word = is_match ? png_token_match((int)len, (int)(p - q)) : png_token_literal(b0);
+                uint32_t lit_sym;
+                int dist_sym, eb, fb;
+                png_token_symbols(word, lit_sym, dist_sym, eb, fb);
+                atomicAdd(&hist[lit_sym], 1u);
+                if (dist_sym >= 0) atomicAdd(&hist[kPngLit + dist_sym], 1u);
+                my_extra += (unsigned long long)eb;
+                my_fixed += (unsigned long long)fb;
+                const uint32_t slot_of = ntok + (uint32_t)__popcll(T & low_mask(lane));
+                if (slot_of < seg) tokens[slot_of] = word;
+            }
+            ntok += (uint32_t)__popcll(T);
+        }
+        const unsigned long long fixed_bits = 3ull + wave_sum(my_fixed) + 7ull, extra_bits = wave_sum(my_extra);
+        if (lane == 0) hist[256] = 1u;
+        __threadfence_block();   // the token words are read back by other lanes of this wave
+        __syncthreads();
+
+        // ---- build: the three codes and the size of the dynamic block
+        for (int s = (int)lane; s < kPngLit; s += 64) sc.keys[s] = png_code_key(hist[s], (uint32_t)s);
+        __syncthreads();
+        wave_code_lengths(sc, kPngLit, 15, lens, lane);
+        if (lane < (uint32_t)kPngDist) sc.keys[lane] = png_code_key(hist[kPngLit + lane], lane);
+        __syncthreads();
+        wave_code_lengths(sc, kPngDist, 15, lens + kPngLit, lane);
+        if (lane == 0) {
+            const int hlit = png_hlit(lens), hdist = png_hdist(lens + kPngLit);
+            s_head[0] = hlit;
+            s_head[1] = hdist;
+            s_head[3] = png_cl_sequence(lens, hlit, lens + kPngLit, hdist, seq, cl_counts);
+        }
+        __syncthreads();
+        if (lane < (uint32_t)kPngCl) sc.keys[lane] = png_code_key(cl_counts[lane], lane);
+        __syncthreads();
+        wave_code_lengths(sc, kPngCl, 7, lens + kPngLens, lane);
+        if (lane == 0) s_head[2] = png_hclen(lens + kPngLens);
+        __syncthreads();
+        const int hlit = s_head[0], hdist = s_head[1], hclen = s_head[2], nseq = s_head[3];
+        unsigned long long my_bits = 0;
+        for (int k = (int)lane; k < nseq; k += 64) {   // <= 5
+            const uint32_t sym = seq[k] & 31u;
+            my_bits += (unsigned long long)lens[kPngLens + sym] + (unsigned long long)png_cl_extra(sym);
+        }
+        for (int s = (int)lane; s < kPngLens; s += 64) my_bits += (unsigned long long)hist[s] * lens[s];   // <= 5
+        const unsigned long long dyn_bits = 3ull + 14ull + 3ull * (unsigned long long)hclen + extra_bits + wave_sum(my_bits);
+
+        const uint32_t stored_bytes = png_stored_segment_bytes(n, last), fixed_bytes = png_huffman_segment_bytes(fixed_bits, last);
+        const uint32_t dyn_bytes = png_huffman_segment_bytes(dyn_bits, last);
+        const int type = png_segment_choice(stored_bytes, fixed_bytes, dyn_bytes);
+
+        // ---- pass 2: the chosen type alone
+        if (type == kPngStored) {
+            if (lane == 0) {
+                slot_b[0] = last ? 1 : 0;
+                slot_b[1] = (uint8_t)(n & 0xFFu);
+                slot_b[2] = (uint8_t)(n >> 8);
+                slot_b[3] = (uint8_t)(~n & 0xFFu);
+                slot_b[4] = (uint8_t)((~n >> 8) & 0xFFu);
+                if (!last) {
+                    slot_b[5u + n] = 0x00;
+                    slot_b[6u + n] = 0x00;
+                    slot_b[7u + n] = 0x00;
+                    slot_b[8u + n] = 0xFF;
+                    slot_b[9u + n] = 0xFF;
+                }
+            }
+            for (uint32_t i = lane; i < n; i += 64u) slot_b[5u + i] = s_b[i];   // <= 512
+        } else {
+            const bool dyn = type == kPngDynamic;
+            if (dyn && lane == 0) {
+                png_canonical_codes(lens, kPngLit, codes);
+                png_canonical_codes(lens + kPngLit, kPngDist, codes + kPngLit);
+                png_canonical_codes(lens + kPngLens, kPngCl, codes + kPngLens);
+            }
+            for (uint32_t i = lane; i < (uint32_t)kDynStageWords; i += 64u) stage[i] = 0u;
+            __syncthreads();
+            if (lane == 0) stage[0] = (last ? 1u : 0u) | ((uint32_t)type << 1);   // BFINAL, BTYPE
+            __syncthreads();
+
+            unsigned long long bitpos = 3;   // of the block, from the slot's first bit (uniform)
+            uint32_t stage_word = 0;         // the slot word stage[0] stands for (uniform)
+
+            // ORs a token of <= 48 bits in at bit `where`, then moves the stage's whole words to the slot; `more` = the new bit position
+            auto emit = [&](const unsigned long long bits, const int nb, const unsigned long long where, const unsigned long long more,
+                            const bool all) {
+                if (nb > 0) {
+                    const uint32_t rel = (uint32_t)(where - 32ull * stage_word), wi = rel >> 5, sh = rel & 31u;   // wi <= 95
+                    const unsigned long long lo = bits << sh;
+                    atomicOr(&stage[wi], (uint32_t)lo);
+                    if (lo >> 32) atomicOr(&stage[wi + 1u], (uint32_t)(lo >> 32));
+                    const uint32_t hi = sh ? (uint32_t)(bits >> (64u - sh)) : 0u;
+                    if (hi) atomicOr(&stage[wi + 2u], hi);
+                }
+                __syncthreads();
+                uint32_t full = (uint32_t)(more >> 5) - stage_word;           // <= 96
+                const uint32_t keep = all ? 0u : stage[full];                  // the word still being filled
+                if (all && (more & 31ull)) ++full;
+                const uint32_t mine0 = lane < full ? stage[lane] : 0u, mine1 = lane + 64u < full ? stage[lane + 64u] : 0u;
+                __syncthreads();
+                if (lane < full && stage_word + lane < slot_words) slot[stage_word + lane] = mine0;
+                if (lane + 64u < full && stage_word + lane + 64u < slot_words) slot[stage_word + lane + 64u] = mine1;
+                stage[lane] = lane == 0 ? keep : 0u;
+                stage[lane + 64u] = 0u;
+                __syncthreads();
+                stage_word += full;
+            };
+            auto step = [&](const unsigned long long bits, const int nb) {   // one token a lane, in lane order
+                const uint32_t incl = wave_incl_sum((uint32_t)nb, lane);
+                const uint32_t step_bits = __shfl(incl, 63);
+                emit(bits, nb, bitpos + incl - (uint32_t)nb, bitpos + step_bits, false);
+                bitpos += step_bits;
+            };
+
+            if (dyn) {
+                unsigned long long hb = 0;
+                int hn = 0;
+                if (lane == 0) {
+                    hb = (unsigned long long)(hlit - 257) | ((unsigned long long)(hdist - 1) << 5) | ((unsigned long long)(hclen - 4) << 10);
+                    hn = 14;
+                } else if (lane <= (uint32_t)hclen) {
+                    hb = lens[kPngLens + png_cl_order((int)lane - 1)];
+                    hn = 3;
+                }
+                step(hb, hn);
+                for (int base = 0; base < nseq; base += 64) {   // <= 5
+                    PngBits t;
+                    t.bits = 0u;
+                    t.nb = 0;
+                    if (base + (int)lane < nseq) t = png_cl_entry(seq[base + (int)lane], codes + kPngLens);
+                    step(t.bits, t.nb);
+                }
+            }
+            for (uint32_t base = 0; base < ntok; base += 64u) {   // <= 512
+                unsigned long long tb = 0;
+                int tn = 0;
+                if (base + lane < ntok && base + lane < seg) {
+                    const uint32_t word = tokens[base + lane];
+                    if (dyn) {
+                        const PngBits64 t = png_dynamic_token(word, codes, codes + kPngLit);
+                        tb = t.bits;
+                        tn = t.nb;
+                    } else {
+                        const PngBits t = png_fixed_token(word);
+                        tb = t.bits;
+                        tn = t.nb;
+                    }
+                }
+                step(tb, tn);
+            }
+            step(dyn ? (unsigned long long)(codes[256] & 0xFFFFu) : 0ull, lane == 0 ? (dyn ? (int)(codes[256] >> 16) : 7) : 0);   // end of block
+            if (!last) {
+                const unsigned long long aligned = (bitpos + 3ull + 7ull) & ~7ull;
+                emit(0xFFFF0000ull, lane == 0 ? 32 : 0, aligned, aligned + 32ull, true);   // 00 00 FF FF
+            } else {
+                emit(0ull, 0, bitpos, bitpos, true);
+            }
+        }
+        if (lane == 0) {
+            SegRec r;
+            r.len = type == kPngStored ? stored_bytes : type == kPngFixed ? fixed_bytes : dyn_bytes;
+            r.s1 = (uint32_t)(s1 % kAdlerMod);
+            r.s2 = (uint32_t)(s2 % kAdlerMod);
+            r.off = 0u;
+            rec[id] = r;
+        }
+    }
+}
+
 struct PngPlan {
     long long F, seg, slot_bytes, total_segs;
     int n_seg;
@@ -351,6 +710,42 @@ int launch_png_deflate(const uint8_t *planes, int n_frames, int h, int w, int de
     return DP_OK;
 }
 
+// the plan of the fixed-mode call, and behind its slots the token area: seg 32-bit words per segment
+struct PngDynWorkspace {
+    PngPlan base;
+    size_t tokens_off, total;
+};
+
+PngDynWorkspace png_dyn_plan(const int n_frames, const int h, const int w, const int depth, const int seg_bytes)
+{
+    PngDynWorkspace p;
+    p.base = png_plan(n_frames, h, w, depth, seg_bytes);
+    p.tokens_off = round16(p.base.total);
+    p.total = p.tokens_off + (size_t)p.base.total_segs * (size_t)p.base.seg * sizeof(uint32_t);
+    return p;
+}
+
+int launch_png_deflate_dyn(const uint8_t *planes, int n_frames, int h, int w, int depth, const PngDynWorkspace &d, uint8_t *out, long long out_stride,
+                           long long *sizes, uint8_t *ws, hipStream_t s)
+{
+    const PngPlan &p = d.base;
+    SegRec *rec = reinterpret_cast<SegRec *>(ws);
+    uint8_t *slots = ws + p.slots_off;
+    uint32_t *tokens = reinterpret_cast<uint32_t *>(ws + d.tokens_off);
+    const int total = (int)p.total_segs;
+    const int grid = total < kSegMaxBlocks ? total : kSegMaxBlocks;
+    hipLaunchKernelGGL(png_segment_dyn_kernel, dim3((unsigned)grid), dim3(64), 0, s, planes, h, w, depth, png_row_bytes(w, depth), (uint32_t)p.F,
+                       (uint32_t)p.seg, p.n_seg, total, slots, p.slot_bytes, tokens, rec);
+    DP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(png_layout_kernel, dim3((unsigned)n_frames), dim3(64), 0, s, rec, p.n_seg, (uint32_t)p.F, (uint32_t)p.seg, out, out_stride, sizes);
+    DP_HIP(hipGetLastError());
+    const int bpf = p.n_seg < kPackMaxBlocksPerFrame ? p.n_seg : kPackMaxBlocksPerFrame;
+    hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)bpf, (unsigned)n_frames), dim3(kPackThreads), 0, s, (const SegRec *)rec, p.n_seg,
+                       (const uint8_t *)slots, p.slot_bytes, out, out_stride);
+    DP_HIP(hipGetLastError());
+    return DP_OK;
+}
+
 int check_png(const char *fn, const void *planes, int n_frames, int h, int w, int depth, int seg_bytes, const void *out, int64_t out_stride,
               const void *sizes)
 {
@@ -362,6 +757,16 @@ int check_png(const char *fn, const void *planes, int n_frames, int h, int w, in
     if (out_stride < 0 || (uint64_t)out_stride < need) {
         set_error("%s: bad argument (out_stride of %lld bytes is below the bound of %llu for %d x %d at depth %d, seg_bytes %d)", fn,
                   (long long)out_stride, (unsigned long long)need, h, w, depth, seg_bytes);
+        return DP_EINVAL;
+    }
+    return DP_OK;
+}
+
+int check_code_lengths(const char *fn, const void *counts, int n_alphabets, int n_symbols, int max_len, const void *lengths)
+{
+    if (!counts || !lengths || n_alphabets < 0 || n_symbols < 2 || n_symbols > kPngLit || max_len < 1 || max_len > 15 ||
+        (1 << max_len) < n_symbols || ((uintptr_t)counts & 3)) {
+        set_error("%s: bad argument (n_alphabets >= 0, n_symbols in 2 ... 286, max_len in 1 ... 15 with 2^max_len >= n_symbols, counts 4-byte aligned)", fn);
         return DP_EINVAL;
     }
     return DP_OK;
@@ -446,6 +851,122 @@ int dp_png_deflate_host_u8(const uint8_t *planes_host, int n_frames, int h, int 
             std::copy(frame.begin(), frame.end(), out_host + (size_t)f * (size_t)out_stride);
             sizes_host[f] = (int64_t)frame.size();
         }
+    } catch (const std::exception &e) {
+        set_error("%s: %s", fn, e.what());
+        return DP_ENOMEM;
+    } catch (...) {
+        set_error("%s: unexpected exception", fn);
+        return DP_ENOMEM;
+    }
+    return DP_OK;
+}
+
+size_t dp_png_deflate_dyn_workspace_bytes(int n_frames, int h, int w, int depth, int seg_bytes)
+{
+    if (!png_geometry_ok(h, w, depth, seg_bytes) || n_frames < 0) return 0;
+    if (n_frames == 0) return 0;
+    return png_dyn_plan(n_frames, h, w, depth, seg_bytes).total;
+}
+
+int dp_png_deflate_dyn_encode_u8(const uint8_t *planes_dev, int n_frames, int h, int w, int depth, int seg_bytes, uint8_t *out_dev,
+                                 int64_t out_stride, int64_t *sizes_dev, void *ws_dev, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dp_png_deflate_dyn_encode_u8";
+    try {
+        const int rc = check_png(fn, planes_dev, n_frames, h, w, depth, seg_bytes, out_dev, out_stride, sizes_dev);
+        if (rc != DP_OK) return rc;
+        if (!ws_dev || ((uintptr_t)ws_dev & 15) || ((uintptr_t)sizes_dev & 7)) {
+            set_error("%s: bad argument (ws_dev 16-byte, sizes_dev 8-byte aligned)", fn);
+            return DP_EINVAL;
+        }
+        if (n_frames > 65535) {
+            set_error("%s: at most 65535 frames per call, not %d", fn, n_frames);
+            return DP_EUNSUPPORTED;
+        }
+        const PngDynWorkspace p = png_dyn_plan(n_frames, h, w, depth, seg_bytes);
+        if (p.base.total_segs >= (1LL << 31)) {
+            set_error("%s: %d frames of %d segments are 2^31 segments or more: cut the batch or raise seg_bytes", fn, n_frames, p.base.n_seg);
+            return DP_EUNSUPPORTED;
+        }
+        if (n_frames == 0) return DP_OK;
+        if (ws_bytes < p.total) {
+            set_error("%s: workspace of %zu bytes, %zu needed", fn, ws_bytes, p.total);
+            return DP_EWORKSPACE;
+        }
+        return launch_png_deflate_dyn(planes_dev, n_frames, h, w, depth, p, out_dev, (long long)out_stride, reinterpret_cast<long long *>(sizes_dev),
+                                      static_cast<uint8_t *>(ws_dev), (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        set_error("%s: %s", fn, e.what());
+        return DP_ENOMEM;
+    } catch (...) {
+        set_error("%s: unexpected exception", fn);
+        return DP_ENOMEM;
+    }
+}
+
+int dp_png_deflate_dyn_host_u8(const uint8_t *planes_host, int n_frames, int h, int w, int depth, int seg_bytes, uint8_t *out_host,
+                               int64_t out_stride, int64_t *sizes_host)
+{
+    const char *fn = "dp_png_deflate_dyn_host_u8";
+    try {
+        const int rc = check_png(fn, planes_host, n_frames, h, w, depth, seg_bytes, out_host, out_stride, sizes_host);
+        if (rc != DP_OK) return rc;
+        const size_t n_px = (size_t)h * (size_t)w;
+        std::vector<uint8_t> frame;
+        for (int f = 0; f < n_frames; ++f) {
+            png_deflate_encode_dyn(planes_host + (size_t)f * n_px, h, w, depth, seg_bytes, frame);
+            if ((int64_t)frame.size() > out_stride) {   // (the bound says it cannot be)
+                set_error("%s: frame %d of %zu bytes exceeds the stride", fn, f, frame.size());
+                return DP_EINVAL;
+            }
+            std::copy(frame.begin(), frame.end(), out_host + (size_t)f * (size_t)out_stride);
+            sizes_host[f] = (int64_t)frame.size();
+        }
+    } catch (const std::exception &e) {
+        set_error("%s: %s", fn, e.what());
+        return DP_ENOMEM;
+    } catch (...) {
+        set_error("%s: unexpected exception", fn);
+        return DP_ENOMEM;
+    }
+    return DP_OK;
+}
+
+int dp_png_code_lengths_u8(const uint32_t *counts_dev, int n_alphabets, int n_symbols, int max_len, uint8_t *lengths_dev, void *stream)
+{
+    const char *fn = "dp_png_code_lengths_u8";
+    try {
+        const int rc = check_code_lengths(fn, counts_dev, n_alphabets, n_symbols, max_len, lengths_dev);
+        if (rc != DP_OK) return rc;
+        if (n_alphabets == 0) return DP_OK;
+        const int grid = n_alphabets < kSegMaxBlocks ? n_alphabets : kSegMaxBlocks;
+        hipLaunchKernelGGL(png_code_lengths_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, counts_dev, n_alphabets, n_symbols,
+                           max_len, lengths_dev);
+        DP_HIP(hipGetLastError());
+    } catch (const std::exception &e) {
+        set_error("%s: %s", fn, e.what());
+        return DP_ENOMEM;
+    } catch (...) {
+        set_error("%s: unexpected exception", fn);
+        return DP_ENOMEM;
+    }
+    return DP_OK;
+}
+
+int dp_png_code_lengths_host(const uint32_t *counts_host, int n_alphabets, int n_symbols, int max_len, uint8_t *lengths_host)
+{
+    const char *fn = "dp_png_code_lengths_host";
+    try {
+        const int rc = check_code_lengths(fn, counts_host, n_alphabets, n_symbols, max_len, lengths_host);
+        if (rc != DP_OK) return rc;
+        for (size_t i = 0; i < (size_t)n_alphabets * (size_t)n_symbols; ++i)
+            if (counts_host[i] > kPngMaxCount) {
+                set_error("%s: bad argument (count %u of symbol %zu is above 2^20)", fn, counts_host[i], i);
+                return DP_EINVAL;
+            }
+        PngCodeScratch sc;
+        for (int a = 0; a < n_alphabets; ++a)
+            png_code_lengths(counts_host + (size_t)a * (size_t)n_symbols, n_symbols, max_len, lengths_host + (size_t)a * (size_t)n_symbols, sc);
     } catch (const std::exception &e) {
         set_error("%s: %s", fn, e.what());
         return DP_ENOMEM;

@@ -13,6 +13,7 @@ tRNS, no gamma, no text.  Decoding gives palette[plane], exactly.
 Chunk CRCs are zlib.crc32 on the host, over the compressed bytes: a fraction of the plane (tools/bench_scripts/png_encode.py
 times it beside the kernels).  One size read-back and one block copy per call, as gif.GifWriter does.
 encoder="host" runs the normative host statement (backend.png_deflate_host) on host arrays: the same bytes without a GPU.
+blocks="dynamic" (default "fixed") lets the encoder write dynamic-Huffman blocks as well: the same pixels in fewer bytes.
 """
 from __future__ import annotations
 
@@ -56,8 +57,10 @@ def container(width, height, depth, palette, stream, idat_bytes=IDAT_BYTES):
     return b"".join(parts)
 
 
-def _streams(planes, depth, seg_bytes, encoder):
+def _streams(planes, depth, seg_bytes, encoder, blocks):
     from . import backend
+    if blocks not in backend.PNG_BLOCKS:
+        raise ValueError(f"blocks must be one of {backend.PNG_BLOCKS}, not {blocks!r}")
     if encoder == "device":
         import torch
         if not (isinstance(planes, torch.Tensor) and planes.is_cuda):
@@ -69,7 +72,7 @@ def _streams(planes, depth, seg_bytes, encoder):
         p = planes if planes.dim() == 3 else planes.unsqueeze(0)
         if p.shape[0] == 0:
             return [], p.shape
-        payload, sizes = backend.png_deflate(p, depth, seg_bytes)
+        payload, sizes = backend.png_deflate(p, depth, seg_bytes, blocks)
         sizes = sizes.cpu().tolist()
         block = payload[:, :max(sizes)].cpu().numpy()
         return [block[f, :n].tobytes() for f, n in enumerate(sizes)], p.shape
@@ -85,24 +88,25 @@ def _streams(planes, depth, seg_bytes, encoder):
     if p.ndim not in (2, 3):
         raise ValueError("planes must be [N,H,W] or [H,W]")
     p = p if p.ndim == 3 else p[None]
-    return backend.png_deflate_host(p, depth, seg_bytes), p.shape
+    return backend.png_deflate_host(p, depth, seg_bytes, blocks), p.shape
 
 
-def encode_png(planes, palette, seg_bytes=None, encoder="device"):
+def encode_png(planes, palette, seg_bytes=None, encoder="device", blocks="fixed"):
     """Index planes [N,H,W] (or [H,W]) and their palette [K,3] -> [the bytes of a PNG file per plane].  ValueError: more than
     256 colours, planes that are not one-byte indices, planes that are not on the GPU for the device encoder (or are, for
-    the host encoder).  An index >= K is the caller's error (a decoder will show whatever entry its low bits name, or
-    refuse the file)."""
+    the host encoder), a `blocks` outside backend.PNG_BLOCKS.  An index >= K is the caller's error (a decoder will show
+    whatever entry its low bits name, or refuse the file).  blocks="dynamic" adds dynamic-Huffman blocks: smaller files that
+    decode to the same pixels (include/ditherpie_hip_png_dyn.h)."""
     from . import backend
     pal = _palette(palette)
     depth = backend.png_depth(pal.shape[0])
-    streams, shape = _streams(planes, depth, seg_bytes, encoder)
+    streams, shape = _streams(planes, depth, seg_bytes, encoder, blocks)
     return [container(shape[2], shape[1], depth, pal, s) for s in streams]
 
 
-def write_png(path, plane, palette, seg_bytes=None, encoder="device"):
+def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fixed"):
     """One plane [H,W] (or [1,H,W]) as a PNG file -> the number of bytes written."""
-    files = encode_png(plane, palette, seg_bytes, encoder)
+    files = encode_png(plane, palette, seg_bytes, encoder, blocks)
     if len(files) != 1:
         raise ValueError(f"write_png takes one plane, not {len(files)}: write_png_sequence writes several")
     with open(path, "wb") as f:
@@ -110,11 +114,11 @@ def write_png(path, plane, palette, seg_bytes=None, encoder="device"):
     return len(files[0])
 
 
-def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device"):
+def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device", blocks="fixed"):
     """Planes [N,H,W] as the files pattern % start, pattern % (start + 1), ... (the 'frame_%05d.png' of a frame
     directory) -> the list of paths written."""
     paths = []
-    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder)):
+    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder, blocks)):
         path = str(pattern) % (int(start) + k)
         with open(path, "wb") as f:
             f.write(data)

@@ -129,13 +129,13 @@ def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Opt
 
 
 def process_frames_png(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
-                       final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None):
+                       final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None, blocks: str = "fixed"):
     """process_frames() as PNG-8 files: uint8 CUDA tensor [N,H,W,3] -> [bytes of one PNG file per frame]; decoding file i
     gives process_frames(...)[i], exactly.  process_frames_indexed, then png.encode_png: the planes are compressed on the
     device and only the compressed streams come back.  ValueError above 256 colours."""
     from . import png
     planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier)
-    return png.encode_png(planes, colours, seg_bytes)
+    return png.encode_png(planes, colours, seg_bytes, blocks=blocks)
 
 
 def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_method: Optional[str] = None,
@@ -739,7 +739,7 @@ class VideoProcessor:
         return made["writer"].n_frames
 
     def process_video_pngs(self, input_path, out_pattern, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1) -> int:
+                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1, blocks="fixed") -> int:
         """The video as a sequence of PNG-8 files out_pattern % start, out_pattern % (start + 1), ... (the 'frame_%05d.png'
         of a frame directory): decode -> GPU -> files, no encoder pipe and no RGB frames on the way out.  Built on the
         decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as process_video_gif is.  Per batch:
@@ -761,6 +761,8 @@ class VideoProcessor:
             raise ValueError("max_frames must be >= 1")
         if seg_bytes is not None and not 256 <= int(seg_bytes) <= 32768:
             raise ValueError("seg_bytes must be in 256 ... 32768")
+        if blocks not in ("fixed", "dynamic"):
+            raise ValueError(f"blocks must be 'fixed' or 'dynamic', not {blocks!r}")
         try:
             if str(out_pattern) % 1 == str(out_pattern) % 2:
                 raise TypeError("no field")
@@ -797,7 +799,7 @@ class VideoProcessor:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
                         planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
-                        for k, data in enumerate(encode_png(planes, colours, seg_bytes)):
+                        for k, data in enumerate(encode_png(planes, colours, seg_bytes, blocks=blocks)):
                             with open(str(out_pattern) % (int(start) + first + a + k), "wb") as f:
                                 f.write(data)
                             made["written"] += 1

@@ -36,7 +36,8 @@ extern "C" {
  *     q < p in the segment whose three bytes hash alike: ((b0 | b1 << 8 | b2 << 16) * 0x9E3779B1 mod 2^32) >> 20.  Its
  *     length is the number of equal bytes up to min(258, n - p).  Greedy: a candidate of length >= 3 is always taken.
  *   - The block type is the smallest of stored and fixed-Huffman in bytes of the whole segment, the realigning block
- *     included; a tie goes to stored.  Dynamic-Huffman blocks are not written by this revision.
+ *     included; a tie goes to stored.  These entry points write no dynamic-Huffman blocks: the entry points of
+ *     ditherpie_hip_png_dyn.h add them as a third candidate, with a larger workspace, and leave these bytes as they are.
  * Segments are what the device compresses independently (one wave each): a smaller seg_bytes costs file size (a cold
  * matcher and up to 5 bytes of realignment per segment) and buys parallelism.  A decoder sees an ordinary stream.
  *

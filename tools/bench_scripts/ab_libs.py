@@ -3,12 +3,39 @@ that was compiled into only one of them (build A from the committed sources, app
 Box-to-box spread on this pool is +-4 %: differences smaller than that can only be seen this way.
 usage: ab_libs.py [case ...]   cases: variant:K:frames  (e.g. floyd_steinberg:16:1 atkinson:16:1 floyd_steinberg:256:1 floyd_steinberg:16:256)
        or ordered modes on 1080p frames: bayer4:K:frames, bayer8:K:frames, none:K:frames, ign:K:frames (bayer4:16:100 = C5's launch;
-       K <= 64: the uniform palette, else palr(K, 7); the cell table is built before the timing)"""
+       K <= 64: the uniform palette, else palr(K, 7); the cell table is built before the timing)
+       or the PNG-8 encoder's fixed-mode entry point on photo-like 1080p planes: png:K:frames (dp_png_deflate_encode_u8 at the default
+       seg_bytes; run these on their own, not mixed with the cases above)"""
 import sys; sys.path.insert(0, '.')
 import numpy as np, torch
 from dither_pie_amd import _lib, dithering_lib
 from dither_pie_amd.dithering_lib import ImageDitherer, DitherMode, ColorReducer
 cases = sys.argv[1:] or ["floyd_steinberg:16:1", "atkinson:16:1", "floyd_steinberg:256:1", "floyd_steinberg:16:256"]
+if all(c.startswith("png:") for c in cases):
+    sys.path.insert(0, 'tests')
+    import png_ref as pr
+    from dither_pie_amd import backend
+    for case in cases:
+        _, K, nf = case.split(":"); K = int(K); nf = int(nf)
+        one = pr.photo_plane(K, 1080, 1920)
+        planes = torch.from_numpy(np.stack([np.roll(one, 7 * i, axis=1) for i in range(nf)])).cuda()
+        best, outs = {False: [], True: []}, {}
+        for rep in range(3):
+            for exp in (False, True):
+                _lib.select(exp)
+                for _ in range(2): outs[exp] = backend.png_deflate(planes, backend.png_depth(K))
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(12):
+                    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                    e0.record(); outs[exp] = backend.png_deflate(planes, backend.png_depth(K)); e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1))
+                best[exp].append(min(ts))
+        a, b = min(best[False]), min(best[True])
+        m = int(outs[False][1].max())
+        same = torch.equal(outs[False][1], outs[True][1]) and torch.equal(outs[False][0][:, :m], outs[True][0][:, :m])
+        print(f"{case:28s} A (product) {a:8.3f} ms   B (experiments twin) {b:8.3f} ms   B/A {b / a:.3f}   identical bytes: {same}"
+              f"   [A runs {' '.join('%.3f' % v for v in best[False])} | B runs {' '.join('%.3f' % v for v in best[True])}]", flush=True)
+    sys.exit(0)
 g = torch.Generator(device='cuda'); g.manual_seed(1)
 ORDERED = {"none": (DitherMode.NONE, {}), "bayer8": (DitherMode.BAYER, {"size": "8x8"}), "bayer4": (DitherMode.BAYER, {"size": "4x4"}),
            "ign": (DitherMode.INTERLEAVED_GRADIENT_NOISE, {})}

@@ -1,7 +1,7 @@
 """Times and file sizes of the PNG-8 output (HIP events for the device part, perf_counter for whole calls; warm clocks,
 median [p10-p90]).
 
-  python tools/bench_scripts/png_encode.py [--repeats 20] [--segs 2048,8192,32768] [--batch 64] [--skip-4k]
+  python tools/bench_scripts/png_encode.py [--repeats 20] [--segs 2048,8192,32768] [--batch 64] [--skip-4k] [--blocks fixed|dynamic|both]
   python tools/bench_scripts/png_encode.py --sizes-only      (no GPU: stream sizes of the host statement against zlib)
 
   * dp_png_deflate_encode_u8 alone (HIP events) on photo-like and noise planes of 16 and 256 colours at 1080p and 4K, one
@@ -13,6 +13,8 @@ median [p10-p90]).
     cache state are shared), with the bytes of both files;
   * --sizes-only: bytes of the host statement over the filtered size at every seg_bytes, with zlib level 1, level 6 and level
     1 restricted to fixed codes (Z_FIXED) beside it, on the 512 x 768 photo-like planes of tests/png_ref.py.
+  * --blocks: the block types the encoder may write beside stored ones ("fixed", the default; "dynamic"; "both" times the two
+    A then B then A ... in the same process and reports each, with the workspace either needs).
 Run from the root of the tree; prints one JSON line per figure."""
 import argparse
 import io
@@ -54,6 +56,25 @@ def time_gpu(fn, repeats, warmup=3):
     return out
 
 
+def time_gpu_interleaved(fns, repeats, warmup=3):
+    """[ms per repeat] per function, the functions taking turns inside every repeat (shared clock and cache state)."""
+    import torch
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(repeats):
+        for fn, acc in zip(fns, out):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            acc.append(a.elapsed_time(b))
+    return out
+
+
 def time_wall(fn, repeats, warmup=2):
     import torch
     for _ in range(warmup):
@@ -73,7 +94,7 @@ def zfixed1(data):
     return co.compress(data) + co.flush()
 
 
-def sizes_only(segs):
+def sizes_only(segs, modes):
     import png_ref as pr
     from dither_pie_amd import backend
     for k in (16, 256):
@@ -83,9 +104,10 @@ def sizes_only(segs):
         emit("zlib", k=k, level1=round(len(zlib.compress(raw, 1)) / F, 4), level6=round(len(zlib.compress(raw, 6)) / F, 4),
              fixed_level1=round(len(zfixed1(raw)) / F, 4))
         for seg in segs:
-            n = len(backend.png_deflate_host(plane, d, seg)[0])
-            emit("host statement", k=k, seg_bytes=seg, of_filtered=round(n / F, 4), of_zlib_fixed_level1=round(n / len(zfixed1(raw)), 4),
-                 of_zlib_level1=round(n / len(zlib.compress(raw, 1)), 4))
+            for blocks in modes:
+                n = len(backend.png_deflate_host(plane, d, seg, blocks=blocks)[0])
+                emit("host statement", k=k, seg_bytes=seg, blocks=blocks, bytes=n, of_filtered=round(n / F, 4),
+                     of_zlib_fixed_level1=round(n / len(zfixed1(raw)), 4), of_zlib_level1=round(n / len(zlib.compress(raw, 1)), 4))
 
 
 def planes_of(kind, k, n, h, w):
@@ -104,14 +126,19 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--skip-4k", action="store_true")
     ap.add_argument("--sizes-only", action="store_true")
+    ap.add_argument("--blocks", choices=("fixed", "dynamic", "both"), default="fixed")
     a = ap.parse_args()
     segs = [int(s) for s in a.segs.split(",")]
+    modes = ["fixed", "dynamic"] if a.blocks == "both" else [a.blocks]
     if a.sizes_only:
-        return sizes_only(segs)
+        return sizes_only(segs, modes)
     import torch
     from PIL import Image
-    from dither_pie_amd import backend, png
+    from dither_pie_amd import _lib, backend, png
     from dither_pie_amd.dithering_lib import DitherMode, ImageDitherer
+    L = _lib.load()
+    entry = {"fixed": "dp_png_deflate_encode_u8", "dynamic": "dp_png_deflate_dyn_encode_u8"}
+    ws_of = {"fixed": L.dp_png_deflate_workspace_bytes, "dynamic": L.dp_png_deflate_dyn_workspace_bytes}
     emit("device", name=torch.cuda.get_device_name(0), default_seg_bytes=backend.PNG_SEG_BYTES)
     geometries = [(1080, 1920)] + ([] if a.skip_4k else [(2160, 3840)])
     for h, w in geometries:
@@ -125,14 +152,17 @@ def main():
                     emit("device copy of the planes", time_gpu(lambda: dev.clone(), a.repeats), **tag)
                     for seg in segs:
                         out = {}
-                        def run():
-                            out["r"] = backend.png_deflate(dev, d, seg)
-                        ms = time_gpu(run, a.repeats)
-                        emit("dp_png_deflate_encode_u8", ms, seg_bytes=seg, bytes_per_frame=int(out["r"][1].sum().item()) // n,
-                             plane_bytes=h * w, **tag)
-                    ms = time_wall(lambda: png.encode_png(dev, palette), a.repeats)
-                    emit("encode_png end to end", ms, **tag)
-                    payload, sizes = backend.png_deflate(dev, d)
+                        def runner(blocks):
+                            def run():
+                                out[blocks] = backend.png_deflate(dev, d, seg, blocks=blocks)
+                            return run
+                        for blocks, ms in zip(modes, time_gpu_interleaved([runner(b) for b in modes], a.repeats)):
+                            emit(entry[blocks], ms, seg_bytes=seg, blocks=blocks, bytes_per_frame=int(out[blocks][1].sum().item()) // n,
+                                 plane_bytes=h * w, workspace_bytes=int(ws_of[blocks](n, h, w, d, seg)), **tag)
+                    for blocks in modes:
+                        ms = time_wall(lambda: png.encode_png(dev, palette, blocks=blocks), a.repeats)
+                        emit("encode_png end to end", ms, blocks=blocks, **tag)
+                    payload, sizes = backend.png_deflate(dev, d, blocks=modes[-1])
                     def back():
                         s = sizes.cpu().tolist()
                         block = payload[:, :max(s)].cpu().numpy()
@@ -151,23 +181,30 @@ def main():
             for k, mode, params in ((16, DitherMode.BAYER, {"size": "4x4"}), (256, DitherMode.ERROR_DIFFUSION, {"variant": "floyd_steinberg"})):
                 pal = [tuple(int(v) for v in c) for c in np.random.RandomState(5).randint(0, 256, (k, 3))]
                 dit = ImageDitherer(k, mode, pal, dither_params=params)
-                def route_a():
-                    return dit.apply_dithering_png(img)
+                def route_a(blocks=modes[0]):
+                    return dit.apply_dithering_png(img, blocks=blocks)
+                def route_d():
+                    return route_a(modes[-1])
                 def route_b():
                     buf = io.BytesIO()
                     dit.apply_dithering_indexed(img).save(buf, "PNG")
                     return buf.getvalue()
                 for _ in range(2):
-                    fa, fb = route_a(), route_b()
-                ta, tb = [], []
+                    fa, fb, fd = route_a(), route_b(), route_d()
+                ta, tb, td = [], [], []
                 for _ in range(max(5, a.repeats // 2)):
-                    for fn, acc in ((route_a, ta), (route_b, tb)):
+                    for fn, acc in ((route_a, ta), (route_b, tb)) + (((route_d, td),) if len(modes) > 1 else ()):
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
                         fn()
                         acc.append(1e3 * (time.perf_counter() - t0))
                 same = np.array_equal(np.asarray(Image.open(io.BytesIO(fa)).convert("RGB")), np.asarray(Image.open(io.BytesIO(fb)).convert("RGB")))
-                emit("apply_dithering_png", ta, h=h, w=w, k=k, mode=mode.name, content=content, file_bytes=len(fa), decodes_like_the_other=bool(same))
+                emit("apply_dithering_png", ta, h=h, w=w, k=k, mode=mode.name, content=content, blocks=modes[0], file_bytes=len(fa),
+                     decodes_like_the_other=bool(same))
+                if len(modes) > 1:
+                    same = np.array_equal(np.asarray(Image.open(io.BytesIO(fd)).convert("RGB")), np.asarray(Image.open(io.BytesIO(fb)).convert("RGB")))
+                    emit("apply_dithering_png", td, h=h, w=w, k=k, mode=mode.name, content=content, blocks=modes[-1], file_bytes=len(fd),
+                         decodes_like_the_other=bool(same))
                 emit("apply_dithering_indexed + Image.save", tb, h=h, w=w, k=k, mode=mode.name, content=content, file_bytes=len(fb))
 
 
