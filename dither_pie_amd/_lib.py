@@ -152,6 +152,14 @@ _SIGS_PNG_DYN = {
     "dp_png_code_lengths_host": (_i, [_vp, _i, _i, _i, _vp]),
 }
 EXPORTS_PNG_DYN = tuple(_SIGS_PNG_DYN)
+# include/ditherpie_hip_pattern.h: pattern (Knoll) dithering and its per-palette search table; a table of its own for the
+# same reason.
+_SIGS_PATTERN = {
+    "dp_pattern_prepare": (_i, [_vp]),
+    "dp_pattern_table_bytes": (_sz, [_vp]),
+    "dp_pattern_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+}
+EXPORTS_PATTERN = tuple(_SIGS_PATTERN)
 
 
 def build(force=False):
@@ -194,7 +202,7 @@ def load():
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
-                                          + list(_SIGS_PNG_DYN.items())):
+                                          + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

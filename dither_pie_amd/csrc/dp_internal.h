@@ -144,6 +144,15 @@ struct ThrDev {
     double inv_h, inv_w;
 };
 
+// Device view of a palette's pattern-dither table (pattern.hip; passed to the kernel by value); tab == nullptr: not built
+struct PatDev {
+    const uint8_t *tab;        // 2^24 bytes: the luminance rank of nearest(colour)
+    const uint32_t *c_rank;    // 256: trunc(pal_f32) of the entry of rank i, r | g<<8 | b<<16
+    const uint32_t *out_rank;  // 256: its output bytes, r | g<<8 | b<<16
+    int K;
+    int brick;                 // table addressed by 4x4x4 bricks of the cube (64-byte lines) instead of r | g<<8 | b<<16
+};
+
 }  // namespace dp
 
 struct dp_palette {
@@ -171,6 +180,10 @@ struct dp_palette {
     // by-value snapshot taken under dev_mu (host.cpp: snapshot / publish).  Pointers of an older snapshot stay valid
     // until dp_palette_destroy.
     std::mutex build_mu, dev_mu;
+    // pattern dithering (pattern.hip): the 2^24-entry nearest table and the colours by luminance rank, built at the first
+    // dp_pattern_u8 / dp_pattern_prepare with the palette under build_mu and published under dev_mu like `dev`
+    dp::PatDev pat;
+    void *pat_blob;    // the one allocation behind `pat` (may be null); freed by dp_palette_destroy
 };
 
 struct dp_thresholds {

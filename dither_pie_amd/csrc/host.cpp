@@ -291,6 +291,8 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     p->pts_host = pts;  // for the candidate tables of the diffusion kernels, built when first needed (ensure_ed_tables)
     p->ed_tried = false;
     p->ext_tried = false;
+    p->pat = dp::PatDev{nullptr, nullptr, nullptr, 0, 0};   // the pattern-dither table: built when first needed (pattern.hip)
+    p->pat_blob = nullptr;
     *out = p;
     return DP_OK;
 }
@@ -348,6 +350,7 @@ void dp_palette_destroy(dp_palette *p)
     if (p->ext_blob) (void)hipFree(p->ext_blob);
     if (p->blob) (void)hipFree(p->blob);
     if (p->accel_blob) (void)hipFree(p->accel_blob);
+    if (p->pat_blob) (void)hipFree(p->pat_blob);
     delete p;
 }
 

@@ -83,7 +83,7 @@ __all__ = [
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
-    "WaveletDitherStrategy", "generate_blue_noise",
+    "WaveletDitherStrategy", "PatternDitherStrategy", "generate_blue_noise",
 ]
 
 
@@ -1088,6 +1088,86 @@ class WaveletDitherStrategy(BaseDitherStrategy):
             return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
 
 
+# ------------------------------------------------------------------------------------- Pattern (Knoll)
+class PatternDitherStrategy(BaseDitherStrategy):
+    """Pattern dithering (Thomas Knoll's; Yliluoma's "algorithm 2"), an ordered dither for arbitrary palettes: per pixel a
+    list of n = m * m palette entries whose mean approximates the pixel (n nearest-colour searches, each steered by
+    `strength` times the error accumulated so far), sorted by luminance; the m x m Bayer rank matrix picks one by position.
+    Where the two-nearest ordered modes can only mix two entries, this mixes up to n.  Position-only, hence stable from
+    frame to frame and tileable: _run takes (y0, x0).  GPU kernel and the per-palette 2^24-entry search table in
+    pattern.hip (include/ditherpie_hip_pattern.h has the integer definition); at most 256 colours.
+
+    Not in the reference and not a DitherMode member: pass an instance as ImageDitherer(dither_mode=...), or use
+    dither_frames().  strength256 = round(strength * 256); a strength outside [0, 1], an unknown matrix and a palette of
+    more than 256 colours raise ValueError at dither time."""
+
+    _MATRICES = {"2x2": 2, "4x4": 4, "8x8": 8}
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            'matrix': {'type': 'choice', 'default': '4x4', 'choices': ['2x2', '4x4', '8x8'], 'label': 'Pattern Size',
+                       'description': 'Rank matrix size (larger = more colours mixed per pixel, coarser pattern)'},
+            'strength': {'type': 'float', 'default': 0.5, 'min': 0.0, 'max': 1.0, 'step': 0.05, 'label': 'Strength',
+                         'description': 'Share of the accumulated error that steers the next candidate (0 = nearest colour)'},
+        }
+
+    def __init__(self, matrix: str = "4x4", strength: float = 0.5):
+        self.matrix = matrix
+        self.strength = strength
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'matrix': self.matrix, 'strength': self.strength}
+
+    def _settings(self):
+        m = self._MATRICES.get(self.matrix)
+        if m is None:
+            raise ValueError(f"pattern matrix must be one of {sorted(self._MATRICES)}, not {self.matrix!r}")
+        try:
+            s256 = int(round(float(self.strength) * 256))
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"pattern strength must be a number in [0, 1], not {self.strength!r}") from None
+        if not 0 <= s256 <= 256:
+            raise ValueError(f"pattern strength must lie in [0, 1], not {self.strength!r}")
+        return m, s256
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        m, s256 = self._settings()
+        return backend.pattern(frames, pal, m, s256, y0=y0, x0=x0, out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"pattern dithering needs a non-empty image, not {h} x {w}")
+        self._settings()
+        if len(palette_arr) > 256:
+            raise ValueError(f"pattern dithering supports at most 256 colours, the palette has {len(palette_arr)}")
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None, y0: int = 0, x0: int = 0):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> dithered uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(dither_mode=self, palette=palette, use_gamma=use_gamma).apply_dithering would dither it (palette:
+        the reference's list of RGB triples).  Frames stay in HBM; (y0, x0): the tile's place in a larger image."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, y0=y0, x0=x0, out=out)
+
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8 (at most 256 colours)."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
+
+
+# strategy instances (ImageDitherer(dither_mode=<instance>)) that are per-pixel independent given global coordinates, as
+# ORDERED_MODES are among the enum members: these shard by row bands / tiles (sharding.dither_band)
+ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
+
+
 # ------------------------------------------------------------------------------------- ImageDitherer
 class ImageDitherer:
     """dithering_lib.py:1877-1992.  Plain attributes only, so instances pickle like the reference's
@@ -1131,7 +1211,12 @@ class ImageDitherer:
 
     def _get_dither_strategy(self, mode: DitherMode) -> BaseDitherStrategy:
         """Defaults from get_parameter_info() overlaid by dither_params (dithering_lib.py:1918-1950);
-        unknown mode -> ValueError, unknown parameter -> TypeError from the constructor."""
+        unknown mode -> ValueError, unknown parameter -> TypeError from the constructor.  An addition to the reference's
+        interface: a BaseDitherStrategy INSTANCE as the mode is returned as it is (dither_params do not apply to it) --
+        how modes without a DitherMode member (PatternDitherStrategy, HalftoneDitherStrategy, WaveletDitherStrategy)
+        reach every ImageDitherer / VideoProcessor path."""
+        if isinstance(mode, BaseDitherStrategy):
+            return mode
         if mode in _OUT_OF_SCOPE:
             raise NotImplementedError(
                 f"dither mode {mode.value!r} is outside the MI355X backend's scope "
