@@ -14,8 +14,6 @@
 
 namespace dp {
 
-constexpr int kQueueSmall = 64;   // traversal queue entries: every balanced tree of K <= 256 has <= 51 inner nodes
-constexpr int kQueueLarge = 256;  // ... larger palettes (K <= 1024) and degenerate trees use the large instantiation
 constexpr int kQueueTiles = 65536;  // wave tiles (256 px) with a flagged pixel that the fix-up pass visits directly (queue in the workspace)
 constexpr int kIdxBits = 10;      // palette index bits packed under the distance key (brute-force kernels)
 constexpr int kLocalBits = 8;     // byte offset of a candidate inside its block (cell-table kernel)
@@ -143,6 +141,16 @@ struct ThrDev {
     int pow2;
     double inv_h, inv_w;
 };
+
+// "no thresholds": what the kernels of the nearest-only and IGN modes are given, and what a threshold table starts from
+inline ThrDev no_thresholds()
+{
+    ThrDev t{};  // no table in any form, no classes
+    t.th_h = t.th_w = 1;
+    t.pow2 = 1;
+    t.inv_h = t.inv_w = 1.0;
+    return t;
+}
 
 // Device view of a palette's pattern-dither table (pattern.hip; passed to the kernel by value); tab == nullptr: not built
 struct PatDev {

@@ -215,6 +215,7 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     }
     const uint8_t *base = (const uint8_t *)p->blob;
     PalDev &d = p->dev;
+    d = PalDev{};  // no accelerator, no diffusion tables: they are added when first needed
     d.K = K;
     d.n_nodes = nn;
     d.n_inner = inner;
@@ -226,9 +227,6 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     d.out_rgb = (const uint32_t *)(base + o_org);
     d.lut_in = lut_in ? (base + o_lut) : nullptr;
     d.fcand = (const float4 *)(base + o_fc);
-    d.ftab = nullptr;
-    d.ftab_words = 0;
-    d.ftab_total = 0;
     d.indices = (const int32_t *)(base + o_idx);
     d.split_dim = (const int32_t *)(base + o_sd);
     d.split = (const double *)(base + o_sp);
@@ -240,39 +238,6 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
         d.mins[c] = t.mins[c];
         d.maxes[c] = t.maxes[c];
     }
-    d.cell_tab = nullptr;
-    d.tab_words = 0;
-    d.tab_total = 0;
-    d.cell_tab4 = nullptr;
-    d.tab4_words = 0;
-    d.cell_perm = d.cell_perm4 = nullptr;
-    d.near_slots = 0;
-    d.cell_wide = d.cell_wide4 = nullptr;
-    d.n_wide = d.n_wide4 = 0;
-    d.adapt = 0;
-    d.warp_tab = nullptr;
-    d.comp_tab = nullptr;
-    d.comp_words = d.comp_warp = 0;
-    d.warp_lut = nullptr;
-    d.warp_words = d.warp_total = d.warp_bw = d.warp_adapt = 0;
-    d.n_split = d.n_slow_blocks = 0;
-    d.n_split_cells = 0;
-    d.max_cell = 0;
-    d.code1 = d.code2 = nullptr;
-    d.exc = nullptr;
-    d.n_exc = 0;
-    d.ed_cells = nullptr;
-    d.ed_nodes = nullptr;
-    d.ed_coarse = nullptr;
-    d.ed_lists16 = nullptr;
-    d.ed_h4 = nullptr;
-    d.ed_h4_words = 0;
-    d.ed_h4_shallow = 0;
-    d.ed_h4_global = 0;
-    d.ed_h4_lds_words = 0;
-    d.ed_coarse_ext = nullptr;
-    d.ed_ext16 = nullptr;
-    d.ed_ext_nodes = nullptr;
     p->ed_blob = nullptr;
     p->ext_blob = nullptr;
     p->accel_blob = nullptr;
@@ -420,16 +385,10 @@ static int thresholds_from_device_f32(float *dev_f32, int th_h, int th_w, const 
     if (!t) return DP_ENOMEM;
     t->blob = dev_f32;
     (void)hipGetDevice(&t->device);
+    t->dev = dp::no_thresholds();
     t->dev.th_h = th_h;
     t->dev.th_w = th_w;
     t->dev.f32 = dev_f32;
-    t->dev.m = nullptr;
-    t->dev.sh = 0;
-    t->dev.fpad = nullptr;
-    t->dev.mpad = nullptr;
-    for (uint32_t &wd : t->dev.cls_nib) wd = 0;
-    t->dev.has_cls = 0;
-    t->dev.tw_pad = 0;
     t->blob_pad = nullptr;
     if (sh >= 0) {
         m.resize(n);

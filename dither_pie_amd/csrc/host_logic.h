@@ -23,6 +23,8 @@ namespace dp {
 
 constexpr int kLeafSize = 10;     // scipy.spatial.KDTree default (dithering_lib.py:339)
 constexpr int kWideList = 16;     // entries of the flat candidate list of a split cell (ordered_fast_kernel, accel.hip)
+constexpr int kQueueSmall = 64;   // traversal queue entries: every balanced tree of K <= 256 has <= 51 inner nodes
+constexpr int kQueueLarge = 256;  // ... larger palettes (K <= 1024) and degenerate trees use the large instantiation
 
 // KD-tree as scipy builds it; node 0 is the root, children follow in pre-order.
 struct HostTree {

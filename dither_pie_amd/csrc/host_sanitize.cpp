@@ -26,6 +26,9 @@
 //                                     int32 frames, h, w, depth, seg_bytes and frames * h * w index bytes; every frame prints
 //                                     its size and its zlib stream in hex (inflated and compared by the test)
 //   host_xxx pngdyn <cases.bin> <n>   the same with dynamic-Huffman blocks as a third candidate (png_deflate_encode_dyn)
+//   host_xxx orderedplan <cases.bin> <n>   the kernel choice of the ordered dither (ordered_plan.h: plan_ordered): n records of
+//                                     one OrderedFacts and one OrderedSwitches (int32 fields in declaration order); prints one
+//                                     plan per line (compared with tests/ordered_plan_ref.py by the test)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +36,7 @@
 #include <string>
 
 #include "host_logic.h"
+#include "ordered_plan.h"
 
 using namespace dp;
 
@@ -552,10 +556,35 @@ static int run_pngdeflate(const char *path, const int n_cases, const bool dynami
     return 0;
 }
 
+// ---- ordered dither: which kernel serves a call ------------------------------------------------------------------
+static int run_orderedplan(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        OrderedFacts facts;
+        OrderedSwitches sw;
+        if (fread(&facts, sizeof(facts), 1, f) != 1 || fread(&sw, sizeof(sw), 1, f) != 1 || facts.hw < 1 || facts.w < 1 || facts.n_cus < 1) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const OrderedPlan p = plan_ordered(facts, sw);
+        static const char *const tables[] = {"plain8", "plain4", "warped"};
+        printf("plan %d %s %d %d %d %d %d %s %u %u %u %u %u %u %u %d %d %u\n", c, family_name(p.family), p.mode, p.bw, (int)p.adapt, (int)p.warp,
+               (int)p.half, tables[p.table], p.grid, p.block, p.n_tiles, p.n_words, p.adv_y, p.adv_x, p.lds_bytes, p.fix_mode,
+               (int)p.fix_big_queue, p.fix_grid);
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn <cases.bin> <n>  |  orderedplan <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -563,6 +592,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "giflzw") return run_giflzw(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "pngdeflate") return run_pngdeflate(argv[2], atoi(argv[3]), false);
     if (std::string(argv[1]) == "pngdyn") return run_pngdeflate(argv[2], atoi(argv[3]), true);
+    if (std::string(argv[1]) == "orderedplan") return run_orderedplan(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

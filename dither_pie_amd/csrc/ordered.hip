@@ -7,29 +7,23 @@
 // coalesced across the wave (768 B per wave each way), finds the two (three) nearest palette entries
 // exactly and evaluates the reference's float64 decision `s0/(s0+s1) <= t` exactly (integer palettes:
 // d0 * 2^sh <= m * (d0+d1) for t = m/2^sh, provably the same decision except when both sides are equal).
-// Which kernel runs (launch_ordered):
-//   ordered_lean_kernel<MODE>        integer palettes with a cell table (accel.hip): the fast path -- LDS
-//                                    candidate blocks, branch-free main loop, rare pixels (split cells,
-//                                    distance ties, exact equality, row-straddling groups) deferred to a
-//                                    wave-private queue and resolved densely with tie codes / exceptions
-//   ordered_lean_float_kernel<MODE>  float (use_gamma) palettes with a cell table: float32 ranking with a
-//                                    certainty gap, float64 recomputation of the winners
-//   ordered_cell_kernel<MODE>        the previous generation of the fast path (inline rare paths); kept for
-//                                    buffers that are not dword-aligned
-//   ordered_int_kernel / ordered_f64_kernel   brute force over the whole palette (no accelerator)
+// Which kernel runs: launch_ordered fills the facts of a call, plan_ordered (ordered_plan.h) decides -- the order of
+// precedence of the seven families and the measurements behind it are written down there, and
+// tests/test_ordered_plan_cpu.py checks the decision without a GPU -- and tile_kernel / brute_kernel / fix_kernel at the
+// end of this file map a plan to one of the instantiations the library ships.
 // Pixels whose result depends on scipy's visiting order in a way no table expresses, and near ties of the
 // float path, only set a flag bit; fixup_kernel compacts the flagged pixels per workgroup into LDS and
 // resolves them through the scipy-order KD-tree emulation (tree_query) and the literal float64 chain.
 #include <type_traits>
 
 #include "dp_internal.h"
+#include "ordered_plan.h"
 #include "tree_query.hip.h"
 
 namespace dp {
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kListCap = 16384;           // LDS pixel list of the fix-up pass (64 KiB) = one full batch
 constexpr int kLdsTreeK = 256;            // palettes up to this size (and kLdsTreeNodes nodes) get their tree staged in LDS
 constexpr int kLdsTreeNodes = 512;
@@ -261,7 +255,6 @@ __global__ __launch_bounds__(kBlock) void ordered_int_kernel(const uint8_t *__re
 // colour (a rare L2 read); exact equality in the decision replays the reference's float64 chain
 // inline; only tie code 3 and overflowing sub-cells are flagged for the fix-up pass.
 // ---------------------------------------------------------------------------------------------
-constexpr int kCellBlock = 1024;
 
 // Keys of the 8 candidates of one block and the three smallest of them.
 //   key = ((|p|^2 - 2 x.p) << 8) | (4*idx)      (4*idx = byte offset of the candidate inside its block)
@@ -641,16 +634,6 @@ __global__ __launch_bounds__(kCellBlock) void ordered_cell_kernel(const uint8_t 
 // MODE: 0 nearest only; 1 matrix in integer form (table in LDS); 2 matrix float32 (table read from
 // global memory, it stays in L1); 3 IGN.
 // ---------------------------------------------------------------------------------------------
-constexpr int kLeanLdsWords = 160 * 1024 / 4;
-constexpr int kLeanQueue = 128;                                         // entries per wave
-constexpr int kLeanQueueWords = (kCellBlock / 64) * kLeanQueue;         // 8 KB at the top of LDS
-constexpr int kLeanTabBytes = (kLeanLdsWords - kLeanQueueWords) * 4;    // table + thresholds must fit below
-constexpr int kLeanHalfLdsWords = 80 * 1024 / 4;                        // HALF instances: two workgroups per CU
-constexpr int kLeanHalfQueue = 112;                                     // entries per wave: drained from 48 up (47 + 64 at most)
-constexpr int kLeanHalfDrain = 48;
-constexpr int kLeanHalfTabBytes = (kLeanHalfLdsWords - (kCellBlock / 64) * kLeanHalfQueue) * 4;
-constexpr int kWarpLutBytes = 768;                                      // tables over warped cells: the three maps ...
-constexpr int kWarpLutAt = kLeanTabBytes - kWarpLutBytes;               // ... sit right below the queue
 
 // Cell coordinates of a colour: the colour itself, or (tables over warped cells, accel.hip) its three bytes mapped
 // through the per-channel tables staged in LDS.
@@ -1253,10 +1236,6 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
 // 0x80000000 | byte offset of the split node's eight blocks, or 0xC0000000 (a single colour with more than eight
 // candidates: fix-up pass).
 // ---------------------------------------------------------------------------------------------
-constexpr int kCompactHalfWords = 80 * 1024 / 4;
-constexpr uint32_t kCompactRecBytes = 256 * 8;                           // LDS: records at 0 ...
-constexpr uint32_t kCompactLutAt = kCompactRecBytes;                     // ... the three warp maps ...
-constexpr uint32_t kCompactTabAt = kCompactLutAt + kWarpLutBytes;        // ... the table, then integer thresholds
 
 // keys of eight palette records and the three smallest (see cand8); r_k = {colour, |p|^2 << 8 | index}
 __device__ __forceinline__ void cand8r(const uint32_t x, const uint2 r0, const uint2 r1, const uint2 r2, const uint2 r3,
@@ -1771,9 +1750,7 @@ __device__ __forceinline__ bool resolve_wide(const uint32_t x, const LeanThr &th
     return true;
 }
 
-constexpr int kFastQueue = 128;  // entries per wave and queue (A and B)
-
-template <int MODE, int BW, int DBG = 0>  // DBG (measurements only, wrong pixels): 1 = nothing deferred is resolved
+template <int MODE, int BW>
 __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t *__restrict__ in,
                                                                   uint8_t *__restrict__ out,
                                                                   unsigned long long *__restrict__ flags,
@@ -1901,7 +1878,7 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
     }
     // Which pixel slots of this wave tile can only take their nearest entry (thr.cls, host.cpp): a property of the position
     // of the wave's first pixel in the threshold table, valid when the 256 pixels of the wave lie in one image row.
-    const bool use_cls = (MODE == 1 || MODE == 2) && thr.has_cls != 0 && !(DBG & 2);
+    const bool use_cls = (MODE == 1 || MODE == 2) && thr.has_cls != 0;
     auto tile_class = [&](const uint32_t ty, const uint32_t tx, const uint32_t gi) -> uint32_t {
         if (MODE == 0) return 15u;
         if (!use_cls) return 0u;
@@ -2027,26 +2004,20 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
             qa += (uint32_t)__popcll(rb);
         }
         // the partial last group (its twelve bytes may not all exist): pixel by pixel through queue B
-        if ((tile + 1u) * kCellBlock > n_full && !(DBG & 1)) {  // scalar: the last tile of the launch only
+        if ((tile + 1u) * kCellBlock > n_full) {  // scalar: the last tile of the launch only
 #pragma unroll
             for (int q = 0; q < 4; ++q) push_b(gidx == n_full && gidx * 4u + (uint32_t)q < g.n_px, gidx * 4u + (uint32_t)q);
         }
-        if (DBG & 1) {
-            qa = 0u;
-        } else {
-            if (pending) finish_a();
-            if (qa >= 64u) start_a();
-        }
+        if (pending) finish_a();
+        if (qa >= 64u) start_a();
     }
-    if (!(DBG & 1)) {
-        while (pending || qa != 0u) {
-            if (pending) finish_a();
-            if (qa != 0u) start_a();
-        }
-        while (qb != 0u) {
-            __threadfence_block();
-            drain_b(qb < 64u ? qb : 64u);
-        }
+    while (pending || qa != 0u) {
+        if (pending) finish_a();
+        if (qa != 0u) start_a();
+    }
+    while (qb != 0u) {
+        __threadfence_block();
+        drain_b(qb < 64u ? qb : 64u);
     }
 }
 
@@ -2272,9 +2243,6 @@ __global__ __launch_bounds__(kCellBlock) void ordered_lean_float_kernel(const ui
 // the fix-up pass: the same rare branch ranks the block's eight candidates in float64 (compact_float_rare), only exact
 // float64 ties remain flagged -- the fix-up pass of the 24-frame batch drops from 0.12 ms to 0.006.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t kCfRecBytes = 256 * 16;
-constexpr uint32_t kCfLutAt = kCfRecBytes;
-constexpr uint32_t kCfTabAt = kCfLutAt + 256;
 
 // The rare pixels of ordered_compact_float_kernel, out of line so that their float64 arithmetic does not take registers
 // from the main loop (a call about once per 50 tiles).  what = 1: the float64 chain decides between the two winners
@@ -2793,8 +2761,6 @@ int num_cus()
     return cached;
 }
 
-static inline bool env_set(const char *name) { return exp_env(name) != nullptr; }
-
 // experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel family of every launch on stderr (tests that must know
 // which kernel a case reached); the product library compiles to nothing here
 static inline void trace_family(const char *family, bool aligned)
@@ -2807,27 +2773,93 @@ static inline void trace_family(const char *family, bool aligned)
 #endif
 }
 
-template <int MODE>
-int launch_cell(uint32_t grid, size_t lds, hipStream_t s, const uint8_t *in, uint8_t *out, unsigned long long *flags,
-                const Geo &g, const PalDev &pal, const ThrDev &thr, float sx, float sy, float sc, uint32_t n_tiles)
+// ---- plan -> kernel: every instantiation of the ordered kernels that the library ships is named here, once ----------------
+using TileKernel = void (*)(const uint8_t *, uint8_t *, unsigned long long *, Geo, PalDev, ThrDev, float, float, float, uint32_t);
+using BruteKernel = void (*)(const uint8_t *, uint8_t *, unsigned long long *, Geo, PalDev, ThrDev, float, float, float);
+using FixKernel = void (*)(const uint8_t *, uint8_t *, const unsigned long long *, uint32_t, Geo, PalDev, ThrDev, float, float, float);
+
+template <int M>
+TileKernel tile_kernel_of(const OrderedPlan &p)
 {
-    auto kern = ordered_cell_kernel<MODE>;
-    // more than 64 KB of dynamic LDS has to be granted per function (once per device is enough,
-    // repeating it is cheap)
-    DP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kCellBlock), lds, s, in, out, flags, g, pal, thr, sx, sy, sc, n_tiles);
-    return DP_OK;
+    switch (p.family) {
+    case kFamCell:
+        return ordered_cell_kernel<M>;
+    case kFamFast:
+        if (p.bw == 4) return ordered_fast_kernel<M, 4>;
+        return ordered_fast_kernel<M, 8>;
+    case kFamLean:  // <MODE, BW, ADAPT, WARP, HALF>
+        if (p.warp && p.bw == 4) return ordered_lean_kernel<M, 4, false, true>;
+        if (p.warp && p.adapt) return ordered_lean_kernel<M, 8, true, true>;
+        if (p.warp) return ordered_lean_kernel<M, 8, false, true>;
+        if (p.bw == 4 && p.half) return ordered_lean_kernel<M, 4, false, false, true>;
+        if (p.bw == 4) return ordered_lean_kernel<M, 4, false, false>;
+        if (p.adapt) return ordered_lean_kernel<M, 8, true, false>;
+        return ordered_lean_kernel<M, 8, false, false>;
+    case kFamCompact:  // <MODE, WARP, HALF>
+        if (p.warp && p.half) return ordered_compact_kernel<M, true, true>;
+        if (p.warp) return ordered_compact_kernel<M, true, false>;
+        if (p.half) return ordered_compact_kernel<M, false, true>;
+        return ordered_compact_kernel<M, false, false>;
+    case kFamLeanFloat:  // (float palettes have no integer decision: no MODE 1)
+        if constexpr (M != 1) return ordered_lean_float_kernel<M>;
+        break;
+    case kFamCompactFloat:
+        if constexpr (M != 1) return ordered_compact_float_kernel<M>;
+        break;
+    case kFamBrute:
+        break;
+    }
+    return nullptr;
 }
 
-template <int MODE>
-void launch_pass1(bool integer, dim3 grid, hipStream_t s, const uint8_t *in, uint8_t *out, unsigned long long *flags,
-                  const Geo &g, const PalDev &pal, const ThrDev &thr, float sx, float sy, float sc)
+TileKernel tile_kernel(const OrderedPlan &p)
 {
-    if (integer)
-        hipLaunchKernelGGL(ordered_int_kernel<MODE>, grid, dim3(kBlock), 0, s, in, out, flags, g, pal, thr, sx, sy, sc);
-    else
-        hipLaunchKernelGGL(ordered_f64_kernel<MODE>, grid, dim3(kBlock), 0, s, in, out, flags, g, pal, thr, sx, sy, sc);
+    switch (p.mode) {
+    case 0: return tile_kernel_of<0>(p);
+    case 1: return tile_kernel_of<1>(p);
+    case 2: return tile_kernel_of<2>(p);
+    case 3: return tile_kernel_of<3>(p);
+    }
+    return nullptr;
+}
+
+// (ordered_f64_kernel<1> is named but never planned: MODE 1 needs an integer palette)
+BruteKernel brute_kernel(const OrderedPlan &p, const bool integer)
+{
+    switch (p.mode) {
+    case 0: return integer ? ordered_int_kernel<0> : ordered_f64_kernel<0>;
+    case 1: return integer ? ordered_int_kernel<1> : ordered_f64_kernel<1>;
+    case 2: return integer ? ordered_int_kernel<2> : ordered_f64_kernel<2>;
+    case 3: return integer ? ordered_int_kernel<3> : ordered_f64_kernel<3>;
+    }
+    return nullptr;
+}
+
+FixKernel fix_kernel(const OrderedPlan &p)
+{
+    const bool big = p.fix_big_queue;
+    switch (p.fix_mode) {
+    case 0: return big ? fixup_kernel<0, kQueueLarge> : fixup_kernel<0, kQueueSmall>;
+    case 2: return big ? fixup_kernel<2, kQueueLarge> : fixup_kernel<2, kQueueSmall>;
+    case 3: return big ? fixup_kernel<3, kQueueLarge> : fixup_kernel<3, kQueueSmall>;
+    }
+    return nullptr;
+}
+
+// what plan_ordered reads, line by line in the order of the declaration (ordered_plan.h: OrderedFacts)
+OrderedFacts facts_of(const PalDev &pal, const ThrDev &thr, const Geo &g, const int mode)
+{
+    return OrderedFacts{mode, pal.K, pal.is_integer, pal.n_inner,
+                        g.n_px, g.hw, g.w,
+                        g.y0, g.x0, g.aligned,
+                        pal.cell_tab != nullptr, pal.tab_words, pal.tab_total,
+                        pal.cell_tab4 != nullptr, pal.tab4_words,
+                        pal.warp_tab != nullptr, pal.warp_words, pal.warp_total, pal.warp_bw, pal.warp_adapt,
+                        pal.adapt, pal.cell_perm != nullptr, pal.cell_perm4 != nullptr, pal.n_wide, pal.n_wide4,
+                        pal.comp_tab != nullptr, pal.comp_words, pal.comp_warp,
+                        pal.ftab != nullptr, pal.ftab_words,
+                        thr.m != nullptr, thr.mpad != nullptr, thr.fpad != nullptr, thr.th_h, thr.th_w, thr.tw_pad,
+                        num_cus()};
 }
 
 }  // namespace
@@ -2837,28 +2869,21 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                    size_t ws_bytes, hipStream_t s)
 {
     (void)ws_bytes;
-    ThrDev thr;
-    thr.th_h = thr.th_w = 1;
-    thr.f32 = nullptr;
-    thr.m = nullptr;
-    thr.sh = 0;
-    thr.fpad = nullptr;
-    thr.mpad = nullptr;
-    for (uint32_t &wd : thr.cls_nib) wd = 0;
-    thr.has_cls = 0;
-    thr.tw_pad = 0;
-    thr.pow2 = 1;
-    thr.inv_h = thr.inv_w = 1.0;
-    if (mode == DP_MODE_MATRIX) thr = *thr_in;
-    // a single colour: every pixel maps to it, and the k=2 query of the reference has no second entry
-    if (pal.K == 1) mode = DP_MODE_NEAREST;
+    const ThrDev thr = mode == DP_MODE_MATRIX ? *thr_in : no_thresholds();
+    // the experiment switches of the decision (all off in the product library)
+    OrderedSwitches sw;
+    sw.lean_no_half = exp_env("DP_LEAN_NO_HALF") != nullptr;
+    sw.fast_all = exp_env("DP_FAST_ALL") != nullptr;
+    sw.force_compact = exp_env("DP_FORCE_COMPACT") != nullptr;
+    sw.no_compact_kernel = exp_env("DP_NO_COMPACT_KERNEL") != nullptr;
+    sw.compact_no_half = exp_env("DP_COMPACT_NO_HALF") != nullptr;
 
     const float sx = (float)((double)ign_seed * 0.37), sy = (float)((double)ign_seed * 0.73);
     const int64_t hw = (int64_t)h * w;
     // frames per launch so that pixel indices stay below 2^30
     // (2^30: the lean kernels' queue entries keep the index of a group of four pixels in 28 bits)
     const int64_t max_frames = std::max<int64_t>(1, ((int64_t)1 << 30) / hw - 1);
-    unsigned long long *flags = reinterpret_cast<unsigned long long *>(ws);
+    unsigned long long *fl = reinterpret_cast<unsigned long long *>(ws);  // chunks run back to back on one stream: the bitmap is reused
     // the dirty word lives in the slack behind the largest possible bitmap of this call
     const size_t dirty_off = ((size_t)((std::min(max_frames, n_frames) * hw + 255) / 256) * 32 + 768) & ~size_t(7);
 
@@ -2879,263 +2904,44 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         g.tx0 = x0 % thr.th_w;
         g.aligned = (((uintptr_t)in_c | (uintptr_t)out_c) & 3) == 0;
         g.neg2 = -(2 << kLocalBits);
-        g.adv_y = g.adv_x = 0;
         g.dirty = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ws) + dirty_off);
+        const OrderedPlan plan = plan_ordered(facts_of(pal, thr, g, mode), sw);
+        g.adv_y = plan.adv_y;
+        g.adv_x = plan.adv_x;
+        const bool brute = plan.family == kFamBrute;
+        const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
+        const TileKernel tile_k = brute ? nullptr : tile_kernel(plan);
+        const FixKernel fix_k = fix_kernel(plan);
+        if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
+            set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
+            return DP_EUNSUPPORTED;
+        }
         DP_HIP(hipMemsetAsync(g.dirty, 0, sizeof(uint32_t), s));  // the count; queue entries need no reset
-        const uint32_t groups = (g.n_px + 3) / 4;
-        const uint32_t blocks = (groups + kBlock - 1) / kBlock;
-        uint32_t n_words = blocks * (kBlock / 64) * 4;
-        unsigned long long *fl = flags;  // chunks run back to back on one stream: the bitmap is reused
-        const bool integer = pal.is_integer != 0;
-        int fix_mode;
-        const char *family = "brute";  // (trace_family: which pass-1 kernel this launch takes)
         ProfMark *pm = prof_begin(s);
-        const bool int_thr_ok = thr.m != nullptr && thr.th_h * thr.th_w <= 256;
-        // the table the lean kernels would stage: 4-entry blocks when the accelerator built them, else 8-entry blocks
-        // ... or, crowded palettes, the table over warped cells (with its maps)
-        const bool warp = pal.warp_tab != nullptr;
-        const bool small = warp ? pal.warp_bw == 4 : pal.cell_tab4 != nullptr;
-        const size_t lean_tab_bytes = warp ? 4 * (size_t)pal.warp_words + kWarpLutBytes : 4 * (size_t)(small ? pal.tab4_words : pal.tab_words);
-        const bool geo_ok = integer && (warp || small || pal.cell_tab != nullptr) && g.aligned && y0 >= 0 && x0 >= 0 && g.n_px <= (1u << 30);
-        const bool lean_geo = geo_ok && lean_tab_bytes <= (size_t)kLeanTabBytes;
-        const bool int_lean = thr.mpad != nullptr && lean_tab_bytes + (size_t)thr.th_h * thr.tw_pad * 4 <= (size_t)kLeanTabBytes;
-        const bool lean_ok = lean_geo && (mode == DP_MODE_NEAREST || mode == DP_MODE_IGN ||
-                                          (mode == DP_MODE_MATRIX && (int_lean || thr.fpad != nullptr)));
-        const bool whole_tab = pal.cell_tab != nullptr && pal.tab_total == pal.tab_words;  // the general kernel stages all of it
-        if (integer && (lean_ok || whole_tab)) {
-            // fast path: LDS cell table + tie codes, persistent 1024-lane workgroups over 4096-pixel tiles
-            const uint32_t n_tiles = (groups + kCellBlock - 1) / kCellBlock;
-            n_words = n_tiles * (kCellBlock / 64) * 4;
-            const size_t lds = sizeof(uint32_t) * ((size_t)pal.tab_words + 256);  // launch_cell (plain table) only
-            // 4-entry blocks on plain cells that leave half of LDS free: two workgroups per CU (DP_LEAN_NO_HALF=1: one)
-            const bool half = lean_ok && small && !warp && !exp_env("DP_LEAN_NO_HALF") &&
-                              lean_tab_bytes + (mode == DP_MODE_MATRIX && int_lean ? (size_t)thr.th_h * thr.tw_pad * 4 : 0) <= (size_t)kLeanHalfTabBytes;
-            const uint32_t cgrid = std::min<uint32_t>(n_tiles, (uint32_t)num_cus() * (half ? 2u : 1u));
-            {
-                const uint64_t adv = ((uint64_t)cgrid * kCellBlock * 4u) % (uint64_t)hw;
-                g.adv_y = (uint32_t)(adv / (uint64_t)w);
-                g.adv_x = (uint32_t)(adv % (uint64_t)w);
-            }
-            int rc;
-            PalDev pal4 = pal;  // the table the lean kernel stages, in the fields it reads
-            if (warp) {
-                pal4.cell_tab = pal.warp_tab;
-                pal4.tab_words = pal.warp_words;
-                pal4.tab_total = pal.warp_total;
-            } else if (small) {
-                pal4.cell_tab = pal.cell_tab4;
-                pal4.tab_words = pal.tab4_words;
-                pal4.tab_total = pal.tab4_words;
-            }
-            // crowded palettes (many split cells, or a table larger than LDS): the instantiation that adapts per wave
-            const bool adapt = warp ? pal.warp_adapt != 0 : (!small && pal.adapt != 0);
-#define DP_LEAN_K(M, BW, AD, WP)                                                                                         \
-    hipLaunchKernelGGL((ordered_lean_kernel<M, BW, AD, WP>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, \
-                       sx, sy, ign_scale, n_tiles)
-#define DP_LEAN(M)                                                                                                        \
-    do {                                                                                                                 \
-        if (warp && small) DP_LEAN_K(M, 4, false, true);                                                                 \
-        else if (warp && adapt) DP_LEAN_K(M, 8, true, true);                                                             \
-        else if (warp) DP_LEAN_K(M, 8, false, true);                                                                     \
-        else if (small && half)                                                                                          \
-            hipLaunchKernelGGL((ordered_lean_kernel<M, 4, false, false, true>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, \
-                               pal4, thr, sx, sy, ign_scale, n_tiles);                                                   \
-        else if (small) DP_LEAN_K(M, 4, false, false);                                                                   \
-        else if (adapt) DP_LEAN_K(M, 8, true, false);                                                                    \
-        else DP_LEAN_K(M, 8, false, false);                                                                              \
-    } while (0)
-            // uncrowded palettes on plain cells: the fast kernel (nearest set staged first; see ordered_fast_kernel)
-            const uint32_t *perm = small ? pal.cell_perm4 : pal.cell_perm;
-            const size_t fast_tab_bytes = 4096u * (small ? 4u : 8u) * 4u;
-            // (the fast kernel stages the 4096 cell blocks, the flat lists of the split cells, integer thresholds, two queues)
-            const size_t fast_fixed = fast_tab_bytes + (size_t)(small ? pal.n_wide4 : pal.n_wide) * kWideList * 4 +
-                                      2 * (kCellBlock / 64) * kFastQueue * 4;
-            const bool int_fast = thr.mpad != nullptr && fast_fixed + (size_t)thr.th_h * thr.tw_pad * 4 <= sizeof(uint32_t) * kLeanLdsWords;
-            // Measured on MI355X (tools/bench_scripts/fast_vs_lean.py, 24 4K frames, 256 colours): nearest-only mode
-            // 0.45 ms against 0.50 ms of the lean kernel; with a matrix the per-slot class branches cost more than the
-            // shorter candidate network saves (0.66 against 0.55 ms), so the matrix / IGN modes stay on the lean kernel
-            // unless DP_FAST_ALL is set (experiments).
-            const bool fast_mode = mode == DP_MODE_NEAREST || exp_env("DP_FAST_ALL") != nullptr;
-            const bool fast_ok = fast_mode && geo_ok && !warp && !adapt && perm != nullptr && fast_fixed <= sizeof(uint32_t) * kLeanLdsWords &&
-                                 (mode == DP_MODE_NEAREST || mode == DP_MODE_IGN ||
-                                  (mode == DP_MODE_MATRIX && (int_fast || thr.fpad != nullptr)));
-            const int dbg = exp_env("DP_FAST_DBG") ? atoi(exp_env("DP_FAST_DBG")) : 0;  // (measurement switch)
-#define DP_FAST(M)                                                                                                        \
-    do {                                                                                                                 \
-        if (dbg == 1 && !small) hipLaunchKernelGGL((ordered_fast_kernel<M, 8, 1>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, sx, sy, ign_scale, n_tiles); \
-        else if (dbg == 2 && !small) hipLaunchKernelGGL((ordered_fast_kernel<M, 8, 2>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, sx, sy, ign_scale, n_tiles); \
-        else if (dbg == 3 && !small) hipLaunchKernelGGL((ordered_fast_kernel<M, 8, 3>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, sx, sy, ign_scale, n_tiles); \
-        else if (small) hipLaunchKernelGGL((ordered_fast_kernel<M, 4>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, sx, sy, ign_scale, n_tiles); \
-        else hipLaunchKernelGGL((ordered_fast_kernel<M, 8>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal4, thr, sx, sy, ign_scale, n_tiles); \
-    } while (0)
-            // crowded palettes: the compact kernel (the whole octree in LDS, every pixel resolved in place), two workgroups
-            // per CU when table + colours + maps + thresholds fit 80 KB
-            const size_t comp_base = pal.comp_tab ? (size_t)kCompactTabAt + 4 * (size_t)pal.comp_words : 0;
-            // (integer thresholds go to LDS behind the table; a table too large for that -- blue noise -- is read as float32 from L1)
-            const bool int_comp = mode == DP_MODE_MATRIX && thr.mpad != nullptr &&
-                                  comp_base + (size_t)thr.th_h * thr.tw_pad * 4 <= sizeof(uint32_t) * kLeanLdsWords;
-            const size_t comp_bytes = comp_base + (int_comp ? (size_t)thr.th_h * thr.tw_pad * 4 : 0);
-            const bool comp_ok = pal.comp_tab != nullptr && geo_ok && (adapt || env_set("DP_FORCE_COMPACT")) && comp_bytes <= sizeof(uint32_t) * kLeanLdsWords &&
-                                 (mode == DP_MODE_NEAREST || mode == DP_MODE_IGN || (mode == DP_MODE_MATRIX && (int_comp || thr.fpad != nullptr))) &&
-                                 !env_set("DP_NO_COMPACT_KERNEL");
-            const bool comp_half = comp_ok && comp_bytes <= sizeof(uint32_t) * kCompactHalfWords && !env_set("DP_COMPACT_NO_HALF");
-            const uint32_t pgrid = std::min<uint32_t>(n_tiles, (uint32_t)num_cus() * (comp_half ? 2u : 1u));
-            if (comp_ok) {
-                const uint64_t adv = ((uint64_t)pgrid * kCellBlock * 4u) % (uint64_t)hw;
-                g.adv_y = (uint32_t)(adv / (uint64_t)w);
-                g.adv_x = (uint32_t)(adv % (uint64_t)w);
-            }
-#define DP_COMP_K(M, WP, HF)                                                                                             \
-    hipLaunchKernelGGL((ordered_compact_kernel<M, WP, HF>), dim3(pgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, \
-                       ign_scale, n_tiles)
-#define DP_COMP(M)                                                                                                        \
-    do {                                                                                                                 \
-        if (pal.comp_warp && comp_half) DP_COMP_K(M, true, true);                                                        \
-        else if (pal.comp_warp) DP_COMP_K(M, true, false);                                                               \
-        else if (comp_half) DP_COMP_K(M, false, true);                                                                   \
-        else DP_COMP_K(M, false, false);                                                                                 \
-    } while (0)
-            if (comp_ok && mode == DP_MODE_NEAREST) {
-                DP_COMP(0);
-                family = "compact";
-                rc = DP_OK;
-                fix_mode = 0;
-            } else if (comp_ok && mode == DP_MODE_IGN) {
-                DP_COMP(3);
-                family = "compact";
-                rc = DP_OK;
-                fix_mode = 3;
-            } else if (comp_ok && mode == DP_MODE_MATRIX && int_comp) {
-                DP_COMP(1);
-                family = "compact";
-                rc = DP_OK;
-                fix_mode = 2;
-            } else if (comp_ok && mode == DP_MODE_MATRIX) {
-                DP_COMP(2);
-                family = "compact";
-                rc = DP_OK;
-                fix_mode = 2;
-#undef DP_COMP
-#undef DP_COMP_K
-            } else if (fast_ok && mode == DP_MODE_NEAREST) {
-                DP_FAST(0);
-                family = "fast";
-                rc = DP_OK;
-                fix_mode = 0;
-            } else if (fast_ok && mode == DP_MODE_IGN) {
-                DP_FAST(3);
-                family = "fast";
-                rc = DP_OK;
-                fix_mode = 3;
-            } else if (fast_ok && mode == DP_MODE_MATRIX && int_fast) {
-                DP_FAST(1);
-                family = "fast";
-                rc = DP_OK;
-                fix_mode = 2;
-            } else if (fast_ok && mode == DP_MODE_MATRIX && thr.fpad != nullptr) {
-                DP_FAST(2);
-                family = "fast";
-                rc = DP_OK;
-                fix_mode = 2;
-#undef DP_FAST
-            } else if (lean_geo && mode == DP_MODE_NEAREST) {
-                DP_LEAN(0);
-                family = "lean";
-                rc = DP_OK;
-                fix_mode = 0;
-            } else if (lean_geo && mode == DP_MODE_IGN) {
-                DP_LEAN(3);
-                family = "lean";
-                rc = DP_OK;
-                fix_mode = 3;
-            } else if (lean_geo && mode == DP_MODE_MATRIX && int_lean) {
-                DP_LEAN(1);
-                family = "lean";
-                rc = DP_OK;
-                fix_mode = 2;
-            } else if (lean_geo && mode == DP_MODE_MATRIX && thr.fpad != nullptr) {
-                DP_LEAN(2);
-                family = "lean";
-                rc = DP_OK;
-                fix_mode = 2;
-#undef DP_LEAN
-#undef DP_LEAN_K
-            } else if (mode == DP_MODE_NEAREST) {
-                family = "cell";
-                rc = launch_cell<0>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
-                fix_mode = 0;
-            } else if (mode == DP_MODE_IGN) {
-                family = "cell";
-                rc = launch_cell<3>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
-                fix_mode = 3;
-            } else if (int_thr_ok) {
-                family = "cell";
-                rc = launch_cell<1>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
-                fix_mode = 2;
-            } else {
-                family = "cell";
-                rc = launch_cell<2>(cgrid, lds, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles);
-                fix_mode = 2;
-            }
-            if (rc != DP_OK) return rc;
-        } else if (!integer && pal.ftab != nullptr && g.aligned && y0 >= 0 && x0 >= 0 &&
-                   (size_t)pal.ftab_words * 4 + (size_t)pal.K * 16 + 256 <= sizeof(uint32_t) * kLeanLdsWords &&  // staged part
-                   (mode != DP_MODE_MATRIX || thr.fpad != nullptr)) {
-            // float (gamma) palettes with a cell table
-            // the one-byte-per-entry table (K <= 256): records + lut + table in LDS
-            const size_t cf_bytes = pal.comp_tab ? (size_t)kCfTabAt + 4 * (size_t)pal.comp_words : 0;
-            const bool cf_ok = pal.comp_tab != nullptr && cf_bytes <= sizeof(uint32_t) * kLeanLdsWords && !env_set("DP_NO_COMPACT_KERNEL");
-            const uint32_t n_tiles = (groups + kCellBlock - 1) / kCellBlock;
-            n_words = n_tiles * (kCellBlock / 64) * 4;
-            const uint32_t cgrid = std::min<uint32_t>(n_tiles, (uint32_t)num_cus());
-            const uint64_t adv = ((uint64_t)cgrid * kCellBlock * 4u) % (uint64_t)hw;
-            g.adv_y = (uint32_t)(adv / (uint64_t)w);
-            g.adv_x = (uint32_t)(adv % (uint64_t)w);
-#define DP_LEANF(M)                                                                                                      \
-    do {                                                                                                                 \
-        if (cf_ok) hipLaunchKernelGGL((ordered_compact_float_kernel<M>), dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles); \
-        else hipLaunchKernelGGL(ordered_lean_float_kernel<M>, dim3(cgrid), dim3(kCellBlock), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale, n_tiles); \
-    } while (0)
-            family = cf_ok ? "compact_float" : "lean_float";
-            if (mode == DP_MODE_NEAREST) {
-                DP_LEANF(0);
-                fix_mode = 0;
-            } else if (mode == DP_MODE_IGN) {
-                DP_LEANF(3);
-                fix_mode = 3;
-            } else {
-                DP_LEANF(2);
-                fix_mode = 2;
-            }
-#undef DP_LEANF
-        } else if (mode == DP_MODE_NEAREST) {
-            launch_pass1<0>(integer, dim3(blocks), s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
-            fix_mode = 0;
-        } else if (mode == DP_MODE_IGN) {
-            launch_pass1<3>(integer, dim3(blocks), s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
-            fix_mode = 3;
+        if (brute) {
+            hipLaunchKernelGGL(brute_k, dim3(plan.grid), dim3(plan.block), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
         } else {
-            if (integer && int_thr_ok)
-                launch_pass1<1>(integer, dim3(blocks), s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
-            else
-                launch_pass1<2>(integer, dim3(blocks), s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
-            fix_mode = 2;
+            // more than 64 KB of dynamic LDS has to be granted per function (once per device is enough, repeating it is cheap)
+            if (plan.family == kFamCell)
+                DP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tile_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+            // the lean and the fast kernel read the table the plan chose through the fields of the plain 8-entry one
+            PalDev pal1 = pal;
+            if (plan.table == kTabWarped) {
+                pal1.cell_tab = pal.warp_tab;
+                pal1.tab_words = pal.warp_words;
+                pal1.tab_total = pal.warp_total;
+            } else if (plan.table == kTabPlain4) {
+                pal1.cell_tab = pal.cell_tab4;
+                pal1.tab_words = pal.tab4_words;
+                pal1.tab_total = pal.tab4_words;
+            }
+            hipLaunchKernelGGL(tile_k, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, s, in_c, out_c, fl, g, pal1, thr, sx, sy, ign_scale,
+                               plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_family(family, g.aligned);
+        trace_family(family_name(plan.family), g.aligned);
         prof_mid(pm, s);
-        // one resident workgroup per CU (the 96 KB LDS list admits no more): a persistent grid avoids queueing
-        const uint32_t fgrid = std::min<uint32_t>((n_words + kBlock * 8 - 1) / (kBlock * 8), (uint32_t)num_cus());
-#define DP_FIX(M, C) hipLaunchKernelGGL((fixup_kernel<M, C>), dim3(fgrid), dim3(kBlock), 0, s, in_c, out_c, fl, n_words, g, pal, thr, sx, sy, ign_scale)
-        const bool big_q = pal.n_inner > kQueueSmall;
-        if (fix_mode == 0) {
-            if (big_q) DP_FIX(0, kQueueLarge); else DP_FIX(0, kQueueSmall);
-        } else if (fix_mode == 3) {
-            if (big_q) DP_FIX(3, kQueueLarge); else DP_FIX(3, kQueueSmall);
-        } else {
-            if (big_q) DP_FIX(2, kQueueLarge); else DP_FIX(2, kQueueSmall);
-        }
-#undef DP_FIX
+        hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);
         DP_HIP(hipGetLastError());
     }
