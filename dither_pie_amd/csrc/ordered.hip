@@ -2761,14 +2761,20 @@ int num_cus()
     return cached;
 }
 
-// experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel family of every launch on stderr (tests that must know
-// which kernel a case reached); the product library compiles to nothing here
-static inline void trace_family(const char *family, bool aligned)
+// experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel of every launch on stderr (tests that must know which
+// kernel a case reached): the family, then the template arguments and the table of the plan and the fix-up pass's queue; the
+// product library compiles to nothing here
+static inline void trace_plan(const OrderedPlan &p, bool aligned)
 {
 #ifdef DP_EXPERIMENTS
-    if (std::getenv("DP_ORDERED_TRACE")) fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d)\n", family, aligned ? 1 : 0);
+    if (std::getenv("DP_ORDERED_TRACE")) {
+        constexpr const char *tables[] = {"plain8", "plain4", "warped"};
+        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d\n",
+                family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
+                p.fix_big_queue ? 1 : 0);
+    }
 #else
-    (void)family;
+    (void)p;
     (void)aligned;
 #endif
 }
@@ -2939,7 +2945,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_family(family_name(plan.family), g.aligned);
+        trace_plan(plan, g.aligned);
         prof_mid(pm, s);
         hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);
