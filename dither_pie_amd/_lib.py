@@ -160,6 +160,20 @@ _SIGS_PATTERN = {
     "dp_pattern_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _vp]),
 }
 EXPORTS_PATTERN = tuple(_SIGS_PATTERN)
+# include/ditherpie_hip_png_file.h: CRC-32 on the device and finished IDAT / fdAT chunks packed back to back (what png.py's
+# assemble="device" and apng.py are built on), with their host statements; a table of its own for the same reason.
+_u32 = C.c_uint32
+_SIGS_PNG_FILE = {
+    "dp_png_crc32_workspace_bytes": (_sz, [_i, _i64]),
+    "dp_png_crc32_u8": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    "dp_png_crc32_host_u8": (_i, [_vp, _i64, _vp, _i, _vp]),
+    "dp_png_crc32_combine_host": (_u32, [_u32, _u32, _i64]),
+    "dp_png_file_bound_bytes": (_sz, [_i64, _i, _i]),
+    "dp_png_file_workspace_bytes": (_sz, [_i, _i64]),
+    "dp_png_file_assemble_u8": (_i, [_vp, _i64, _vp, _i, _i, _u32, _u32, _vp, _i64, _i, _vp, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "dp_png_file_assemble_host_u8": (_i, [_vp, _i64, _vp, _i, _i, _u32, _u32, _vp, _i64, _i, _vp, _i, _vp, _sz, _vp]),
+}
+EXPORTS_PNG_FILE = tuple(_SIGS_PNG_FILE)
 
 
 def build(force=False):
@@ -202,7 +216,8 @@ def load():
                                              f"{ABI_VERSION}: rebuild it with `make -C {CSRC}`")
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
-                                          + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())):
+                                          + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
+                                          + list(_SIGS_PNG_FILE.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

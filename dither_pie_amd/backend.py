@@ -1325,6 +1325,172 @@ def png_code_lengths_host(counts, max_len):
     return out[0] if one else out
 
 
+PNG_CRC_PIECE_BYTES = 64    # DP_PNG_CRC_PIECE_BYTES: what one lane of dp_png_crc32_u8 runs the register over
+PNG_CRC_SPAN_BYTES = 16384  # DP_PNG_CRC_SPAN_BYTES: what one workgroup covers in one step (256 pieces)
+PNG_FILE_MAX_PRE = 4096     # dp_png_file_assemble_u8: bytes in front of a frame's chunk
+PNG_FILE_MAX_POST = 64      # ... and behind it
+
+
+def _runs_host(data, sizes):
+    d = np.ascontiguousarray(data, dtype=np.uint8)
+    if d.ndim == 1:
+        d = d[None]
+    if d.ndim != 2:
+        raise ValueError("data must be [R, stride] (or [stride]) bytes")
+    z = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64).reshape(-1))
+    if z.shape[0] != d.shape[0]:
+        raise ValueError(f"{d.shape[0]} runs and {z.shape[0]} sizes")
+    return d, z
+
+
+def png_crc32(data, sizes):
+    """CRC-32 (zlib.crc32) of byte runs on the device (dp_png_crc32_u8): contiguous uint8 CUDA data [R, stride] (or [stride], one
+    run) and sizes [R] (a CUDA int64 tensor, or host integers) -> uint32 CUDA tensor [R]; run r is data[r, :sizes[r]].  A size
+    outside 0 ... stride is the caller's error (it is clamped).  Asynchronous on the current stream."""
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
+        raise TypeError("data must be a contiguous CUDA uint8 tensor")
+    d = data if data.dim() == 2 else data.unsqueeze(0)
+    if d.dim() != 2:
+        raise ValueError("data must be [R, stride] (or [stride]) bytes")
+    r, stride = d.shape
+    z = (sizes if isinstance(sizes, torch.Tensor) else torch.as_tensor(np.asarray(sizes, dtype=np.int64).reshape(-1))).to(d.device, torch.int64).contiguous()
+    if z.dim() != 1 or z.shape[0] != r:
+        raise ValueError(f"{r} runs and {tuple(z.shape)} sizes")
+    out = torch.empty(r, dtype=torch.uint32, device=d.device)
+    if r == 0:
+        return out
+    L = _lib.load()
+    with torch.cuda.device(d.device):
+        for a in range(0, r, PNG_MAX_FRAMES):
+            b = min(r, a + PNG_MAX_FRAMES)
+            need = int(L.dp_png_crc32_workspace_bytes(b - a, stride))
+            with _Launch(d.device, need) as ws:
+                check(L.dp_png_crc32_u8(d[a:b].data_ptr(), stride, z[a:b].data_ptr(), b - a, out[a:b].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+def png_crc32_host(data, sizes):
+    """The same from the host statement (dp_png_crc32_host_u8): array-like bytes [R, stride] (or [stride]) and sizes [R] -> numpy
+    uint32 [R]."""
+    d, z = _runs_host(data, sizes)
+    out = np.zeros(d.shape[0], np.uint32)
+    if d.shape[0]:
+        keep = d if d.size else np.zeros(1, np.uint8)                   # (an empty array has no address to pass)
+        check(_lib.load().dp_png_crc32_host_u8(_np_ptr(keep), d.shape[1], _np_ptr(z), d.shape[0], _np_ptr(out)))
+    return out
+
+
+def png_crc32_combine_host(crc_a, crc_b, len_b):
+    """The CRC-32 of A + B from the CRC-32 of A, of B, and the length of B (dp_png_crc32_combine_host)."""
+    if int(len_b) < 0:
+        raise ValueError("len_b must be >= 0")
+    return int(_lib.load().dp_png_crc32_combine_host(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
+
+
+def _file_args(n, pre, post, n_idat, seq0, seq_step):
+    """-> (pre as numpy [rows, pre_bytes] or None, per_frame, post as numpy or None, n_idat, seq0, seq_step)"""
+    per_frame = False
+    if pre is not None and not isinstance(pre, torch.Tensor):
+        pre = np.frombuffer(bytes(pre), np.uint8) if isinstance(pre, (bytes, bytearray, memoryview)) else np.ascontiguousarray(pre, dtype=np.uint8)
+    if pre is not None:
+        if pre.ndim == 2:
+            per_frame = True
+            if pre.shape[0] != n:
+                raise ValueError(f"{pre.shape[0]} prefixes for {n} frames")
+        elif pre.ndim != 1:
+            raise ValueError("pre must be bytes, [pre_bytes] or [N, pre_bytes]")
+        if pre.shape[-1] > PNG_FILE_MAX_PRE:
+            raise ValueError(f"a prefix holds at most {PNG_FILE_MAX_PRE} bytes, not {pre.shape[-1]}")
+        if pre.shape[-1] == 0:
+            pre, per_frame = None, False
+    if post is not None:
+        post = np.frombuffer(bytes(post), np.uint8)
+        if post.size > PNG_FILE_MAX_POST:
+            raise ValueError(f"a suffix holds at most {PNG_FILE_MAX_POST} bytes, not {post.size}")
+        if post.size == 0:
+            post = None
+    n_idat = n if n_idat is None else int(n_idat)
+    if not 0 <= n_idat <= n:
+        raise ValueError(f"n_idat must be in 0 ... {n}, not {n_idat}")
+    s0, st = int(seq0), int(seq_step)
+    if not (0 <= s0 < 2 ** 32 and 0 <= st < 2 ** 32):
+        raise ValueError("seq0 and seq_step must be in 0 ... 2^32 - 1")
+    return pre, per_frame, post, n_idat, s0, st
+
+
+def png_file_assemble(payload, sizes, pre=None, post=None, n_idat=None, seq0=0, seq_step=2):
+    """Finished PNG chunks from the encoder's output, on the device (dp_png_file_assemble_u8): payload [N, stride] uint8 and
+    sizes [N] int64 as png_deflate returns them -> (out uint8 [N * bound], offsets int64 [N + 1]), both on the device.  Frame f
+    is out[offsets[f]:offsets[f + 1]]: its prefix, ONE chunk -- IDAT for f < n_idat (default: all), else fdAT with the
+    sequence number seq0 + (f - n_idat) * seq_step -- with its CRC-32, the suffix; the frames are packed back to back and
+    out[offsets[N]:] is unspecified.  pre: bytes or [pre_bytes] (shared by all frames) or [N, pre_bytes] (one per frame), a
+    host array or a CUDA tensor, at most PNG_FILE_MAX_PRE bytes; post: bytes, at most PNG_FILE_MAX_POST.  At most
+    PNG_MAX_FRAMES frames per call.  Asynchronous on the current stream, like png_deflate: read offsets back, then copy
+    out[:offsets[-1]] once."""
+    if not (isinstance(payload, torch.Tensor) and payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 2 and payload.is_contiguous()):
+        raise TypeError("payload must be a contiguous CUDA uint8 tensor [N, stride]")
+    if not (isinstance(sizes, torch.Tensor) and sizes.device == payload.device and sizes.dtype == torch.int64 and sizes.dim() == 1
+            and sizes.shape[0] == payload.shape[0] and sizes.is_contiguous()):
+        raise TypeError("sizes must be a contiguous int64 tensor [N] on the payload's device")
+    n, stride = payload.shape
+    if n > PNG_MAX_FRAMES:
+        raise ValueError(f"at most {PNG_MAX_FRAMES} frames per call, not {n}: cut the batch")
+    pre, per_frame, post, n_idat, s0, st = _file_args(n, pre, post, n_idat, seq0, seq_step)
+    dev = payload.device
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), offsets
+    L = _lib.load()
+    pre_bytes, post_bytes = (0 if pre is None else int(pre.shape[-1])), (0 if post is None else int(post.size))
+    bound = int(L.dp_png_file_bound_bytes(stride, pre_bytes, post_bytes))
+    if bound == 0:
+        raise ValueError(f"a stride of {stride} bytes is more than a chunk takes (below 2^31 - 16)")
+    with torch.cuda.device(dev):
+        pre_t = None if pre is None else (pre if isinstance(pre, torch.Tensor) else torch.from_numpy(pre.copy())).to(dev, torch.uint8).contiguous()
+        post_t = None if post is None else torch.from_numpy(post.copy()).to(dev)
+        out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
+        need = int(L.dp_png_file_workspace_bytes(n, stride))
+        with _Launch(dev, need) as ws:
+            check(L.dp_png_file_assemble_u8(payload.data_ptr(), stride, sizes.data_ptr(), n, n_idat, s0, st,
+                                            None if pre_t is None else pre_t.data_ptr(), pre_bytes if per_frame else 0, pre_bytes,
+                                            None if post_t is None else post_t.data_ptr(), post_bytes, out.data_ptr(), out.numel(), offsets.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), _stream()))
+        for t in (pre_t, post_t):                                       # uploaded here, read by kernels that may not have run yet
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+    return out, offsets
+
+
+def png_file_assemble_host(streams, pre=None, post=None, n_idat=None, seq0=0, seq_step=2):
+    """The same bytes from the host statement (dp_png_file_assemble_host_u8), no device involved: [bytes per frame] (what
+    png_deflate_host returns) -> (bytes, [offsets]); frame f is bytes[offsets[f]:offsets[f + 1]]."""
+    streams = [bytes(s) for s in streams]
+    n = len(streams)
+    if n > PNG_MAX_FRAMES:
+        raise ValueError(f"at most {PNG_MAX_FRAMES} frames per call, not {n}: cut the batch")
+    if isinstance(pre, torch.Tensor):
+        pre = pre.detach().cpu().numpy()
+    pre, per_frame, post, n_idat, s0, st = _file_args(n, pre, post, n_idat, seq0, seq_step)
+    if n == 0:
+        return b"", [0]
+    stride = max(max(len(s) for s in streams), 1)
+    data = np.zeros((n, stride), np.uint8)
+    for f, s in enumerate(streams):
+        data[f, :len(s)] = np.frombuffer(s, np.uint8)
+    sizes = np.array([len(s) for s in streams], np.int64)
+    L = _lib.load()
+    pre_bytes, post_bytes = (0 if pre is None else int(pre.shape[-1])), (0 if post is None else int(post.size))
+    bound = int(L.dp_png_file_bound_bytes(stride, pre_bytes, post_bytes))
+    if bound == 0:
+        raise ValueError(f"a stream of {stride} bytes is more than a chunk takes (below 2^31 - 16)")
+    pre = None if pre is None else np.ascontiguousarray(pre)
+    out = np.empty(n * bound, np.uint8)
+    offsets = np.zeros(n + 1, np.int64)
+    check(L.dp_png_file_assemble_host_u8(_np_ptr(data), stride, _np_ptr(sizes), n, n_idat, s0, st, _np_ptr(pre), pre_bytes if per_frame else 0, pre_bytes,
+                                         _np_ptr(post), post_bytes, _np_ptr(out), out.size, _np_ptr(offsets)))
+    return out[:int(offsets[-1])].tobytes(), offsets.tolist()
+
+
 def profile_enable(on=True):
     check(_lib.load().dp_profile_enable(1 if on else 0))
 

@@ -2137,4 +2137,123 @@ inline void png_deflate_encode_dyn(const uint8_t *plane, const int h, const int 
     png_deflate_encode_blocks(plane, h, w, depth, seg_bytes, true, out);
 }
 
+// ---- PNG chunk CRCs and finished chunks (png_file.hip, include/ditherpie_hip_png_file.h) -----------------------------------
+// CRC-32/ISO-HDLC: reflected polynomial 0xEDB88320, register initialised to 0xFFFFFFFF, result inverted.  Everything is a
+// polynomial over GF(2) modulo P in the reflected representation: bit 31 of a word is the coefficient of x^0.
+//   register   crc32_update(state, bytes): the register after the bytes; crc = ~crc32_update(~0, bytes)
+//   pure       the register run from 0 with no inversion: pure(M) = M(x) x^32 mod P.  Linear, and blind to leading zeros:
+//              pure(A || B) = pure(A) x^(8 len B) + pure(B).  What the device computes per piece and joins.
+//   finish     crc(prefix || M) = ~(state(prefix) x^(8 len M) + pure(M)): the register after the prefix, shifted past M.
+// The device cuts a run into pieces of kCrcPieceBytes that END on the last 4-byte boundary of the run's addresses (the up
+// to three bytes behind it are fed bit by bit at the end); kCrcPieces of them are what one workgroup covers in one step
+// (kCrcSpanBytes).  The bytes in front of the run that the first piece and the first span lack count as zeros.
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+constexpr int kCrcPieceBytes = 64;                               // DP_PNG_CRC_PIECE_BYTES
+constexpr int kCrcPieces = 256;                                  // one lane each
+constexpr int kCrcSpanBytes = kCrcPieceBytes * kCrcPieces;       // DP_PNG_CRC_SPAN_BYTES
+constexpr int kPngFileMaxPre = 4096, kPngFileMaxPost = 64;
+constexpr int64_t kPngFileMaxStream = (1LL << 31) - 16;          // a stream bound must stay below it
+
+// a b mod P; x^0 is 0x80000000.  Always 32 rounds: the same instruction stream in every lane.
+DP_HD constexpr uint32_t crc_gfmul(const uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        p ^= (a & (0x80000000u >> i)) ? b : 0u;
+        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
+    }
+    return p;
+}
+
+DP_HD constexpr uint32_t crc_bits8(uint32_t c)   // eight rounds of the register: c x^8 mod P
+{
+    for (int i = 0; i < 8; ++i) c = (c >> 1) ^ ((c & 1u) ? kCrcPoly : 0u);
+    return c;
+}
+
+struct CrcTables {
+    uint32_t byte[4][256];        // slicing by four: byte[k][v] is the register after byte v and k zero bytes
+    uint32_t piece[kCrcPieces];   // x^(8 kCrcPieceBytes j): what lifts the piece j pieces before the span's last one
+    uint32_t x8[32];              // x^(8 2^k): the squares a shift by any byte count below 2^32 is put together from
+};
+
+constexpr CrcTables make_crc_tables()
+{
+    CrcTables t{};
+    for (uint32_t v = 0; v < 256; ++v) t.byte[0][v] = crc_bits8(v);
+    for (int k = 1; k < 4; ++k)
+        for (uint32_t v = 0; v < 256; ++v) t.byte[k][v] = (t.byte[k - 1][v] >> 8) ^ t.byte[0][t.byte[k - 1][v] & 255u];
+    t.x8[0] = 0x80000000u >> 8;
+    for (int k = 1; k < 32; ++k) t.x8[k] = crc_gfmul(t.x8[k - 1], t.x8[k - 1]);
+    uint32_t step = 0x80000000u;                                  // x^(8 kCrcPieceBytes)
+    for (int k = 0; k < 32; ++k)
+        if ((kCrcPieceBytes >> k) & 1) step = crc_gfmul(step, t.x8[k]);
+    t.piece[0] = 0x80000000u;
+    for (int j = 1; j < kCrcPieces; ++j) t.piece[j] = crc_gfmul(t.piece[j - 1], step);
+    return t;
+}
+constexpr CrcTables kCrcTables = make_crc_tables();
+static_assert(kCrcTables.byte[0][1] == 0x77073096u && kCrcTables.byte[0][255] == 0x2D02EF8Du, "the CRC-32 byte table");
+static_assert(kCrcTables.byte[1][1] == crc_bits8(kCrcTables.byte[0][1]), "slicing tables: one more zero byte each");
+static_assert(kCrcTables.piece[1] == kCrcTables.x8[6] && kCrcTables.piece[2] == kCrcTables.x8[7] && kCrcSpanBytes == 1 << 14, "64-byte pieces, 16 KiB spans");
+
+// c x^(8 n_bytes) mod P from a table of squares x8 (host: kCrcTables.x8)
+DP_HD inline uint32_t crc_shift_bytes(uint32_t c, uint64_t n_bytes, const uint32_t *x8)
+{
+    for (int k = 0; n_bytes && k < 32; ++k, n_bytes >>= 1)
+        if (n_bytes & 1u) c = crc_gfmul(c, x8[k]);
+    return c;
+}
+
+inline uint32_t crc32_update(uint32_t state, const uint8_t *p, const size_t n)
+{
+    for (size_t i = 0; i < n; ++i) state = (state >> 8) ^ kCrcTables.byte[0][(state ^ p[i]) & 255u];
+    return state;
+}
+inline uint32_t crc32_bytes(const uint8_t *p, const size_t n) { return ~crc32_update(0xFFFFFFFFu, p, n); }
+// the CRC of A || B from the CRCs of A and B: the initial value and the inversion cancel
+inline uint32_t crc32_combine(const uint32_t crc_a, const uint32_t crc_b, const uint64_t len_b) { return crc_shift_bytes(crc_a, len_b, kCrcTables.x8) ^ crc_b; }
+
+// Finished chunks.  Frame f of a call: pre_bytes bytes of the caller's, one chunk -- IDAT for f < n_idat, else fdAT with the
+// sequence number seq0 + (f - n_idat) seq_step in front of the stream --, post_bytes bytes of the caller's.
+DP_HD inline int64_t png_file_clamp(const int64_t size, const int64_t stride) { return size < 0 ? 0 : size > stride ? stride : size; }
+DP_HD inline uint32_t png_file_type(const bool fdat) { return fdat ? 0x66644154u : 0x49444154u; }   // big-endian "fdAT", "IDAT"
+inline bool png_file_geometry_ok(const int64_t stream_stride, const int pre_bytes, const int post_bytes)
+{
+    return stream_stride >= 0 && stream_stride < kPngFileMaxStream && pre_bytes >= 0 && pre_bytes <= kPngFileMaxPre && post_bytes >= 0 && post_bytes <= kPngFileMaxPost;
+}
+inline uint64_t png_file_bound(const int64_t stream_stride, const int pre_bytes, const int post_bytes) { return (uint64_t)pre_bytes + 16u + (uint64_t)stream_stride + (uint64_t)post_bytes; }
+inline void png_file_be32(uint8_t *p, const uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
+
+// -> the bytes written; offsets[0 ... n_frames] are filled.  `out` holds n_frames * png_file_bound(...) bytes.
+inline int64_t png_file_assemble(const uint8_t *streams, const int64_t stream_stride, const int64_t *sizes, const int n_frames, const int n_idat,
+                                 const uint32_t seq0, const uint32_t seq_step, const uint8_t *pre, const int64_t pre_stride, const int pre_bytes,
+                                 const uint8_t *post, const int post_bytes, uint8_t *out, int64_t *offsets)
+{
+    int64_t at = 0;
+    offsets[0] = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t n = png_file_clamp(sizes[f], stream_stride);
+        const bool fdat = f >= n_idat;
+        if (pre_bytes) std::memcpy(out + at, pre + (size_t)f * (size_t)pre_stride, (size_t)pre_bytes);
+        at += pre_bytes;
+        uint8_t *head = out + at;
+        png_file_be32(head, (uint32_t)n + (fdat ? 4u : 0u));
+        png_file_be32(head + 4, png_file_type(fdat));
+        int hdr = 8;
+        if (fdat) {
+            png_file_be32(head + 8, seq0 + (uint32_t)(f - n_idat) * seq_step);
+            hdr = 12;
+        }
+        if (n) std::memcpy(head + hdr, streams + (size_t)f * (size_t)stream_stride, (size_t)n);
+        const uint32_t crc = ~crc32_update(crc32_update(0xFFFFFFFFu, head + 4, (size_t)hdr - 4), head + hdr, (size_t)n);
+        png_file_be32(head + hdr + n, crc);
+        at += hdr + n + 4;
+        if (post_bytes) std::memcpy(out + at, post, (size_t)post_bytes);
+        at += post_bytes;
+        offsets[f + 1] = at;
+    }
+    return at;
+}
+
 }  // namespace dp

@@ -25,6 +25,9 @@
 //   host_xxx pngdeflate <cases.bin> <n>   the host statement of the PNG-8 image data (png_deflate_encode): n records of
 //                                     int32 frames, h, w, depth, seg_bytes and frames * h * w index bytes; every frame prints
 //                                     its size and its zlib stream in hex (inflated and compared by the test)
+//   host_xxx pngfile <cases.bin> <n>   the host statements of the finished chunks and their CRCs (png_file_assemble, crc32_bytes,
+//                                      crc32_combine): n records of 8 int32 (frames, stride, n_idat, seq0, seq_step, pre_bytes,
+//                                      per-frame prefixes 0 / 1, post_bytes), the int64 sizes, the streams, the prefixes, the suffix
 //   host_xxx pngdyn <cases.bin> <n>   the same with dynamic-Huffman blocks as a third candidate (png_deflate_encode_dyn)
 //   host_xxx orderedplan <cases.bin> <n>   the kernel choice of the ordered dither (ordered_plan.h: plan_ordered): n records of
 //                                     one OrderedFacts and one OrderedSwitches (int32 fields in declaration order); prints one
@@ -556,6 +559,52 @@ static int run_pngdeflate(const char *path, const int n_cases, const bool dynami
     return 0;
 }
 
+// ---- finished PNG chunks and their CRCs --------------------------------------------------------------------------
+static int run_pngfile(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[8];   // frames, stride, n_idat, seq0, seq_step, pre_bytes, per-frame prefixes, post_bytes
+        if (fread(head, sizeof(int32_t), 8, f) != 8 || head[0] < 0 || head[0] > 4096 || head[2] < 0 || head[2] > head[0] ||
+            !png_file_geometry_ok(head[1], head[5], head[7])) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const size_t n = (size_t)head[0], stride = (size_t)head[1], pre_rows = head[6] ? n : 1;
+        // exactly as many bytes as the statement may touch: anything past them is a sanitizer report
+        std::vector<int64_t> sizes(n), offsets(n + 1, -1);
+        std::vector<uint8_t> streams(n * stride), pre(pre_rows * (size_t)head[5]), post((size_t)head[7]);
+        std::vector<uint8_t> out(n * (size_t)png_file_bound(head[1], head[5], head[7]));
+        if (fread(sizes.data(), sizeof(int64_t), n, f) != n || fread(streams.data(), 1, streams.size(), f) != streams.size() ||
+            fread(pre.data(), 1, pre.size(), f) != pre.size() || fread(post.data(), 1, post.size(), f) != post.size()) {
+            fprintf(stderr, "short record %d in %s\n", c, path);
+            return 2;
+        }
+        const int64_t total = png_file_assemble(streams.data(), head[1], sizes.data(), head[0], head[2], (uint32_t)head[3], (uint32_t)head[4], pre.data(),
+                                                head[6] ? head[5] : 0, head[5], post.data(), head[7], out.data(), offsets.data());
+        if (total < 0 || (size_t)total > out.size() || offsets[n] != total) {
+            printf("case %d: %lld bytes against a bound of %zu\n", c, (long long)total, out.size());
+            return 1;
+        }
+        printf("file %d %lld ", c, (long long)total);
+        for (int64_t i = 0; i < total; ++i) printf("%02x", out[(size_t)i]);
+        printf("\n");
+        uint32_t joined = crc32_bytes(nullptr, 0);
+        for (size_t r = 0; r < n; ++r) {
+            const size_t len = (size_t)png_file_clamp(sizes[r], head[1]);
+            const uint32_t one = crc32_bytes(streams.data() + r * stride, len);
+            joined = crc32_combine(joined, one, len);
+            printf("crc %d %zu %08x %08x\n", c, r, one, joined);   // the run's own, and that of all runs so far back to back
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
 // ---- ordered dither: which kernel serves a call ------------------------------------------------------------------
 static int run_orderedplan(const char *path, const int n_cases)
 {
@@ -584,7 +633,7 @@ static int run_orderedplan(const char *path, const int n_cases)
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn <cases.bin> <n>  |  orderedplan <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -592,6 +641,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "giflzw") return run_giflzw(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "pngdeflate") return run_pngdeflate(argv[2], atoi(argv[3]), false);
     if (std::string(argv[1]) == "pngdyn") return run_pngdeflate(argv[2], atoi(argv[3]), true);
+    if (std::string(argv[1]) == "pngfile") return run_pngfile(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "orderedplan") return run_orderedplan(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;

@@ -1299,11 +1299,12 @@ class ImageDitherer:
         out.putpalette(colours.reshape(-1).tolist(), "RGB")
         return out
 
-    def apply_dithering_png(self, image, seg_bytes=None, blocks="fixed") -> bytes:
+    def apply_dithering_png(self, image, seg_bytes=None, blocks="fixed", assemble="host") -> bytes:
         """PIL image -> the bytes of a PNG-8 file whose decoding equals apply_dithering(image), exactly.  Host-in as
         apply_dithering_indexed; the index plane never comes back: it is compressed where it lies (png.encode_png: the
         zlib stream on the device, the container and its CRCs in Python) and only the compressed stream crosses to the
-        host.  ValueError above 256 colours."""
+        host.  assemble="device": the container and its CRCs on the device as well (png.encode_png).  ValueError above
+        256 colours."""
         from . import png
         rgb = image if image.mode == "RGB" else image.convert("RGB")
         w, h = rgb.size
@@ -1321,7 +1322,7 @@ class ImageDitherer:
             np.copyto(host_in.numpy(), np.frombuffer(rgb.tobytes(), dtype=np.uint8))
             dev_in = host_in.view(h, w, 3).cuda(non_blocking=True)
         planes, colours = self.apply_dithering_frames_indexed(dev_in)
-        return png.encode_png(planes, colours, seg_bytes, blocks=blocks)[0]
+        return png.encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)[0]
 
     def prepare(self, device=None, accel=True):
         """Create the device-side palette now (and, with accel=True, its search accelerator: ~3.5 ms once) instead of on

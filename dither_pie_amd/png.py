@@ -14,6 +14,10 @@ Chunk CRCs are zlib.crc32 on the host, over the compressed bytes: a fraction of 
 times it beside the kernels).  One size read-back and one block copy per call, as gif.GifWriter does.
 encoder="host" runs the normative host statement (backend.png_deflate_host) on host arrays: the same bytes without a GPU.
 blocks="dynamic" (default "fixed") lets the encoder write dynamic-Huffman blocks as well: the same pixels in fewer bytes.
+assemble="device" (default "host") builds the files on the GPU as well (backend.png_file_assemble): the chunk CRCs are
+computed there, the finished files are packed back to back and come over in one copy of exactly their size.  Each stream
+is then ONE IDAT chunk (a chunk may hold 2^31 - 1 bytes), so a file whose stream is longer than IDAT_BYTES differs from the
+host-assembled one in its chunking: it equals container(..., idat_bytes=2**31 - 1) of the same stream, byte for byte.
 """
 from __future__ import annotations
 
@@ -57,19 +61,23 @@ def container(width, height, depth, palette, stream, idat_bytes=IDAT_BYTES):
     return b"".join(parts)
 
 
+def _device_planes(planes):
+    import torch
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda):
+        raise ValueError("planes must be a CUDA tensor (encoder='host' takes host arrays)")
+    if planes.dtype != torch.uint8:
+        raise ValueError(f"planes must be one-byte indices (torch.uint8), not {planes.dtype}: a PNG palette holds 256 colours")
+    if planes.dim() not in (2, 3):
+        raise ValueError("planes must be [N,H,W] or [H,W]")
+    return planes if planes.dim() == 3 else planes.unsqueeze(0)
+
+
 def _streams(planes, depth, seg_bytes, encoder, blocks):
     from . import backend
     if blocks not in backend.PNG_BLOCKS:
         raise ValueError(f"blocks must be one of {backend.PNG_BLOCKS}, not {blocks!r}")
     if encoder == "device":
-        import torch
-        if not (isinstance(planes, torch.Tensor) and planes.is_cuda):
-            raise ValueError("planes must be a CUDA tensor (encoder='host' takes host arrays)")
-        if planes.dtype != torch.uint8:
-            raise ValueError(f"planes must be one-byte indices (torch.uint8), not {planes.dtype}: a PNG palette holds 256 colours")
-        if planes.dim() not in (2, 3):
-            raise ValueError("planes must be [N,H,W] or [H,W]")
-        p = planes if planes.dim() == 3 else planes.unsqueeze(0)
+        p = _device_planes(planes)
         if p.shape[0] == 0:
             return [], p.shape
         payload, sizes = backend.png_deflate(p, depth, seg_bytes, blocks)
@@ -91,22 +99,54 @@ def _streams(planes, depth, seg_bytes, encoder, blocks):
     return backend.png_deflate_host(p, depth, seg_bytes, blocks), p.shape
 
 
-def encode_png(planes, palette, seg_bytes=None, encoder="device", blocks="fixed"):
+ASSEMBLE = ("host", "device")
+
+
+def _check_assemble(assemble, encoder):
+    if assemble not in ASSEMBLE:
+        raise ValueError(f"assemble must be one of {ASSEMBLE}, not {assemble!r}")
+    if assemble == "device" and encoder != "device":
+        raise ValueError("assemble='device' builds the files on the GPU: it needs encoder='device'")
+
+
+def _files_on_device(planes, pal, depth, seg_bytes, blocks):
+    """The files of encode_png, assembled on the GPU: prefix = signature, IHDR, PLTE; one IDAT chunk; suffix = IEND."""
+    from . import backend
+    if blocks not in backend.PNG_BLOCKS:
+        raise ValueError(f"blocks must be one of {backend.PNG_BLOCKS}, not {blocks!r}")
+    p = _device_planes(planes)
+    head = container(p.shape[2], p.shape[1], depth, pal, b"")          # (checks the geometry as the host path does)
+    pre = head[:len(head) - 24]                                        # without the empty IDAT (12 bytes) and IEND (12)
+    files = []
+    for a in range(0, p.shape[0], backend.PNG_MAX_FRAMES):
+        payload, sizes = backend.png_deflate(p[a:a + backend.PNG_MAX_FRAMES], depth, seg_bytes, blocks)
+        out, offsets = backend.png_file_assemble(payload, sizes, pre=pre, post=chunk(b"IEND", b""))
+        offsets = offsets.cpu().tolist()
+        block = out[:offsets[-1]].cpu().numpy()                       # exactly the files' bytes, one copy
+        files += [block[offsets[f]:offsets[f + 1]].tobytes() for f in range(len(offsets) - 1)]
+    return files
+
+
+def encode_png(planes, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
     """Index planes [N,H,W] (or [H,W]) and their palette [K,3] -> [the bytes of a PNG file per plane].  ValueError: more than
     256 colours, planes that are not one-byte indices, planes that are not on the GPU for the device encoder (or are, for
     the host encoder), a `blocks` outside backend.PNG_BLOCKS.  An index >= K is the caller's error (a decoder will show
     whatever entry its low bits name, or refuse the file).  blocks="dynamic" adds dynamic-Huffman blocks: smaller files that
-    decode to the same pixels (include/ditherpie_hip_png_dyn.h)."""
+    decode to the same pixels (include/ditherpie_hip_png_dyn.h).  assemble="device": chunk CRCs and the files themselves on
+    the GPU (include/ditherpie_hip_png_file.h), one IDAT chunk per file; refused with encoder="host"."""
     from . import backend
+    _check_assemble(assemble, encoder)
     pal = _palette(palette)
     depth = backend.png_depth(pal.shape[0])
+    if assemble == "device":
+        return _files_on_device(planes, pal, depth, seg_bytes, blocks)
     streams, shape = _streams(planes, depth, seg_bytes, encoder, blocks)
     return [container(shape[2], shape[1], depth, pal, s) for s in streams]
 
 
-def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fixed"):
+def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
     """One plane [H,W] (or [1,H,W]) as a PNG file -> the number of bytes written."""
-    files = encode_png(plane, palette, seg_bytes, encoder, blocks)
+    files = encode_png(plane, palette, seg_bytes, encoder, blocks, assemble)
     if len(files) != 1:
         raise ValueError(f"write_png takes one plane, not {len(files)}: write_png_sequence writes several")
     with open(path, "wb") as f:
@@ -114,11 +154,11 @@ def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fi
     return len(files[0])
 
 
-def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device", blocks="fixed"):
+def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
     """Planes [N,H,W] as the files pattern % start, pattern % (start + 1), ... (the 'frame_%05d.png' of a frame
     directory) -> the list of paths written."""
     paths = []
-    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder, blocks)):
+    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder, blocks, assemble)):
         path = str(pattern) % (int(start) + k)
         with open(path, "wb") as f:
             f.write(data)

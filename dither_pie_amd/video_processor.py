@@ -129,13 +129,15 @@ def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Opt
 
 
 def process_frames_png(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
-                       final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None, blocks: str = "fixed"):
+                       final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None, blocks: str = "fixed",
+                       assemble: str = "host"):
     """process_frames() as PNG-8 files: uint8 CUDA tensor [N,H,W,3] -> [bytes of one PNG file per frame]; decoding file i
     gives process_frames(...)[i], exactly.  process_frames_indexed, then png.encode_png: the planes are compressed on the
-    device and only the compressed streams come back.  ValueError above 256 colours."""
+    device and only the compressed streams come back (assemble="device": the finished files, png.encode_png).  ValueError above
+    256 colours."""
     from . import png
     planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier)
-    return png.encode_png(planes, colours, seg_bytes, blocks=blocks)
+    return png.encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)
 
 
 def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_method: Optional[str] = None,
@@ -738,14 +740,78 @@ class VideoProcessor:
         self._report_progress(1.0, "GIF complete!")
         return made["writer"].n_frames
 
+    def process_video_apng(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
+                           delta=True, max_frames=None, seg_bytes=None, blocks="fixed") -> int:
+        """The video as an animated PNG of palette indices (apng.ApngWriter): decode -> GPU -> file, no encoder pipe and no
+        RGB frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as
+        process_video_gif is.  Per batch: process_frames_indexed, the inter-frame delta, the zlib streams, the chunk CRCs and
+        the finished fcTL + IDAT / fdAT chunks on the device, one copy of exactly those bytes to the host, one write.
+        Decoding frame i of the file gives process_frames of frame i, exactly; the file plays at apng.delay(fps), which is
+        exact for every rate a fraction of two 16-bit numbers expresses (30000/1001 among them).
+        One palette: an APNG has a single PLTE, so there is no scene_palettes argument, and a ditherer that fits its palette
+        per frame is refused at the first frame whose colours differ from the file's.  A palette fitted to the whole clip
+        (scan_palette) is the natural companion.
+        One device: the first of `devices`; a list of several is refused.  Failure policy as process_video_gif: a batch that
+        fails RAISES, and so does a device failure, a malformed stream or a decoder that exits with an error; the partial
+        file is left as it is.
+        -> the number of frames written.  ValueError before the decoder starts: several devices, a ditherer of more than 256
+        colours where that is known up front, max_frames < 1, seg_bytes outside 256 ... 32768, a `blocks` that does not
+        exist."""
+        from .apng import APNG_MAX_COLOURS, ApngWriter
+        if self.devices is not None and len(list(self.devices)) > 1:
+            raise ValueError(f"process_video_apng runs on one device, not on {len(list(self.devices))}: an APNG's frames are "
+                             "written in order by one writer; pass devices=[one]")
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        if seg_bytes is not None and not 256 <= int(seg_bytes) <= 32768:
+            raise ValueError("seg_bytes must be in 256 ... 32768")
+        if blocks not in ("fixed", "dynamic"):
+            raise ValueError(f"blocks must be 'fixed' or 'dynamic', not {blocks!r}")
+        if getattr(ditherer, "palette", None) is not None and len(ditherer.palette) > APNG_MAX_COLOURS:
+            raise ValueError(f"the ditherer has {len(ditherer.palette)} colours: a PNG palette holds {APNG_MAX_COLOURS}")
+        info = self.get_video_info(input_path)
+        fps = info.get("fps") or 25.0
+        made = {}
+
+        class _BatchFailed(BaseException):   # past _batch_with_retries' `except Exception`: no frame-by-frame retry here
+            def __init__(self, error):
+                super().__init__(str(error))
+                self.error = error
+
+        def setup(dev, gpu_stream, h, w, stats):
+            oh, ow = output_size(h, w, pixelize_method, max_size, final_resize_multiplier)
+            writer = made["writer"] = ApngWriter(made["file"], ow, oh, fps, 0, delta, seg_bytes, "device", blocks)
+
+            def feed(x, first):
+                try:
+                    planes, colours = process_frames_indexed(x, ditherer, pixelize_method, max_size, final_resize_multiplier)
+                    writer.add(planes, colours)
+                except Exception as e:  # noqa: BLE001
+                    raise _BatchFailed(e) from e
+            return feed
+
+        with open(output_path, "w+b") as f:
+            made["file"] = f
+            try:
+                self._scan_decoded(input_path, max_frames, setup, "APNG encode", "APNG", indexed=True)
+            except _BatchFailed as e:
+                raise e.error
+            finally:
+                if "writer" in made:
+                    made["writer"].close()
+        self.last_apng_stats = dict(self.last_scan_stats, mode="apng", bytes=os.path.getsize(output_path))
+        self._report_progress(1.0, "APNG complete!")
+        return made["writer"].n_frames
+
     def process_video_pngs(self, input_path, out_pattern, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1, blocks="fixed") -> int:
+                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1, blocks="fixed", assemble="host") -> int:
         """The video as a sequence of PNG-8 files out_pattern % start, out_pattern % (start + 1), ... (the 'frame_%05d.png'
         of a frame directory): decode -> GPU -> files, no encoder pipe and no RGB frames on the way out.  Built on the
         decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as process_video_gif is.  Per batch:
         process_frames_indexed -- piece by piece with each scene's palette when scene_palettes (the list scan_scenes
         returns) is given --, the zlib streams on the device, one copy of the compressed bytes to the host, the containers
-        in Python.  Decoding file i gives process_frames of frame i (with its scene's palette), exactly.
+        in Python (assemble="device": the containers and their CRCs on the device too, png.encode_png).  Decoding file i
+        gives process_frames of frame i (with its scene's palette), exactly.
         One device: the first of `devices`; a list of several is refused.  Failure policy as process_video_gif: a batch that
         fails RAISES, and so does a device failure, a malformed stream or a decoder that exits with an error; the files
         written so far are left as they are.
@@ -763,6 +829,8 @@ class VideoProcessor:
             raise ValueError("seg_bytes must be in 256 ... 32768")
         if blocks not in ("fixed", "dynamic"):
             raise ValueError(f"blocks must be 'fixed' or 'dynamic', not {blocks!r}")
+        if assemble not in ("host", "device"):
+            raise ValueError(f"assemble must be 'host' or 'device', not {assemble!r}")
         try:
             if str(out_pattern) % 1 == str(out_pattern) % 2:
                 raise TypeError("no field")
@@ -799,7 +867,7 @@ class VideoProcessor:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
                         planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
-                        for k, data in enumerate(encode_png(planes, colours, seg_bytes, blocks=blocks)):
+                        for k, data in enumerate(encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)):
                             with open(str(out_pattern) % (int(start) + first + a + k), "wb") as f:
                                 f.write(data)
                             made["written"] += 1

@@ -1,8 +1,9 @@
 """Times and file sizes of the PNG-8 output (HIP events for the device part, perf_counter for whole calls; warm clocks,
 median [p10-p90]).
 
-  python tools/bench_scripts/png_encode.py [--repeats 20] [--segs 2048,8192,32768] [--batch 64] [--skip-4k] [--blocks fixed|dynamic|both]
+  python tools/bench_scripts/png_encode.py [--repeats 20] [--segs 2048,8192,32768] [--batch 64] [--skip-4k] [--blocks fixed|dynamic|both] [--assemble host|both]
   python tools/bench_scripts/png_encode.py --sizes-only      (no GPU: stream sizes of the host statement against zlib)
+  python tools/bench_scripts/png_encode.py --assemble both   (host-assembled against device-assembled files, and nothing else)
 
   * dp_png_deflate_encode_u8 alone (HIP events) on photo-like and noise planes of 16 and 256 colours at 1080p and 4K, one
     frame and a batch of --batch frames, at every seg_bytes of --segs; beside it a device copy of the plane bytes;
@@ -15,6 +16,12 @@ median [p10-p90]).
     1 restricted to fixed codes (Z_FIXED) beside it, on the 512 x 768 photo-like planes of tests/png_ref.py.
   * --blocks: the block types the encoder may write beside stored ones ("fixed", the default; "dynamic"; "both" times the two
     A then B then A ... in the same process and reports each, with the workspace either needs).
+  * --assemble both: png.encode_png(assemble="host") and png.encode_png(assemble="device") of the same planes, taking turns
+    inside every repeat in ONE process, each timed with HIP events (what the stream was busy or waited for) and by the wall
+    clock (what the caller waits for), median [p10-p90]; the files are compared byte for byte first.  Beside them
+    dp_png_file_assemble_u8 alone (HIP events: the CRC, layout and copy kernels) and the copy of the finished bytes to the
+    host.  The host path is the code this option was added beside, unchanged: it is the yardstick.  Only this comparison
+    runs.
 Run from the root of the tree; prints one JSON line per figure."""
 import argparse
 import io
@@ -89,6 +96,62 @@ def time_wall(fn, repeats, warmup=2):
     return out
 
 
+def time_both_interleaved(fns, repeats, warmup=2):
+    """([HIP-event ms], [wall ms]) per function, the functions taking turns inside every repeat."""
+    import torch
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    ev, wall = [[] for _ in fns], [[] for _ in fns]
+    for _ in range(repeats):
+        for i, fn in enumerate(fns):
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            wall[i].append(1e3 * (time.perf_counter() - t0))
+            ev[i].append(a.elapsed_time(b))
+    return ev, wall
+
+
+def assemble_both(a, geometries, modes):
+    import torch
+    from dither_pie_amd import backend, png
+    for h, w in geometries:
+        for k in (16, 256):
+            d = backend.png_depth(k)
+            palette = np.random.RandomState(4).randint(0, 256, (k, 3)).astype(np.uint8)
+            for kind in ("photo", "noise"):
+                for n in (1, a.batch if (h, w) == (1080, 1920) else max(1, a.batch // 4)):
+                    dev = torch.from_numpy(planes_of(kind, k, n, h, w)).cuda()
+                    for blocks in modes:
+                        tag = dict(h=h, w=w, k=k, kind=kind, frames=n, blocks=blocks)
+                        host_files = png.encode_png(dev, palette, blocks=blocks)
+                        dev_files = png.encode_png(dev, palette, blocks=blocks, assemble="device")
+                        payload, sizes = backend.png_deflate(dev, d, blocks=blocks)
+                        s = sizes.cpu().tolist()
+                        pay = payload.cpu().numpy()
+                        one_chunk = [png.container(w, h, d, palette, pay[f, :m].tobytes(), idat_bytes=2 ** 31 - 1) for f, m in enumerate(s)]
+                        emit("files", same_as_one_idat_container=dev_files == one_chunk, same_as_host_assembled=dev_files == host_files,
+                             bytes=sum(len(f) for f in dev_files), **tag)
+                        ev, wall = time_both_interleaved([lambda: png.encode_png(dev, palette, blocks=blocks),
+                                                          lambda: png.encode_png(dev, palette, blocks=blocks, assemble="device")], a.repeats)
+                        for i, name in enumerate(("host", "device")):
+                            emit("encode_png, HIP events", ev[i], assemble=name, **tag)
+                            emit("encode_png, wall clock", wall[i], assemble=name, **tag)
+                        head = png.container(w, h, d, palette, b"")
+                        made = {}
+                        def assemble():
+                            made["out"] = backend.png_file_assemble(payload, sizes, pre=head[:-24], post=head[-12:])
+                        emit("  dp_png_file_assemble_u8 alone (with its prefix upload)", time_gpu(assemble, a.repeats), **tag)
+                        out, offsets = made["out"]
+                        emit("  offsets and finished bytes to the host", time_wall(lambda: out[:int(offsets[-1].item())].cpu(), a.repeats), **tag)
+                        del host_files, dev_files, one_chunk, pay
+
+
 def zfixed1(data):
     co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
     return co.compress(data) + co.flush()
@@ -127,6 +190,7 @@ def main():
     ap.add_argument("--skip-4k", action="store_true")
     ap.add_argument("--sizes-only", action="store_true")
     ap.add_argument("--blocks", choices=("fixed", "dynamic", "both"), default="fixed")
+    ap.add_argument("--assemble", choices=("host", "both"), default="host")
     a = ap.parse_args()
     segs = [int(s) for s in a.segs.split(",")]
     modes = ["fixed", "dynamic"] if a.blocks == "both" else [a.blocks]
@@ -141,6 +205,8 @@ def main():
     ws_of = {"fixed": L.dp_png_deflate_workspace_bytes, "dynamic": L.dp_png_deflate_dyn_workspace_bytes}
     emit("device", name=torch.cuda.get_device_name(0), default_seg_bytes=backend.PNG_SEG_BYTES)
     geometries = [(1080, 1920)] + ([] if a.skip_4k else [(2160, 3840)])
+    if a.assemble == "both":
+        return assemble_both(a, geometries, modes)
     for h, w in geometries:
         for k in (16, 256):
             d = backend.png_depth(k)
