@@ -174,6 +174,13 @@ _SIGS_PNG_FILE = {
     "dp_png_file_assemble_host_u8": (_i, [_vp, _i64, _vp, _i, _i, _u32, _u32, _vp, _i64, _i, _vp, _i, _vp, _sz, _vp]),
 }
 EXPORTS_PNG_FILE = tuple(_SIGS_PNG_FILE)
+# include/ditherpie_hip_dotdiff.h: dot diffusion (error diffusion in class-matrix order, tiled); a table of its own for the
+# same reason.
+_SIGS_DOTDIFF = {
+    "dp_dotdiff_reach": (_i, [_vp, _i]),
+    "dp_dotdiff_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _vp]),
+}
+EXPORTS_DOTDIFF = tuple(_SIGS_DOTDIFF)
 
 
 def build(force=False):
@@ -217,7 +224,7 @@ def load():
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
-                                          + list(_SIGS_PNG_FILE.items())):
+                                          + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

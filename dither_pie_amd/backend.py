@@ -354,6 +354,62 @@ def pattern(frames, pal: Palette, matrix, strength256, y0=0, x0=0, out=None):
     return out.view(frames.shape)
 
 
+DOTDIFF_SIZES = (2, 4, 8, 16)   # class matrices of dp_dotdiff_u8 are m x m
+DOTDIFF_MAX_REACH = 16          # DP_DOTDIFF_MAX_REACH: the halo of a tile of the kernel
+DOTDIFF_TILE = 64               # the tile edge of the kernel (dotdiff.hip: kDotTile); tests build their multi-tile shapes on it
+
+
+def _dotdiff_classes(classes):
+    """An m x m class matrix -> its m * m bytes, row-major; ValueError unless it is a permutation of 0 .. m*m-1."""
+    try:
+        a = np.asarray(classes)
+    except Exception:
+        raise ValueError("dot diffusion: the class matrix must be an m x m array of integers") from None
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] not in DOTDIFF_SIZES or a.dtype.kind not in "iu":
+        raise ValueError(f"dot diffusion: the class matrix must be m x m integers with m in {DOTDIFF_SIZES}, "
+                         f"not {a.dtype} {a.shape}")
+    if sorted(a.reshape(-1).tolist()) != list(range(a.size)):
+        raise ValueError(f"dot diffusion: the class matrix must be a permutation of 0 .. {a.size - 1}")
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def dotdiff_reach(classes):
+    """The reach of a class matrix (dp_dotdiff_reach; include/ditherpie_hip_dotdiff.h): the longest path of king moves
+    through the tiled matrix along which the class strictly increases.  Host code: no device is needed."""
+    c = _dotdiff_classes(classes)
+    r = int(_lib.load().dp_dotdiff_reach(_np_ptr(c), int(c.shape[0])))
+    if r < 0:
+        raise ValueError("dot diffusion: the library refused the class matrix")
+    return r
+
+
+def dotdiff(frames, pal: Palette, classes, strength256, out=None):
+    """Dot diffusion (include/ditherpie_hip_dotdiff.h) of uint8 frames already in HBM -> uint8 frames: error diffusion in the
+    order of the tiled class matrix `classes` (m x m, m in 2, 4, 8, 16, a permutation, reach at most 16), exact per tile with
+    no scan.  The nearest search is the palette's 2^24-entry table, shared with pattern() (built at the first call of either
+    with the palette; Palette.pattern_prepare() builds it ahead).  strength256 0 .. 256; at most 256 colours; `out` must not be
+    the frames themselves."""
+    c = _dotdiff_classes(classes)
+    if not (isinstance(strength256, (int, np.integer)) and 0 <= strength256 <= 256):
+        raise ValueError(f"dot diffusion strength256 must be an integer in 0 .. 256, not {strength256!r}")
+    if pal.K > 256:
+        raise ValueError(f"dot diffusion supports at most 256 colours, the palette has {pal.K}")
+    reach = dotdiff_reach(c)
+    if reach > DOTDIFF_MAX_REACH:
+        raise ValueError(f"dot diffusion: the class matrix has reach {reach}, at most {DOTDIFF_MAX_REACH} is supported")
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    if n and out.data_ptr() == f.data_ptr():
+        raise ValueError("dot diffusion does not work in place: out must not be the frames")
+    _check_palette_device(pal, f)
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):   # (no workspace: the lock of the (device, stream) only)
+        check(L.dp_dotdiff_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, _np_ptr(c), int(c.shape[0]), int(strength256),
+                              _stream()))
+    return out.view(frames.shape)
+
+
 class HalftoneParams(C.Structure):
     """struct dp_halftone_params (include/ditherpie_hip.h)."""
     _fields_ = [("cell_size", C.c_double), ("cos_a", C.c_double), ("sin_a", C.c_double), ("exponent", C.c_double),

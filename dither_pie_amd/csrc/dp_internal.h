@@ -268,6 +268,10 @@ int64_t wavelet_uniforms_needed(int h, int w, int wid);
 size_t wavelet_ws_bytes(int64_t n_frames, int h, int w, int wid);
 int launch_wavelet(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PalDev &pal,
                    const dp_wavelet_params &P, void *ws, size_t ws_bytes, hipStream_t s);
+// the palette's 2^24-entry nearest table (pattern.hip), shared by pattern dithering and dot diffusion (dotdiff.hip)
+int pattern_check_palette(const char *fn, const dp_palette *p);
+int pattern_ensure_table(const dp_palette *pal, hipStream_t s);
+PatDev pattern_snapshot(const dp_palette *pal);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,
                           hipStream_t s);
 }  // namespace dp

@@ -7,6 +7,7 @@
 #include <numeric>
 
 #include "dp_internal.h"
+#include "../../include/ditherpie_hip_dotdiff.h"
 
 namespace dp {
 
@@ -1035,6 +1036,14 @@ int dp_resize_nearest_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_fram
     }
     if (n_frames == 0) return DP_OK;
     return launch_resize_nearest(in_dev, out_dev, n_frames, h, w, oh, ow, (hipStream_t)stream);
+}
+
+// include/ditherpie_hip_dotdiff.h: host logic only (the device entry point is in dotdiff.hip)
+int dp_dotdiff_reach(const uint8_t *classes_host, int m)
+{
+    if (!dotdiff_matrix_ok(classes_host, m)) return -1;
+    int level[kDotDiffMaxCells];
+    return dotdiff_levels(classes_host, m, level);
 }
 
 int dp_profile_enable(int on)

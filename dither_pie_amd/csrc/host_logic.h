@@ -2256,4 +2256,67 @@ inline int64_t png_file_assemble(const uint8_t *streams, const int64_t stream_st
     return at;
 }
 
+// ---- Dot diffusion: class matrices and their level schedule (dotdiff.hip, include/ditherpie_hip_dotdiff.h) -----------------
+//
+// A class matrix is m x m (m = 2, 4, 8, 16), a permutation of 0 .. m*m-1, tiled over the plane.  level(cell) is the largest
+// number of king moves of a path through the tiled matrix that ends in the cell and along which the class strictly
+// increases; reach = the largest level.  Cells of one level are never neighbours (of two neighbours the one of the higher
+// class has the higher level) and a cell's level exceeds that of every neighbour of a lower class: the pixels of one level
+// can be quantised together once the levels below are done, which is how the kernel walks a tile.
+constexpr int kDotDiffMaxReach = 16;        // DP_DOTDIFF_MAX_REACH: the halo a tile of the kernel carries on each side
+constexpr int kDotDiffMaxCells = 256;
+
+inline bool dotdiff_matrix_ok(const uint8_t *cls, const int m)
+{
+    if (!cls || (m != 2 && m != 4 && m != 8 && m != 16)) return false;
+    bool seen[kDotDiffMaxCells] = {};
+    for (int i = 0; i < m * m; ++i) {
+        if ((int)cls[i] >= m * m || seen[cls[i]]) return false;   // (m = 16: every byte is below 256, repeats remain)
+        seen[cls[i]] = true;
+    }
+    return true;
+}
+
+// level[cell] for a matrix that dotdiff_matrix_ok accepts (int: a 16 x 16 matrix can reach 255); -> reach
+inline int dotdiff_levels(const uint8_t *cls, const int m, int *level)
+{
+    int cell_of[kDotDiffMaxCells];
+    for (int i = 0; i < m * m; ++i) cell_of[cls[i]] = i;
+    int reach = 0;
+    for (int c = 0; c < m * m; ++c) {       // in class order: every neighbour of a lower class has its level already
+        const int cell = cell_of[c], y = cell / m, x = cell % m;
+        int lv = 0;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!dy && !dx) continue;
+                const int n = ((y + dy + m) % m) * m + (x + dx + m) % m;
+                if ((int)cls[n] < c) lv = std::max(lv, level[n] + 1);
+            }
+        level[cell] = lv;
+        reach = std::max(reach, lv);
+    }
+    return reach;
+}
+
+// What the kernel is given besides the matrix: the cells ordered by level (ascending, by cell number inside a level) and
+// where each level starts in that order.  For a matrix of reach <= kDotDiffMaxReach.
+struct DotDiffSchedule {
+    uint8_t order[kDotDiffMaxCells];
+    uint16_t start[kDotDiffMaxReach + 2];   // level l: order[start[l] .. start[l + 1])
+    int n_levels;                           // reach + 1
+};
+
+inline void dotdiff_schedule(const int *level, const int m, const int reach, DotDiffSchedule &s)
+{
+    s.n_levels = reach + 1;
+    int at = 0;
+    for (int l = 0; l <= reach; ++l) {
+        s.start[l] = (uint16_t)at;
+        for (int i = 0; i < m * m; ++i)
+            if (level[i] == l) s.order[at++] = (uint8_t)i;
+    }
+    for (int l = reach + 1; l < kDotDiffMaxReach + 2; ++l) s.start[l] = (uint16_t)at;
+    for (int i = at; i < kDotDiffMaxCells; ++i) s.order[i] = 0;
+}
+
 }  // namespace dp

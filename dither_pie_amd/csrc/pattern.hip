@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "../../include/ditherpie_hip_pattern.h"
+#include "pattern_tab.hip.h"
 
 namespace dp {
 namespace {
@@ -35,13 +36,6 @@ constexpr size_t kTabBytes = (size_t)DP_PATTERN_TABLE_BYTES;
 constexpr int kBuildSide = 2048;                                   // the table is built in "frames" of 2048 x 2048 colours
 constexpr uint32_t kBuildPx = (uint32_t)kBuildSide * kBuildSide;   // 2^22: four of them
 constexpr size_t kSideBytes = 3 * 256 * sizeof(uint32_t);          // c_rank, out_rank, the ranks by index (build only)
-
-template <bool BRICK>
-__device__ __forceinline__ uint32_t tab_addr(const uint32_t r, const uint32_t g, const uint32_t b)
-{
-    if (BRICK) return ((r >> 2) << 6) | ((g >> 2) << 12) | ((b >> 2) << 18) | (r & 3u) | ((g & 3u) << 2) | ((b & 3u) << 4);
-    return r | (g << 8) | (b << 16);
-}
 
 template <bool BRICK>
 __device__ __forceinline__ uint32_t tab_colour(const uint32_t a)   // the inverse: r | g<<8 | b<<16 of table address a
@@ -245,22 +239,25 @@ int fill_table(const PalDev &d, uint8_t *tab, int brick, hipStream_t s)
     return rc;
 }
 
-// K <= 256 and every palette value in [0, 255] (what trunc() and the clamp of the definition assume)
-int check_palette(const char *fn, const dp_palette *p)
+}  // namespace
+
+// K <= 256 and every palette value in [0, 255] (what trunc() and the clamp of the definitions assume); `fn` is the entry
+// point that is refusing (dp_pattern_*, dp_dotdiff_u8)
+int pattern_check_palette(const char *fn, const dp_palette *p)
 {
     if (p->dev.K > 256) {
-        set_error("%s: pattern dithering supports at most 256 colours, the palette has %d", fn, p->dev.K);
+        set_error("%s: the nearest table supports at most 256 colours, the palette has %d", fn, p->dev.K);
         return DP_EUNSUPPORTED;
     }
     for (const double v : p->pts_host)
         if (!(v >= 0.0 && v <= 255.0)) {
-            set_error("%s: pattern dithering needs palette values in [0, 255], found %g", fn, v);
+            set_error("%s: the nearest table needs palette values in [0, 255], found %g", fn, v);
             return DP_EUNSUPPORTED;
         }
     return DP_OK;
 }
 
-PatDev pat_snapshot(const dp_palette *pal_c)
+PatDev pattern_snapshot(const dp_palette *pal_c)
 {
     dp_palette *p = const_cast<dp_palette *>(pal_c);
     std::lock_guard<std::mutex> lock(p->dev_mu);
@@ -269,7 +266,7 @@ PatDev pat_snapshot(const dp_palette *pal_c)
 
 // Build the table once (under build_mu; the launches go to `s`, which is waited for before the table is published: another
 // thread may use it on another stream at once).  A failed build leaves the palette without a table; the next call retries.
-int ensure_table(const dp_palette *pal_c, hipStream_t s)
+int pattern_ensure_table(const dp_palette *pal_c, hipStream_t s)
 {
     dp_palette *p = const_cast<dp_palette *>(pal_c);
     std::lock_guard<std::mutex> lock(p->build_mu);
@@ -328,7 +325,6 @@ int ensure_table(const dp_palette *pal_c, hipStream_t s)
     return DP_OK;
 }
 
-}  // namespace
 }  // namespace dp
 
 using namespace dp;
@@ -349,9 +345,9 @@ int dp_pattern_prepare(dp_palette *pal)
         set_error("dp_pattern_prepare: NULL palette");
         return DP_EINVAL;
     }
-    const int rc = check_palette("dp_pattern_prepare", pal);
+    const int rc = pattern_check_palette("dp_pattern_prepare", pal);
     if (rc != DP_OK) return rc;
-    return ensure_table(pal, nullptr);
+    return pattern_ensure_table(pal, nullptr);
 }
 
 int dp_pattern_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, int y0, int x0, const dp_palette *pal,
@@ -371,10 +367,10 @@ int dp_pattern_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
         set_error("dp_pattern_u8: strength256 must lie in 0 .. 256, not %d", strength256);
         return DP_EINVAL;
     }
-    int rc = check_palette("dp_pattern_u8", pal);
+    int rc = pattern_check_palette("dp_pattern_u8", pal);
     if (rc != DP_OK) return rc;
     if (n_frames == 0) return DP_OK;
-    rc = ensure_table(pal, (hipStream_t)stream);
+    rc = pattern_ensure_table(pal, (hipStream_t)stream);
     if (rc != DP_OK) return rc;
     const uint8_t *lut;
     {
@@ -382,7 +378,7 @@ int dp_pattern_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
         std::lock_guard<std::mutex> lock(p->dev_mu);
         lut = p->dev.lut_in;
     }
-    return launch_pattern(in_dev, out_dev, n_frames, h, w, y0, x0, pat_snapshot(pal), lut, matrix, strength256, (hipStream_t)stream);
+    return launch_pattern(in_dev, out_dev, n_frames, h, w, y0, x0, pattern_snapshot(pal), lut, matrix, strength256, (hipStream_t)stream);
 }
 
 }  // extern "C"

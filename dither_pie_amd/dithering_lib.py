@@ -83,7 +83,7 @@ __all__ = [
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
-    "WaveletDitherStrategy", "PatternDitherStrategy", "generate_blue_noise",
+    "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "generate_blue_noise",
 ]
 
 
@@ -1163,6 +1163,93 @@ class PatternDitherStrategy(BaseDitherStrategy):
             return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
 
 
+# ------------------------------------------------------------------------------------- Dot diffusion (Knuth)
+class DotDiffusionDitherStrategy(BaseDitherStrategy):
+    """Dot diffusion (Knuth 1987): error diffusion without a scan.  Every pixel has a class from a small tiled class matrix,
+    pixels are quantised in class order and a pixel's error goes to its neighbours of a higher class only (weight 2
+    orthogonally, 1 diagonally).  Dependencies are local, so the GPU diffuses tiles independently and exactly
+    (dotdiff.hip; include/ditherpie_hip_dotdiff.h has the integer definition): the look of diffusion at a small multiple of the
+    cost of an ordered mode.  Errors cross every tile a caller could cut, so _run refuses (y0, x0) as the scans do.
+
+    matrix: a name of MATRICES ("knuth": Knuth's 8 x 8 matrix, the default) or an m x m array (m = 2, 4, 8, 16) that is a
+    permutation of 0 .. m*m-1 and whose reach (backend.dotdiff_reach) is at most 16.  strength256 = round(strength * 256).
+    Not in the reference and not a DitherMode member: pass an instance as ImageDitherer(dither_mode=...), or use
+    dither_frames().  A bad matrix, a strength outside [0, 1] and a palette of more than 256 colours raise ValueError at
+    dither time."""
+
+    MATRICES = {
+        "knuth": ((34, 48, 40, 32, 29, 15, 23, 31), (42, 58, 56, 53, 21, 5, 7, 10), (50, 62, 61, 45, 13, 1, 2, 18),
+                  (38, 46, 54, 37, 25, 17, 9, 26), (28, 14, 22, 30, 35, 49, 41, 33), (20, 4, 6, 11, 43, 59, 57, 52),
+                  (12, 0, 3, 19, 51, 63, 60, 44), (24, 16, 8, 27, 39, 47, 55, 36)),
+    }
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            'matrix': {'type': 'choice', 'default': 'knuth', 'choices': ['knuth'], 'label': 'Class Matrix',
+                       'description': 'Order in which the pixels of a tile are quantised (an m x m array is taken too)'},
+            'strength': {'type': 'float', 'default': 1.0, 'min': 0.0, 'max': 1.0, 'step': 0.05, 'label': 'Strength',
+                         'description': 'Share of a pixel\'s error handed to its neighbours (0 = nearest colour)'},
+        }
+
+    def __init__(self, matrix="knuth", strength: float = 1.0):
+        self.matrix = matrix
+        self.strength = strength
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'matrix': self.matrix, 'strength': self.strength}
+
+    def _settings(self):
+        """-> (the class matrix as a uint8 array, strength256)."""
+        from . import backend
+        matrix = self.matrix
+        if isinstance(matrix, str):
+            if matrix not in self.MATRICES:
+                raise ValueError(f"dot diffusion matrix must be one of {sorted(self.MATRICES)} or an array, not {matrix!r}")
+            matrix = self.MATRICES[matrix]
+        classes = backend._dotdiff_classes(matrix)
+        try:
+            s256 = int(round(float(self.strength) * 256))
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"dot diffusion strength must be a number in [0, 1], not {self.strength!r}") from None
+        if not 0 <= s256 <= 256:
+            raise ValueError(f"dot diffusion strength must lie in [0, 1], not {self.strength!r}")
+        return classes, s256
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("dot diffusion hands errors across every tile edge and cannot be tiled by the caller")
+        classes, s256 = self._settings()
+        return backend.dotdiff(frames, pal, classes, s256, out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"dot diffusion needs a non-empty image, not {h} x {w}")
+        self._settings()
+        if len(palette_arr) > 256:
+            raise ValueError(f"dot diffusion supports at most 256 colours, the palette has {len(palette_arr)}")
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> dithered uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(dither_mode=self, palette=palette, use_gamma=use_gamma).apply_dithering would dither it (palette:
+        the reference's list of RGB triples).  Frames stay in HBM; `out` must not be the frames."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, out=out)
+
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8 (at most 256 colours)."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
+
+
 # strategy instances (ImageDitherer(dither_mode=<instance>)) that are per-pixel independent given global coordinates, as
 # ORDERED_MODES are among the enum members: these shard by row bands / tiles (sharding.dither_band)
 ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
@@ -1213,8 +1300,8 @@ class ImageDitherer:
         """Defaults from get_parameter_info() overlaid by dither_params (dithering_lib.py:1918-1950);
         unknown mode -> ValueError, unknown parameter -> TypeError from the constructor.  An addition to the reference's
         interface: a BaseDitherStrategy INSTANCE as the mode is returned as it is (dither_params do not apply to it) --
-        how modes without a DitherMode member (PatternDitherStrategy, HalftoneDitherStrategy, WaveletDitherStrategy)
-        reach every ImageDitherer / VideoProcessor path."""
+        how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, HalftoneDitherStrategy,
+        WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
         if isinstance(mode, BaseDitherStrategy):
             return mode
         if mode in _OUT_OF_SCOPE:
