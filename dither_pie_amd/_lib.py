@@ -181,6 +181,13 @@ _SIGS_DOTDIFF = {
     "dp_dotdiff_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _vp]),
 }
 EXPORTS_DOTDIFF = tuple(_SIGS_DOTDIFF)
+# include/ditherpie_hip_cells.h: cell-palette dithering (k colours per cell, every allowed set searched); a table of its own
+# for the same reason.
+_SIGS_CELLS = {
+    "dp_cells_candidates": (_i, [_i, _i, _u32, _vp, _i]),
+    "dp_cells_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _i, _i, _u32, _vp, _i, _i, _i, _vp]),
+}
+EXPORTS_CELLS = tuple(_SIGS_CELLS)
 
 
 def build(force=False):
@@ -224,7 +231,8 @@ def load():
                 for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_INDEXED.items()) + list(_SIGS_CLIP.items())
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
-                                          + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())):
+                                          + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
+                                          + list(_SIGS_CELLS.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

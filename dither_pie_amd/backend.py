@@ -410,6 +410,87 @@ def dotdiff(frames, pal: Palette, classes, strength256, out=None):
     return out.view(frames.shape)
 
 
+CELL_SIZES = (4, 8, 16)     # cells of dp_cells_u8 are cw x ch pixels, each of these
+CELL_MATRICES = (2, 4, 8)   # the Bayer matrix of its perturbation
+CELL_MAX_COLOURS = 16       # the palette of a cell-palette dither
+CELL_MAX_CHOSEN = 4         # colours a cell chooses besides the fixed ones
+CELL_MAX_GROUPS = 4
+
+
+def _cell_masks(K, colours, fixed_mask, groups):
+    """The arguments of the candidate enumeration, checked -> (fixed_mask, the groups as a uint16 array); ValueError."""
+    if not (isinstance(K, (int, np.integer)) and 1 <= K <= CELL_MAX_COLOURS):
+        raise ValueError(f"cell-palette dithering supports 1 .. {CELL_MAX_COLOURS} colours, the palette has {K!r}")
+    if not (isinstance(colours, (int, np.integer)) and 1 <= colours <= CELL_MAX_CHOSEN):
+        raise ValueError(f"cell-palette colours per cell must be an integer in 1 .. {CELL_MAX_CHOSEN}, not {colours!r}")
+    if not (isinstance(fixed_mask, (int, np.integer)) and 0 <= fixed_mask < 1 << K):
+        raise ValueError(f"cell-palette fixed_mask must name palette entries below {K}, not {fixed_mask!r}")
+    if groups is None:
+        groups = [(1 << K) - 1]
+    try:
+        groups = [g for g in groups]
+    except TypeError:
+        raise ValueError(f"cell-palette groups must be 1 .. {CELL_MAX_GROUPS} masks, not {groups!r}") from None
+    if not 1 <= len(groups) <= CELL_MAX_GROUPS:
+        raise ValueError(f"cell-palette groups must be 1 .. {CELL_MAX_GROUPS} masks, not {len(groups)}")
+    for g in groups:
+        if not (isinstance(g, (int, np.integer)) and 0 < g < 1 << K):
+            raise ValueError(f"a cell-palette group must be a non-empty mask of palette entries below {K}, not {g!r}")
+        if bin(int(g) & ~int(fixed_mask)).count("1") < colours:
+            raise ValueError(f"cell-palette group {int(g):#x} has fewer than {colours} entries outside the fixed ones")
+    return int(fixed_mask), np.array([int(g) for g in groups], np.uint16)
+
+
+def cell_candidates(K, colours, fixed_mask=0, groups=None):
+    """The number of colour sets dp_cells_u8 tries per cell (dp_cells_candidates; include/ditherpie_hip_cells.h has the
+    enumeration): groups=None is one group of all K entries.  Host code: no device is needed."""
+    fixed_mask, g = _cell_masks(K, colours, fixed_mask, groups)
+    n = int(_lib.load().dp_cells_candidates(int(K), int(colours), fixed_mask, _np_ptr(g), len(g)))
+    if n < 0:
+        raise ValueError("cell-palette dithering: the library refused the groups")
+    return n
+
+
+def cells(frames, pal: Palette, cell, colours, matrix, spread, fixed_mask=0, groups=None, out=None, sets=None):
+    """Cell-palette dithering (include/ditherpie_hip_cells.h) of uint8 frames already in HBM -> uint8 frames: the frame is cut
+    into cells of cell = (cw, ch) pixels (each 4, 8 or 16), every cell shows `colours` (1 .. 4) palette entries of its choice,
+    all from one of the `groups` (masks; None: one group of all entries), besides the entries of fixed_mask; every allowed set
+    is tried on the pixels perturbed by the Bayer matrix (2, 4, 8) times spread (0 .. 255).  At most 16 colours.  `out` may be
+    the frames.  sets: True or a uint16 tensor [N, ceil(H/ch), ceil(W/cw)] -> returns (out, sets), the mask each cell took."""
+    try:
+        cw, ch = cell
+    except (TypeError, ValueError):
+        raise ValueError(f"cell must be a pair (width, height) of {CELL_SIZES}, not {cell!r}") from None
+    if cw not in CELL_SIZES or ch not in CELL_SIZES:
+        raise ValueError(f"cell must be a pair (width, height) of {CELL_SIZES}, not {cell!r}")
+    if matrix not in CELL_MATRICES:
+        raise ValueError(f"cell-palette matrix must be one of {CELL_MATRICES}, not {matrix!r}")
+    if not (isinstance(spread, (int, np.integer)) and 0 <= spread <= 255):
+        raise ValueError(f"cell-palette spread must be an integer in 0 .. 255, not {spread!r}")
+    fixed_mask, g = _cell_masks(pal.K, colours, fixed_mask, groups)
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    _check_palette_device(pal, f)
+    shape = (n, -(-h // ch), -(-w // cw))
+    want_sets = sets is not None and sets is not False
+    if sets is True:
+        sets = torch.empty(shape, dtype=torch.uint16, device=f.device)
+    elif want_sets:
+        if not (isinstance(sets, torch.Tensor) and sets.is_cuda and sets.dtype == torch.uint16 and sets.device == f.device):
+            raise TypeError("sets must be True or a CUDA uint16 tensor on the frames' device")
+        if sets.numel() != shape[0] * shape[1] * shape[2] or not sets.is_contiguous():
+            raise ValueError(f"sets must be contiguous with {shape[0]} x {shape[1]} x {shape[2]} elements")
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):   # (no workspace: the lock of the (device, stream) only)
+        check(L.dp_cells_u8(f.data_ptr(), out.data_ptr(), sets.data_ptr() if want_sets else None, n, h, w, pal._h, int(cw), int(ch),
+                            int(colours), fixed_mask, _np_ptr(g), len(g), int(matrix), int(spread), _stream()))
+    out = out.view(frames.shape)
+    if not want_sets:
+        return out
+    return out, sets.view(shape if frames.dim() == 4 else shape[1:])
+
+
 class HalftoneParams(C.Structure):
     """struct dp_halftone_params (include/ditherpie_hip.h)."""
     _fields_ = [("cell_size", C.c_double), ("cos_a", C.c_double), ("sin_a", C.c_double), ("exponent", C.c_double),

@@ -8,6 +8,7 @@
 
 #include "dp_internal.h"
 #include "../../include/ditherpie_hip_dotdiff.h"
+#include "../../include/ditherpie_hip_cells.h"
 
 namespace dp {
 
@@ -1044,6 +1045,13 @@ int dp_dotdiff_reach(const uint8_t *classes_host, int m)
     if (!dotdiff_matrix_ok(classes_host, m)) return -1;
     int level[kDotDiffMaxCells];
     return dotdiff_levels(classes_host, m, level);
+}
+
+// include/ditherpie_hip_cells.h: host logic only (the device entry point is in cells.hip)
+int dp_cells_candidates(int K, int colours, uint32_t fixed_mask, const uint16_t *groups_host, int n_groups)
+{
+    CellsPlan plan;
+    return cells_plan(K, colours, fixed_mask, groups_host, n_groups, plan);
 }
 
 int dp_profile_enable(int on)

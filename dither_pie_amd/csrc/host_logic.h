@@ -2319,4 +2319,105 @@ inline void dotdiff_schedule(const int *level, const int m, const int reach, Dot
     for (int i = at; i < kDotDiffMaxCells; ++i) s.order[i] = 0;
 }
 
+// ---- Cell-palette dithering: the candidates of a cell and the perturbation (cells.hip, include/ditherpie_hip_cells.h) ------
+//
+// Every cell may show `colours` = k entries of its choice besides the entries of `fixed`.  The candidates are enumerated
+// group by group in the order given; within a group the sets T are the k-subsets of the group's entries outside `fixed`, in
+// lexicographic order of their ascending index tuples, and the candidate is S = T | fixed.  At most 4 C(16, 4) = 7280.
+// The enumeration is stated once: cells_plan validates and counts, cells_unrank maps a rank to its mask (host and device).
+constexpr int kCellPalMaxK = 16, kCellPalMaxColours = 4, kCellPalMaxGroups = 4, kCellPalMaxCandidates = 7280;
+
+DP_HD inline uint32_t cells_binom(const int n, const int k)   // C(n, k) for n <= 16, k <= 4; 0 for k > n or k < 0
+{
+    if (k < 0 || k > n) return 0u;
+    uint32_t c = 1u;
+    for (int i = 1; i <= k; ++i) c = c * (uint32_t)(n - k + i) / (uint32_t)i;   // C(n-k+i, i): exact at every step
+    return c;
+}
+
+DP_HD inline int cells_popcount16(uint32_t v)
+{
+    int n = 0;
+    for (v &= 0xffffu; v; v &= v - 1u) ++n;
+    return n;
+}
+
+struct CellsPlan {
+    uint16_t avail[kCellPalMaxGroups];       // group & ~fixed: what a candidate of the group chooses from
+    uint16_t first[kCellPalMaxGroups + 1];   // the rank of the group's first candidate; first[n_groups] = the count
+    uint16_t fixed;
+    int colours, n_groups;
+};
+
+// -> the number of candidates, or -1: K outside 1 .. 16, colours outside 1 .. 4, n_groups outside 1 .. 4, no groups, a bit of
+// fixed or of a group at or above K, an empty group, a group with fewer than `colours` entries outside fixed
+inline int cells_plan(const int K, const int colours, const uint32_t fixed, const uint16_t *groups, const int n_groups, CellsPlan &p)
+{
+    if (K < 1 || K > kCellPalMaxK || colours < 1 || colours > kCellPalMaxColours || n_groups < 1 || n_groups > kCellPalMaxGroups || !groups)
+        return -1;
+    const uint32_t beyond = ~((1u << K) - 1u);
+    if (fixed & beyond) return -1;
+    p = CellsPlan{};
+    p.fixed = (uint16_t)fixed;
+    p.colours = colours;
+    p.n_groups = n_groups;
+    uint32_t at = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const uint32_t grp = groups[g];
+        if (!grp || (grp & beyond)) return -1;
+        p.avail[g] = (uint16_t)(grp & ~fixed);
+        const int n = cells_popcount16(p.avail[g]);
+        if (n < colours) return -1;
+        p.first[g] = (uint16_t)at;
+        at += cells_binom(n, colours);
+    }
+    for (int g = n_groups; g <= kCellPalMaxGroups; ++g) p.first[g] = (uint16_t)at;
+    return (int)at;
+}
+
+// the mask S of candidate `rank` (rank < first[n_groups])
+DP_HD inline uint32_t cells_unrank(const CellsPlan &p, const uint32_t rank)
+{
+    int g = 0;
+    while (g + 1 < p.n_groups && rank >= p.first[g + 1]) ++g;
+    uint32_t r = rank - p.first[g], left = p.avail[g], mask = 0u;
+    int n = cells_popcount16(left), k = p.colours;
+    for (int j = 0; j < kCellPalMaxK && k > 0; ++j) {
+        if (!((left >> j) & 1u)) continue;
+        --n;                                           // entries of the group above j
+        const uint32_t with = cells_binom(n, k - 1);   // candidates whose next entry is j
+        if (r < with) {
+            mask |= 1u << j;
+            --k;
+        } else {
+            r -= with;
+        }
+    }
+    return mask | p.fixed;
+}
+
+// B_m[y mod m][x mod m], the Bayer rank matrix of pattern dithering: B_2 = [[0, 2], [3, 1]], B_2m = 4 B_m(low bits) + B_2(top bit)
+inline int cells_bayer_rank(const int m, const int y, const int x)
+{
+    const int bits = m == 8 ? 3 : (m == 4 ? 2 : 1);
+    int r = 0;
+    for (int j = 0; j < bits; ++j) {
+        const int yb = (y >> j) & 1, xb = (x >> j) & 1;
+        r |= (((xb ^ yb) << 1) | yb) << (2 * (bits - 1 - j));
+    }
+    return r;
+}
+
+// t[y * m + x] = floor(((2 B_m[y][x] + 1 - m^2) * spread) / (2 m^2)) for m in {2, 4, 8}, spread 0 .. 255: -128 .. 127
+inline void cells_perturbation(const int m, const int spread, int8_t *t)
+{
+    const int mm = m * m;
+    for (int y = 0; y < m; ++y)
+        for (int x = 0; x < m; ++x) {
+            const int v = (2 * cells_bayer_rank(m, y, x) + 1 - mm) * spread;
+            const int d = 2 * mm;
+            t[y * m + x] = (int8_t)(v >= 0 ? v / d : -((-v + d - 1) / d));
+        }
+}
+
 }  // namespace dp

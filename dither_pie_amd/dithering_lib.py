@@ -83,7 +83,8 @@ __all__ = [
     "BayerDitherStrategy", "BlueNoiseDitherStrategy", "InterleavedGradientNoiseDitherStrategy",
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
-    "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "generate_blue_noise",
+    "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "CellPaletteDitherStrategy",
+    "generate_blue_noise",
 ]
 
 
@@ -1250,6 +1251,145 @@ class DotDiffusionDitherStrategy(BaseDitherStrategy):
             return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
 
 
+# ------------------------------------------------------------------------------------- Cell palettes (k colours per cell)
+class CellPaletteDitherStrategy(BaseDitherStrategy):
+    """Cell-palette dithering: the picture is cut into small cells and every cell may show only a few of the palette's
+    colours -- the colour constraint of the 8-bit home computers.  Per cell EVERY allowed set of colours is tried on the
+    pixels, perturbed by a Bayer matrix, and the set of least total squared error is taken (cells.hip;
+    include/ditherpie_hip_cells.h has the integer definition), so there is no attribute clash to repair.
+
+    cell: "WxH" or a pair (width, height), each of 4, 8, 16.  colours: how many entries a cell chooses, 1 .. 4.  matrix:
+    "2x2", "4x4", "8x8" (or 2, 4, 8), spread 0 .. 255: the perturbation.  shared: palette indices every cell owns besides
+    its choice.  groups: an iterable of iterables of indices; the chosen entries of a cell all come from one group (None:
+    one group of the whole palette).  At most 16 colours.
+      C64 hires:        CellPaletteDitherStrategy() with the caller's 16-colour palette (8 x 8 cells, two colours each)
+      C64 multicolour:  CellPaletteDitherStrategy(cell="4x8", colours=3, shared=(background,))
+      ZX Spectrum:      CellPaletteDitherStrategy.zx_spectrum() with ZX_SPECTRUM_PALETTE (two colours of one brightness)
+    Not in the reference and not a DitherMode member: pass an instance as ImageDitherer(dither_mode=...), or use
+    dither_frames().  Cells are anchored at the frame's first pixel, so _run refuses (y0, x0): a band edge would split
+    cells.  Bad settings and a palette of more than 16 colours raise ValueError at dither time."""
+
+    _ZX = ((0, 0, 1), (1, 0, 0), (1, 0, 1), (0, 1, 0), (0, 1, 1), (1, 1, 0), (1, 1, 1))   # blue red magenta green cyan yellow white
+    ZX_SPECTRUM_PALETTE = ([(0, 0, 0)] + [tuple(215 * c for c in t) for t in _ZX] + [tuple(255 * c for c in t) for t in _ZX])
+    ZX_SPECTRUM_GROUPS = ((0, 1, 2, 3, 4, 5, 6, 7), (0, 8, 9, 10, 11, 12, 13, 14))
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        sizes = [f"{a}x{b}" for a in (4, 8, 16) for b in (4, 8, 16)]
+        return {
+            'cell': {'type': 'choice', 'default': '8x8', 'choices': sizes, 'label': 'Cell Size',
+                     'description': 'Width x height of the cells that share a small set of colours'},
+            'colours': {'type': 'int', 'default': 2, 'min': 1, 'max': 4, 'label': 'Colours per Cell',
+                        'description': 'Palette entries a cell chooses (besides the shared ones)'},
+            'matrix': {'type': 'choice', 'default': '4x4', 'choices': ['2x2', '4x4', '8x8'], 'label': 'Matrix Size',
+                       'description': 'Bayer matrix that perturbs the pixels before the search'},
+            'spread': {'type': 'int', 'default': 64, 'min': 0, 'max': 255, 'label': 'Spread',
+                       'description': 'Amplitude of the perturbation (0 = nearest colour of the cell\'s set)'},
+        }
+
+    def __init__(self, cell="8x8", colours: int = 2, matrix="4x4", spread: int = 64, shared=(), groups=None):
+        self.cell = cell
+        self.colours = colours
+        self.matrix = matrix
+        self.spread = spread
+        self.shared = shared
+        self.groups = groups
+
+    @classmethod
+    def zx_spectrum(cls, matrix="4x4", spread: int = 64):
+        """The ZX Spectrum's rule for ZX_SPECTRUM_PALETTE: 8 x 8 cells, two colours of one brightness level (black is in both)."""
+        return cls(cell="8x8", colours=2, matrix=matrix, spread=spread, groups=cls.ZX_SPECTRUM_GROUPS)
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'cell': self.cell, 'colours': self.colours, 'matrix': self.matrix, 'spread': self.spread,
+                'shared': self.shared, 'groups': self.groups}
+
+    @staticmethod
+    def _mask(indices, what):
+        try:
+            idx = [i for i in indices]
+        except TypeError:
+            raise ValueError(f"cell-palette {what} must be an iterable of palette indices, not {indices!r}") from None
+        mask = 0
+        for i in idx:
+            if not (isinstance(i, (int, np.integer)) and 0 <= i < 16):
+                raise ValueError(f"cell-palette {what} must hold palette indices in 0 .. 15, not {i!r}")
+            mask |= 1 << int(i)
+        return mask
+
+    def _settings(self):
+        """-> ((cw, ch), colours, matrix size, spread, fixed mask, group masks or None)."""
+        from . import backend
+        cell = self.cell
+        if isinstance(cell, str):
+            parts = cell.lower().split("x")
+            if len(parts) != 2 or not all(p.strip().isdigit() for p in parts):
+                raise ValueError(f"cell must be 'WxH' with W, H in {backend.CELL_SIZES}, not {self.cell!r}")
+            cell = (int(parts[0]), int(parts[1]))
+        try:
+            cw, ch = cell
+        except (TypeError, ValueError):
+            raise ValueError(f"cell must be 'WxH' or a pair with W, H in {backend.CELL_SIZES}, not {self.cell!r}") from None
+        if cw not in backend.CELL_SIZES or ch not in backend.CELL_SIZES:
+            raise ValueError(f"cell must be 'WxH' or a pair with W, H in {backend.CELL_SIZES}, not {self.cell!r}")
+        if not (isinstance(self.colours, (int, np.integer)) and 1 <= self.colours <= backend.CELL_MAX_CHOSEN):
+            raise ValueError(f"colours per cell must be an integer in 1 .. {backend.CELL_MAX_CHOSEN}, not {self.colours!r}")
+        m = self.matrix
+        if isinstance(m, str):
+            m = {"2x2": 2, "4x4": 4, "8x8": 8}.get(m)
+        if m not in backend.CELL_MATRICES:
+            raise ValueError(f"cell-palette matrix must be '2x2', '4x4' or '8x8', not {self.matrix!r}")
+        if not (isinstance(self.spread, (int, np.integer)) and 0 <= self.spread <= 255):
+            raise ValueError(f"cell-palette spread must be an integer in 0 .. 255, not {self.spread!r}")
+        fixed = self._mask(self.shared, "shared")
+        groups = None
+        if self.groups is not None:
+            try:
+                groups = [self._mask(g, "groups") for g in self.groups]
+            except TypeError:
+                raise ValueError(f"cell-palette groups must be an iterable of iterables of indices, not {self.groups!r}") from None
+        return (int(cw), int(ch)), int(self.colours), int(m), int(self.spread), fixed, groups
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None, sets=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("cell-palette dithering anchors its cells at the frame's first pixel and cannot be tiled by the caller")
+        cell, colours, m, spread, fixed, groups = self._settings()
+        if pal.K > backend.CELL_MAX_COLOURS:
+            raise ValueError(f"cell-palette dithering supports at most {backend.CELL_MAX_COLOURS} colours, the palette has {pal.K}")
+        return backend.cells(frames, pal, cell, colours, m, spread, fixed_mask=fixed, groups=groups, out=out, sets=sets)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        from . import backend
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"cell-palette dithering needs a non-empty image, not {h} x {w}")
+        _, colours, _, _, fixed, groups = self._settings()
+        if len(palette_arr) > backend.CELL_MAX_COLOURS:
+            raise ValueError(f"cell-palette dithering supports at most {backend.CELL_MAX_COLOURS} colours, "
+                             f"the palette has {len(palette_arr)}")
+        backend._cell_masks(len(palette_arr), colours, fixed, groups)
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None, return_sets: bool = False):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> dithered uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(dither_mode=self, palette=palette, use_gamma=use_gamma).apply_dithering would dither it (palette:
+        the reference's list of RGB triples).  Frames stay in HBM; `out` may be the frames.  return_sets: -> (frames, sets),
+        sets a uint16 CUDA tensor [N, ceil(H/ch), ceil(W/cw)] (or without N): the mask of the entries each cell took."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, out=out, sets=True if return_sets else None)
+
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
+
+
 # strategy instances (ImageDitherer(dither_mode=<instance>)) that are per-pixel independent given global coordinates, as
 # ORDERED_MODES are among the enum members: these shard by row bands / tiles (sharding.dither_band)
 ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
@@ -1300,8 +1440,8 @@ class ImageDitherer:
         """Defaults from get_parameter_info() overlaid by dither_params (dithering_lib.py:1918-1950);
         unknown mode -> ValueError, unknown parameter -> TypeError from the constructor.  An addition to the reference's
         interface: a BaseDitherStrategy INSTANCE as the mode is returned as it is (dither_params do not apply to it) --
-        how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, HalftoneDitherStrategy,
-        WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
+        how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, CellPaletteDitherStrategy,
+        HalftoneDitherStrategy, WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
         if isinstance(mode, BaseDitherStrategy):
             return mode
         if mode in _OUT_OF_SCOPE:
