@@ -36,7 +36,10 @@ __device__ __forceinline__ int ed_key16(const float4 c, const float o0, const fl
 // term |o|^2 is common to all candidates and the bias keeps the value inside [2^16, 2^19) for points of the cube -- positive,
 // so the bit patterns order like the values, and with an ulp of at most 2^-5: one rounding of the fourth word (float
 // palettes; integer ones are exact), one per multiply-add and up to 8 ulp from the tag bits are below 0.32 in absolute
-// terms per key (ed_expanded_margin).
+// terms per key (ed_expanded_margin).  Only the EXPANDED instance of nearest_color_cells calls it, and only
+// ed_wavefront_kernel (ediff.hip) instantiates that one, after clamping the point to [0, 255]: the variable-weight diffusers, whose
+// points leave the cube, take the plain instance (the face, edge and corner queries of tests/test_gpu_steered_queries.py sit
+// on that boundary).
 __device__ __forceinline__ int ed_key_expanded(const float4 x, const float o0, const float o1, const float o2, const uint32_t tag)
 {
     keep_record_whole(x);

@@ -57,7 +57,10 @@ template <int CAP>
 __device__ __forceinline__ int nearest_any(const PalDev &pal, const float4 *__restrict__ cand, const float o0,
                                            const float o1, const float o2)
 {
-    // float32 prefilter with a relative AND absolute margin (values are not clamped here, distances can be tiny).
+    // float32 prefilter with a RELATIVE margin only (values are not clamped here, distances can be tiny -- and need no absolute
+    // margin: each difference c - o is rounded once and the three squares are summed without cancellation, so the float32
+    // distance is within a few 2^-24 of the exact one however small it is; tests/test_gpu_steered_queries.py asks near ties
+    // down to 1e-7 of d0 and exact ties at fractional points, inside and beyond the cube).
     // `cand` = {x, y, z, out_rgb}: in LDS for the wavefront kernel (broadcast reads, four in flight), global otherwise
     float b0 = __int_as_float(0x7f800000), b1 = b0;
     int i0 = 0;

@@ -29,7 +29,9 @@
  *   orc_hybrid_numba_u8   HybridDitherStrategy's numba branch (_hybrid_numba, :1396-1494) -- parity unpinned, see the function
  *   orc_error_diffusion_u8 ErrorDiffusionDitherStrategy.dither, pure-Python
  *                         branch                           dithering_lib.py:655-690
- *   orc_kmeans_step       one Lloyd assignment + accumulation pass of
+ *   orc_error_diffusion_q_u8, orc_var_diffusion_q_u8  the same runs, also reporting the float32 point of every
+ *                         KD-tree lookup (tests/steer_ref.py); the results are those of the plain entry points
+ *   orc_kmeans_step      one Lloyd assignment + accumulation pass of
  *                         sklearn KMeans as used at        dithering_lib.py:1854-1856
  *
  * Build: gcc -O2 -ffp-contract=off -fopenmp -shared -fPIC (see oracle/Makefile).
@@ -573,9 +575,10 @@ int orc_ordered_u8(const uint8_t *in, uint8_t *out, int32_t *idx_out, int h, int
 /* error diffusion (pure-Python branch), dithering_lib.py:655-690      */
 /* taps: dx[], dy[], wq[] = f32(weight/divisor) in list order          */
 /* ------------------------------------------------------------------ */
-int orc_error_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
-                           const uint8_t *out_colors, const uint8_t *lut_in, const int *dx, const int *dy,
-                           const double *wq, int ntaps, int serpentine)
+/* q_out (nullable): per pixel, the three float32 values handed to orc_tree_query (after the clamp) */
+static int error_diffusion_body(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                                const uint8_t *out_colors, const uint8_t *lut_in, const int *dx, const int *dy,
+                                const double *wq, int ntaps, int serpentine, float *q_out)
 {
     orc_tree *t = (orc_tree *)malloc(sizeof(orc_tree));
     float *W = (float *)malloc(sizeof(float) * 3 * (size_t)h * w);
@@ -606,6 +609,8 @@ int orc_error_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const 
                 old[c] = v;
                 q[c] = (double)v;
             }
+            if (q_out)
+                for (int c = 0; c < 3; c++) q_out[((size_t)y * w + x) * 3 + c] = old[c];
             double d2[1];
             int ii[1] = {0};
             orc_tree_query(t, q, 1, d2, ii);
@@ -640,6 +645,21 @@ int orc_error_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const 
     free(W);
     free(pick);
     return 0;
+}
+
+int orc_error_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                           const uint8_t *out_colors, const uint8_t *lut_in, const int *dx, const int *dy,
+                           const double *wq, int ntaps, int serpentine)
+{
+    return error_diffusion_body(in, out, h, w, pal, K, out_colors, lut_in, dx, dy, wq, ntaps, serpentine, NULL);
+}
+
+/* the same run, with the query points written to q_out [h*w*3] */
+int orc_error_diffusion_q_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                             const uint8_t *out_colors, const uint8_t *lut_in, const int *dx, const int *dy,
+                             const double *wq, int ntaps, int serpentine, float *q_out)
+{
+    return error_diffusion_body(in, out, h, w, pal, K, out_colors, lut_in, dx, dy, wq, ntaps, serpentine, q_out);
 }
 
 /* ------------------------------------------------------------------ */
@@ -942,9 +962,10 @@ void orc_kmeans_step(const uint8_t *px, long n, const double *centers, int K, in
 /* not-yet-visited neighbours; only model 4 clamps before the search    */
 /* and supports serpentine.                                             */
 /* ------------------------------------------------------------------ */
-int orc_var_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
-                         const uint8_t *out_colors, const uint8_t *lut_in, int model, double p0, double p1,
-                         int serpentine, const uint8_t *gate, const float *coef)
+/* q_out (nullable): per pixel, the three float32 values handed to orc_tree_query (clamped for model 4 only) */
+static int var_diffusion_body(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                              const uint8_t *out_colors, const uint8_t *lut_in, int model, double p0, double p1,
+                              int serpentine, const uint8_t *gate, const float *coef, float *q_out)
 {
     static const int fs_dx[4] = {1, -1, 0, 1}, fs_dy[4] = {0, 1, 1, 1};
     static const float fs_w[4] = {7.0f / 16, 3.0f / 16, 5.0f / 16, 1.0f / 16};
@@ -980,6 +1001,8 @@ int orc_var_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const fl
                 old[c] = v;
                 q[c] = (double)v;
             }
+            if (q_out)
+                for (int c = 0; c < 3; c++) q_out[((size_t)y * w + x) * 3 + c] = old[c];
             double d2[1];
             int ii[1] = {0};
             orc_tree_query(t, q, 1, d2, ii);
@@ -1038,6 +1061,21 @@ int orc_var_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const fl
     }
     free(t); free(W); free(gray); free(pick);
     return 0;
+}
+
+int orc_var_diffusion_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                         const uint8_t *out_colors, const uint8_t *lut_in, int model, double p0, double p1,
+                         int serpentine, const uint8_t *gate, const float *coef)
+{
+    return var_diffusion_body(in, out, h, w, pal, K, out_colors, lut_in, model, p0, p1, serpentine, gate, coef, NULL);
+}
+
+/* the same run, with the query points written to q_out [h*w*3] */
+int orc_var_diffusion_q_u8(const uint8_t *in, uint8_t *out, int h, int w, const float *pal, int K,
+                           const uint8_t *out_colors, const uint8_t *lut_in, int model, double p0, double p1,
+                           int serpentine, const uint8_t *gate, const float *coef, float *q_out)
+{
+    return var_diffusion_body(in, out, h, w, pal, K, out_colors, lut_in, model, p0, p1, serpentine, gate, coef, q_out);
 }
 
 /* scipy.ndimage.uniform_filter1d (NI_UniformFilter1D) along one axis, mode='nearest', origin 0:    */

@@ -55,6 +55,7 @@ def lib():
         L.orc_error_diffusion_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int]
+        L.orc_error_diffusion_q_u8.argtypes = L.orc_error_diffusion_u8.argtypes + [C.c_void_p]
         L.orc_error_diffusion_numba_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_double, C.c_int, C.c_int]
@@ -63,6 +64,7 @@ def lib():
         L.orc_blue_noise.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.orc_var_diffusion_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_var_diffusion_q_u8.argtypes = L.orc_var_diffusion_u8.argtypes + [C.c_void_p]
         L.orc_uniform_filter1d_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int]
         L.orc_kmeans_step.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
@@ -288,22 +290,38 @@ def ordered_u8(arr, pal_f32, out_colors, lut_in, mode, thr=None, scale=1.0, seed
     return (out, idx) if want_idx else out
 
 
-def error_diffusion_u8(arr, pal_f32, out_colors, lut_in, variant="atkinson", serpentine=False):
+def _taps_of(variant, taps, div):
+    """the named kernel, or an explicit taps=[(dx, dy, weight)], div= in its place"""
+    if taps is None:
+        return ed_kernel(variant)
+    if div is None:
+        raise ValueError("explicit taps need their divisor")
+    return list(taps), div
+
+
+def error_diffusion_u8(arr, pal_f32, out_colors, lut_in, variant="atkinson", serpentine=False, taps=None, div=None,
+                       want_queries=False):
+    """want_queries: also return, per pixel, the float32 point (after the clamp) the KD-tree was asked about, [h, w, 3]."""
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
     h, w, _ = arr.shape
     out = np.empty_like(arr)
-    taps, div = ed_kernel(variant)
+    taps, div = _taps_of(variant, taps, div)
     dx = np.array([t[0] for t in taps], np.int32)
     dy = np.array([t[1] for t in taps], np.int32)
     wq = np.array([t[2] / div for t in taps], np.float64)
-    rc = lib().orc_error_diffusion_u8(_p(arr), _p(out), h, w, _p(pal_f32), pal_f32.shape[0], _p(out_colors),
-                                      _p(lut_in), _p(dx), _p(dy), _p(wq), len(taps), 1 if serpentine else 0)
+    q = np.empty((h, w, 3), np.float32) if want_queries else None
+    if want_queries:
+        rc = lib().orc_error_diffusion_q_u8(_p(arr), _p(out), h, w, _p(pal_f32), pal_f32.shape[0], _p(out_colors),
+                                            _p(lut_in), _p(dx), _p(dy), _p(wq), len(taps), 1 if serpentine else 0, _p(q))
+    else:
+        rc = lib().orc_error_diffusion_u8(_p(arr), _p(out), h, w, _p(pal_f32), pal_f32.shape[0], _p(out_colors),
+                                          _p(lut_in), _p(dx), _p(dy), _p(wq), len(taps), 1 if serpentine else 0)
     if rc != 0:
         raise ValueError("oracle error_diffusion_u8 failed")
-    return out
+    return (out, q) if want_queries else out
 
 
-def error_diffusion_numba_u8(arr, pal_f32, out_colors, lut_in, variant="atkinson", serpentine=False):
+def error_diffusion_numba_u8(arr, pal_f32, out_colors, lut_in, variant="atkinson", serpentine=False, taps=None, div=None):
     """The reference's numba branch (_error_diffusion_numba, dithering_lib.py:213-308) restated in C, typed per numba's
     unification rule: r / g / b are assigned a float32 element AND float64 literals (:239-251), hence float64, and so are
     the distances of the scan and the error that is pushed.  PARITY UNPINNED (fixtures pending): numba cannot be installed
@@ -312,7 +330,7 @@ def error_diffusion_numba_u8(arr, pal_f32, out_colors, lut_in, variant="atkinson
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
     h, w, _ = arr.shape
     out = np.empty_like(arr)
-    taps, div = ed_kernel(variant)
+    taps, div = _taps_of(variant, taps, div)
     dx = np.array([t[0] for t in taps], np.int32)
     dy = np.array([t[1] for t in taps], np.int32)
     wts = np.array([t[2] for t in taps], np.float32)
@@ -447,16 +465,26 @@ def ostromoukhov_coefficients():
     return _OSTRO
 
 
-def var_diffusion_u8(arr, pal_f32, out_colors, lut_in, model, p0=0.0, p1=0.0, serpentine=False, gate=None):
+def var_diffusion_u8(arr, pal_f32, out_colors, lut_in, model, p0=0.0, p1=0.0, serpentine=False, gate=None, coef=None,
+                     want_queries=False):
+    """coef: model 4's float32 [256, 3] table in place of Ostromoukhov's own.  want_queries: also return, per pixel, the
+    float32 point the KD-tree was asked about (clamped by model 4, as it is for the others), [h, w, 3]."""
     arr = np.ascontiguousarray(arr, dtype=np.uint8)
     h, w, _ = arr.shape
     out = np.empty_like(arr)
-    coef = ostromoukhov_coefficients() if model == 4 else None
-    rc = lib().orc_var_diffusion_u8(_p(arr), _p(out), h, w, _p(pal_f32), pal_f32.shape[0], _p(out_colors), _p(lut_in),
-                                    model, float(p0), float(p1), 1 if serpentine else 0, _p(gate), _p(coef))
+    if model == 4:
+        coef = ostromoukhov_coefficients() if coef is None else np.ascontiguousarray(coef, dtype=np.float32).reshape(256, 3)
+    else:
+        coef = None
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.uint8)
+    q = np.empty((h, w, 3), np.float32) if want_queries else None
+    args = (_p(arr), _p(out), h, w, _p(pal_f32), pal_f32.shape[0], _p(out_colors), _p(lut_in),
+            model, float(p0), float(p1), 1 if serpentine else 0, _p(gate), _p(coef))
+    rc = lib().orc_var_diffusion_q_u8(*args, _p(q)) if want_queries else lib().orc_var_diffusion_u8(*args)
     if rc != 0:
         raise ValueError("oracle var_diffusion_u8 failed")
-    return out
+    return (out, q) if want_queries else out
 
 
 def apply_dithering(arr, palette, mode="bayer", params=None, use_gamma=False, y0=0, x0=0):
