@@ -12,8 +12,8 @@
 //   into lanes 0.., and their raw pixels are loaded one block ahead of the walk.  Aligned runs of 4^L indices whose
 //   2^L x 2^L square lies outside the image are skipped in one jump (L >= 3), so off-image indices cost next to nothing.
 //   Walk: the last four in-image errors and their path indices live in registers; the nearest colour comes from the
-//   lane-parallel palette scan of ed_rowserial_kernel (entry l + 64 m in lane l, float32 prefilter with the margin test,
-//   nearest_f64 on near ties with scipy's traversal replay on exact ties).
+//   lane-parallel palette scan of the one-wave-per-frame kernels (ed_nearest.hip.h: wave_nearest -- entry l + 64 m in lane l,
+//   float32 prefilter with the margin test, nearest_f64 on near ties with scipy's traversal replay on exact ties).
 #include "dp_internal.h"
 #include "tree_query.hip.h"
 #include "wave_util.hip.h"
@@ -62,7 +62,6 @@ __global__ __launch_bounds__(64) void riemersma_kernel(const uint8_t *__restrict
     const size_t npx = (size_t)h * (size_t)w;
     const uint8_t *fin = in + (size_t)blockIdx.x * npx * 3;
     uint8_t *fout = out + (size_t)blockIdx.x * npx * 3;
-    const float inf = __int_as_float(0x7f800000);
     const int K = pal.K;
     const uint64_t N = 1ull << (2 * bits);
     const uint32_t uh = (uint32_t)h, uw = (uint32_t)w;
@@ -171,50 +170,8 @@ __global__ __launch_bounds__(64) void riemersma_kernel(const uint8_t *__restrict
             const float o0 = rm_clamp255(__fadd_rn(a0, __fmul_rn(e3x, w3)));  // the newest error: the dependency chain
             const float o1 = rm_clamp255(__fadd_rn(a1, __fmul_rn(e3y, w3)));
             const float o2 = rm_clamp255(__fadd_rn(a2, __fmul_rn(e3z, w3)));
-            // lane-parallel palette scan (as ed_rowserial_kernel)
-            float b0 = inf, b1 = inf;
-            int i0 = lane;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const float da = pc[m].x - o0, db = pc[m].y - o1, dc = pc[m].z - o2;
-                const float d = __fmaf_rn(da, da, __fmaf_rn(db, db, dc * dc));
-                const bool lt0 = d < b0;
-                b1 = lt0 ? b0 : (d < b1 ? d : b1);
-                i0 = lt0 ? lane + 64 * m : i0;
-                b0 = lt0 ? d : b0;
-            }
-            const float B0 = wave_min_to_all(b0);
-            const unsigned long long wm = __ballot(b0 == B0);
-            const int winner = __ffsll((long long)wm) - 1;
-            // the margin test "b1 > b0 * 1.000002" fails iff more than one lane is within it, or a lane's own runner-up is
-            const float lim = B0 * 1.000002f;
-            const unsigned long long close = __ballot(b0 <= lim);
-            const bool near_tie = (close & (close - 1ull)) != 0ull || (M > 1 && __ballot(b1 <= lim) != 0ull);
-            int j = M == 1 ? winner : __builtin_amdgcn_readlane(i0, winner);
-            float cx, cy, cz;
-            uint32_t cw;
-            if (!near_tie) {
-                if (M == 1) {
-                    cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].x), winner));
-                    cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].y), winner));
-                    cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].z), winner));
-                    cw = (uint32_t)__builtin_amdgcn_readlane(__float_as_int(pc[0].w), winner);
-                } else {
-                    const float4 c = s_pal[j];
-                    cx = c.x;
-                    cy = c.y;
-                    cz = c.z;
-                    cw = __float_as_uint(c.w);
-                }
-            } else {  // near tie: float64 scan, scipy's traversal on exact ties
-                j = nearest_f64<CAP>(pal, o0, o1, o2);
-                const float4 c = pal.fcand[j];
-                cx = c.x;
-                cy = c.y;
-                cz = c.z;
-                cw = __float_as_uint(c.w);
-            }
-            if (lane == i) my_c = cw;  // the lane that holds this step's position writes its colour
+            const float4 c = wave_nearest_record<CAP, M>(pal, pc, s_pal, wave_nearest<M>(pc, lane, o0, o1, o2), o0, o1, o2);
+            if (lane == i) my_c = __float_as_uint(c.w);  // the lane that holds this step's position writes its colour
             q0 = q1;
             q1 = q2;
             q2 = q3;
@@ -228,9 +185,9 @@ __global__ __launch_bounds__(64) void riemersma_kernel(const uint8_t *__restrict
             e2x = e3x;
             e2y = e3y;
             e2z = e3z;
-            e3x = __fsub_rn(o0, cx);
-            e3y = __fsub_rn(o1, cy);
-            e3z = __fsub_rn(o2, cz);
+            e3x = __fsub_rn(o0, c.x);
+            e3y = __fsub_rn(o1, c.y);
+            e3z = __fsub_rn(o2, c.z);
         }
         if (lane < cnt) {
             uint8_t *o = fout + ((size_t)row * uw + col) * 3;

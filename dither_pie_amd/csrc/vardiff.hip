@@ -25,235 +25,6 @@ namespace {
 
 __device__ __forceinline__ float clamp255f(const float v) { return v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v); }
 
-// near ties of the float32 scan: float64 scan with the KD-tree's arithmetic, scipy's traversal on exact ties
-template <int CAP>
-__device__ __forceinline__ int nearest_any_f64(const PalDev &pal, const float o0, const float o1, const float o2)
-{
-    int i0 = 0;
-    const int K = pal.K;
-    const double x0 = (double)o0, x1 = (double)o1, x2 = (double)o2;
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
-    double e0 = inf, e1 = inf;
-    for (int j = 0; j < K; ++j) {
-        const double d = sq_dist3(pal.pts + 3 * j, x0, x1, x2);
-        if (d < e0) {
-            e1 = e0;
-            e0 = d;
-            i0 = j;
-        } else if (d < e1) {
-            e1 = d;
-        }
-    }
-    if (e0 == e1 && K > kLeafSize) {
-        double d2[1];
-        int ii[1];
-        tree_query<1, CAP>(pal, x0, x1, x2, d2, ii);
-        i0 = ii[0];
-    }
-    return i0;
-}
-
-template <int CAP>
-__device__ __forceinline__ int nearest_any(const PalDev &pal, const float4 *__restrict__ cand, const float o0,
-                                           const float o1, const float o2)
-{
-    // float32 prefilter with a RELATIVE margin only (values are not clamped here, distances can be tiny -- and need no absolute
-    // margin: each difference c - o is rounded once and the three squares are summed without cancellation, so the float32
-    // distance is within a few 2^-24 of the exact one however small it is; tests/test_gpu_steered_queries.py asks near ties
-    // down to 1e-7 of d0 and exact ties at fractional points, inside and beyond the cube).
-    // `cand` = {x, y, z, out_rgb}: in LDS for the wavefront kernel (broadcast reads, four in flight), global otherwise
-    float b0 = __int_as_float(0x7f800000), b1 = b0;
-    int i0 = 0;
-    const int K = pal.K;
-    auto visit = [&](const float4 c, const int j) {
-        keep_record_whole(c);  // (ds_read_b128 instead of the narrowed ds_read_b96: ed_nearest.hip.h)
-        const float a = c.x - o0, b = c.y - o1, cc = c.z - o2;
-        const float d = __fmaf_rn(a, a, __fmaf_rn(b, b, cc * cc));
-        const bool lt0 = d < b0;
-        b1 = lt0 ? b0 : (d < b1 ? d : b1);
-        i0 = lt0 ? j : i0;
-        b0 = lt0 ? d : b0;
-    };
-    int jj = 0;
-    for (; jj + 4 <= K; jj += 4) {
-        const float4 c0 = cand[jj], c1 = cand[jj + 1], c2 = cand[jj + 2], c3 = cand[jj + 3];
-        visit(c0, jj);
-        visit(c1, jj + 1);
-        visit(c2, jj + 2);
-        visit(c3, jj + 3);
-    }
-    for (; jj < K; ++jj) visit(cand[jj], jj);
-    if (b1 > b0 * 1.000002f) return i0;
-    if (b0 == b1) {
-        const int tied = integer_tie_choice(pal, cand, o0, o1, o2, b0, i0);
-        if (tied >= 0) return tied;
-    }
-    return nearest_any_f64<CAP>(pal, o0, o1, o2);
-}
-
-// Palettes of up to 16 colours, any query point: the key scan of nearest_color_cells (ed_nearest.hip.h) over the list of
-// the point's cell in the EXTENDED 16^3 table (ediff.hip, build_ed_cells: the outermost cells stand for the half-spaces
-// beyond the cube, a point is looked up by its clamped coordinates).  These diffusers do not clamp their values, and a
-// wave nearly always holds a point outside the cube: without this every step scanned the whole palette.
-template <int CAP>
-__device__ __forceinline__ int nearest_ext(const PalDev &pal, const float4 *__restrict__ cand, const uint32_t *__restrict__ ext,
-                                           const float o0, const float o1, const float o2)
-{
-    const int c0 = min(max((int)o0 >> 4, 0), 15), c1 = min(max((int)o1 >> 4, 0), 15), c2 = min(max((int)o2 >> 4, 0), 15);
-    const uint32_t e = ext[c0 | (c1 << 4) | (c2 << 8)];
-    const int n = (int)(e & 15u);
-    if (n <= 7) {
-        const int j1 = (e >> 4) & 15, j2 = (e >> 8) & 15, j3 = (e >> 12) & 15, j4 = (e >> 16) & 15;
-        const float4 q1 = cand[j1], q2 = cand[j2], q3 = cand[j3], q4 = cand[j4];
-        int k1 = ed_key(q1, o0, o1, o2, 1u), k2 = ed_key(q2, o0, o1, o2, 2u), k3 = ed_key(q3, o0, o1, o2, 3u),
-            k4 = ed_key(q4, o0, o1, o2, 4u);
-        int m0 = min(min(k1, k2), k3), m1 = ed_med3(k1, k2, k3);
-        m1 = ed_med3(m0, m1, k4);
-        m0 = min(m0, k4);
-        if (n > 4) {
-            const int j5 = (e >> 20) & 15, j6 = (e >> 24) & 15, j7 = (e >> 28) & 15;
-            const float4 q5 = cand[j5], q6 = cand[j6], q7 = cand[j7];
-            const int k5 = ed_key(q5, o0, o1, o2, 5u), k6 = ed_key(q6, o0, o1, o2, 6u), k7 = ed_key(q7, o0, o1, o2, 7u);
-            m1 = ed_med3(m0, m1, k5);
-            m0 = min(m0, k5);
-            m1 = ed_med3(m0, m1, k6);
-            m0 = min(m0, k6);
-            m1 = ed_med3(m0, m1, k7);
-            m0 = min(m0, k7);
-        }
-        const float f0 = __int_as_float(m0 & ~7), f1 = __int_as_float(m1 & ~7);
-        if (f1 > f0 * 1.000003f) return (int)((e >> (4 * (m0 & 7))) & 15u);
-    }
-    return nearest_any<CAP>(pal, cand, o0, o1, o2);  // long lists, near ties, exact ties: the full scan and its validation
-}
-
-// Palettes of 17..256 colours, any query point: the key scan over the byte list of the point's cell in the extended 16^3 table
-// (host_logic.h: EdTables::ext16 -- the outermost cells are unbounded, a point is looked up by its clamped coordinates).  Lists of
-// up to twelve entries are padded to a multiple of four positions by the builder; longer ones, near ties and exact ties go to the full
-// scan and its validation.  Until round 5 every step of these diffusers scanned the whole palette above 16 colours.
-template <int CAP>
-__device__ __forceinline__ int nearest_ext16(const PalDev &pal, const float4 *__restrict__ cand, const uint4 *__restrict__ ext16,
-                                             const float o0, const float o1, const float o2, const bool inside)
-{
-    const int c0 = min(max((int)o0 >> 4, 0), 15), c1 = min(max((int)o1 >> 4, 0), 15), c2 = min(max((int)o2 >> 4, 0), 15);
-    uint4 blk = ext16[c0 | (c1 << 4) | (c2 << 8)];
-    int n = (int)(blk.x & 255u);
-    if (n == 254) {
-        // an outermost cell with too long a list: down its octree by the CLAMPED integer coordinates (a point beyond the cube falls
-        // into the outer children, which are unbounded on that side); sizes 8, 4, 2, 1 -- a unit child is a list or 255
-        const uint32_t i0 = (uint32_t)min(max((int)o0, 0), 255), i1 = (uint32_t)min(max((int)o1, 0), 255), i2 = (uint32_t)min(max((int)o2, 0), 255);
-        for (int bit = 3; n == 254 && bit >= 0; --bit) {
-            const uint32_t sub = ((i0 >> bit) & 1u) | (((i1 >> bit) & 1u) << 1) | (((i2 >> bit) & 1u) << 2);
-            blk = pal.ed_ext_nodes[(size_t)(blk.x >> 8) * 8 + sub];
-            n = (int)(blk.x & 255u);
-        }
-    }
-    // A lane whose cell has no usable list and whose point lies beyond the cube must scan the whole palette -- and then the wave
-    // executes that scan anyway: all its lanes take it, instead of the scan PLUS the list paths of the others (a palette crowded at a
-    // face of the cube -- any palette under use_gamma, at the dark end -- has such a lane in most waves: 256 colours 59 -> 87 ms per
-    // 1080p frame with the three paths side by side).
-    if (__ballot((n < 1 || n > 15) && !(inside && pal.ed_cells != nullptr)) != 0ull) return nearest_any<CAP>(pal, cand, o0, o1, o2);
-    if (pal.K > 256) {
-        // 257..1024 colours: up to twelve ten-bit entries (ed_nearest.hip.h: ed_wide_entry); the same two stages as below
-        if (n >= 1 && n <= 12) {
-            int m0 = 0x7fffffff, m1 = 0x7fffffff;
-            for (uint32_t g = 0; (int)g < n; g += 4u) {
-                const int j1 = ed_wide_entry(blk, g), j2 = ed_wide_entry(blk, g + 1u), j3 = ed_wide_entry(blk, g + 2u), j4 = ed_wide_entry(blk, g + 3u);
-                const float4 q1 = cand[j1], q2 = cand[j2], q3 = cand[j3], q4 = cand[j4];
-                const int k1 = ed_key16(q1, o0, o1, o2, g), k2 = ed_key16(q2, o0, o1, o2, g + 1u), k3 = ed_key16(q3, o0, o1, o2, g + 2u),
-                          k4 = ed_key16(q4, o0, o1, o2, g + 3u);
-                m1 = ed_med3(m0, m1, k1);
-                m0 = min(m0, k1);
-                m1 = ed_med3(m0, m1, k2);
-                m0 = min(m0, k2);
-                m1 = ed_med3(m0, m1, k3);
-                m0 = min(m0, k3);
-                m1 = ed_med3(m0, m1, k4);
-                m0 = min(m0, k4);
-            }
-            const float f0 = __int_as_float(m0 & ~15), f1 = __int_as_float(m1 & ~15);
-            if (f1 > f0 * 1.000004f) return ed_wide_entry(blk, (uint32_t)m0 & 15u);
-            float b0 = __int_as_float(0x7f800000), b1 = b0;
-            int i0 = 0;
-            for (int i = 0; i < n; ++i) {
-                const int j = ed_wide_entry(blk, (uint32_t)i);
-                const float4 c = cand[j];
-                const float a0 = c.x - o0, a1 = c.y - o1, a2 = c.z - o2;
-                const float d = __fmaf_rn(a0, a0, __fmaf_rn(a1, a1, a2 * a2));
-                const bool lt0 = d < b0;
-                b1 = lt0 ? b0 : (d < b1 ? d : b1);
-                i0 = lt0 ? j : i0;
-                b0 = lt0 ? d : b0;
-            }
-            if (b1 > b0 * 1.000002f) return i0;
-        }
-        if (n > 12 && inside && pal.ed_cells) return nearest_color_cells<CAP, false, CAP == kQueueLarge>(pal, cand, nullptr, o0, o1, o2, nullptr, nullptr, nullptr);
-        return nearest_any<CAP>(pal, cand, o0, o1, o2);
-    }
-    if (n >= 1 && n <= 12) {
-        uint4 b = blk;
-        b.x = __funnelshift_r(b.x, b.y, 8);  // drop the count byte
-        b.y = __funnelshift_r(b.y, b.z, 8);
-        b.z = __funnelshift_r(b.z, b.w, 8);
-        int m0 = 0x7fffffff, m1 = 0x7fffffff;
-        uint32_t tag = 0u;
-        for (int left = n; left > 0; left -= 4, tag += 4u) {
-            const int j1 = (int)(b.x & 255u), j2 = (int)((b.x >> 8) & 255u), j3 = (int)((b.x >> 16) & 255u), j4 = (int)(b.x >> 24);
-            const float4 q1 = cand[j1], q2 = cand[j2], q3 = cand[j3], q4 = cand[j4];
-            const int k1 = ed_key16(q1, o0, o1, o2, tag), k2 = ed_key16(q2, o0, o1, o2, tag + 1u), k3 = ed_key16(q3, o0, o1, o2, tag + 2u),
-                      k4 = ed_key16(q4, o0, o1, o2, tag + 3u);
-            m1 = ed_med3(m0, m1, k1);
-            m0 = min(m0, k1);
-            m1 = ed_med3(m0, m1, k2);
-            m0 = min(m0, k2);
-            m1 = ed_med3(m0, m1, k3);
-            m0 = min(m0, k3);
-            m1 = ed_med3(m0, m1, k4);
-            m0 = min(m0, k4);
-            b.x = b.y;
-            b.y = b.z;
-            b.z = 0u;
-        }
-        const float f0 = __int_as_float(m0 & ~15), f1 = __int_as_float(m1 & ~15);
-        if (f1 > f0 * 1.000004f) {
-            const uint32_t pos = ((uint32_t)m0 & 15u) + 1u;  // byte 1..12 of the block
-            const uint32_t wsel = pos < 4u ? blk.x : (pos < 8u ? blk.y : (pos < 12u ? blk.z : blk.w));
-            return (int)((wsel >> ((pos & 3u) * 8u)) & 255u);
-        }
-    }
-    if (n >= 1 && n <= 15) {
-        // longer lists and near ties of the key scan: the float32 scan of nearest_any over the LISTED entries only (a wave pays for
-        // the slowest of its 64 lanes: sending it through the whole palette for one lane's 13-entry list cost most of the gain)
-        float b0 = __int_as_float(0x7f800000), b1 = b0;
-        int i0 = 0;
-        uint4 b = blk;
-        b.x = __funnelshift_r(b.x, b.y, 8);
-        b.y = __funnelshift_r(b.y, b.z, 8);
-        b.z = __funnelshift_r(b.z, b.w, 8);
-        b.w >>= 8;
-        for (int i = 0; i < n; ++i) {
-            const int j = (int)(b.x & 255u);
-            const float4 c = cand[j];
-            const float a0 = c.x - o0, a1 = c.y - o1, a2 = c.z - o2;
-            const float d = __fmaf_rn(a0, a0, __fmaf_rn(a1, a1, a2 * a2));
-            const bool lt0 = d < b0;
-            b1 = lt0 ? b0 : (d < b1 ? d : b1);
-            i0 = lt0 ? j : i0;
-            b0 = lt0 ? d : b0;
-            b.x = __funnelshift_r(b.x, b.y, 8);
-            b.y = __funnelshift_r(b.y, b.z, 8);
-            b.z = __funnelshift_r(b.z, b.w, 8);
-            b.w >>= 8;
-        }
-        if (b1 > b0 * 1.000002f) return i0;
-    }
-    // a 16-wide cell with more than 15 possible nearest entries (a crowded palette -- e.g. any palette under use_gamma, whose dark
-    // entries crowd the low end of the linear scale): a point INSIDE the cube has the 8^3 lists and their octree (error diffusion's
-    // path); only points beyond the cube in such a cell scan the whole palette
-    if (n > 15 && inside && pal.ed_cells) return nearest_color_cells<CAP, false, false>(pal, cand, nullptr, o0, o1, o2, nullptr, nullptr, nullptr);
-    return nearest_any<CAP>(pal, cand, o0, o1, o2);
-}
-
 struct VarParams {
     int model;
     int serpentine;
@@ -326,7 +97,7 @@ __global__ __launch_bounds__(64) void var_serial_kernel(const uint8_t *__restric
                 o1 = clamp255f(o1);
                 o2 = clamp255f(o2);
             }
-            const int j = nearest_any<CAP>(pal, pal.fcand, o0, o1, o2);
+            const int j = nearest_color<CAP>(pal, pal.fcand, o0, o1, o2);
             float e0 = __fsub_rn(o0, pal.pts_f32[3 * j]), e1 = __fsub_rn(o1, pal.pts_f32[3 * j + 1]),
                   e2 = __fsub_rn(o2, pal.pts_f32[3 * j + 2]);
             float aux = 1.0f;
@@ -379,7 +150,6 @@ __global__ __launch_bounds__(64) void os_rowserial_kernel(const uint8_t *__restr
     const size_t f = blockIdx.x;
     const uint8_t *fin = in + f * (size_t)h * w * 3;
     uint8_t *fout = out + f * (size_t)h * w * 3;
-    const float inf = __int_as_float(0x7f800000);
     const int K = pal.K;
     const bool serp = vp.serpentine != 0;
 
@@ -435,40 +205,9 @@ __global__ __launch_bounds__(64) void os_rowserial_kernel(const uint8_t *__restr
                 a1 = __fadd_rn(a1, __fmul_rn(e1y, w1));
                 a2 = __fadd_rn(a2, __fmul_rn(e1z, w1));
                 const float o0 = clamp255f(a0), o1 = clamp255f(a1), o2 = clamp255f(a2);
-                float b0 = inf, b1 = inf;
-                int i0 = lane;
-#pragma unroll
-                for (int m = 0; m < M; ++m) {
-                    const float da = pc[m].x - o0, db = pc[m].y - o1, dc = pc[m].z - o2;
-                    const float d = __fmaf_rn(da, da, __fmaf_rn(db, db, dc * dc));
-                    const bool lt0 = d < b0;
-                    b1 = lt0 ? b0 : (d < b1 ? d : b1);
-                    i0 = lt0 ? lane + 64 * m : i0;
-                    b0 = lt0 ? d : b0;
-                }
-                const float B0 = wave_min_to_all(b0);
-                const unsigned long long wm = __ballot(b0 == B0);
-                const int winner = __ffsll((long long)wm) - 1;
-                const float lim = B0 * 1.000002f;
-                const unsigned long long close = __ballot(b0 <= lim);
-                const bool near_tie = (close & (close - 1ull)) != 0ull || (M > 1 && __ballot(b1 <= lim) != 0ull);
-                int j = M == 1 ? winner : __builtin_amdgcn_readlane(i0, winner);
-                float cx, cy, cz;
-                uint32_t cw;
-                if (!near_tie && M == 1) {
-                    cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].x), winner));
-                    cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].y), winner));
-                    cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pc[0].z), winner));
-                    cw = (uint32_t)__builtin_amdgcn_readlane(__float_as_int(pc[0].w), winner);
-                } else {
-                    if (near_tie) j = nearest_any_f64<CAP>(pal, o0, o1, o2);
-                    const float4 c = (M > 1 && !near_tie) ? s_pal[j] : pal.fcand[j];
-                    cx = c.x;
-                    cy = c.y;
-                    cz = c.z;
-                    cw = __float_as_uint(c.w);
-                }
-                const float ex = __fsub_rn(o0, cx), ey = __fsub_rn(o1, cy), ez = __fsub_rn(o2, cz);
+                const float4 c = wave_nearest_record<CAP, M>(pal, pc, s_pal, wave_nearest<M>(pc, lane, o0, o1, o2), o0, o1, o2);
+                const uint32_t cw = __float_as_uint(c.w);
+                const float ex = __fsub_rn(o0, c.x), ey = __fsub_rn(o1, c.y), ez = __fsub_rn(o2, c.z);
                 float lum = __fadd_rn(__fadd_rn(__fmul_rn(0.299f, o0), __fmul_rn(0.587f, o1)), __fmul_rn(0.114f, o2));
                 const int row = (int)clamp255f(lum);
                 if (lane == i) {
@@ -811,7 +550,7 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
                     if (model != 4 && coarse) j = nearest_ext<CAP>(pal, s_pal, coarse, o0, o1, o2);
                     else if (model != 4 && pal.ed_ext16) j = nearest_ext16<CAP>(pal, s_pal, pal.ed_ext16, o0, o1, o2, inside);
                     else if (model != 1 && pal.ed_cells && __ballot(!inside) == 0ull) j = nearest_color_cells<CAP, false, CAP == kQueueLarge>(pal, s_pal, coarse, o0, o1, o2, nullptr, nullptr, pal.ed_h4);
-                    else j = nearest_any<CAP>(pal, s_pal, o0, o1, o2);
+                    else j = nearest_color<CAP>(pal, s_pal, o0, o1, o2);
                     const float4 pj = s_pal[j];
                     e0 = __fsub_rn(o0, pj.x);
                     e1 = __fsub_rn(o1, pj.y);

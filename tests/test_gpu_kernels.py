@@ -575,6 +575,31 @@ def test_serpentine_wide_rows_use_the_frame_parallel_kernel(be, orc):
         _assert_same(out, orc.apply_dithering(arr, pal, "error_diffusion", params, False), f"w={w}")
 
 
+@pytest.mark.gpu
+def test_ostromoukhov_serpentine_wide_rows(be, orc):
+    """Ostromoukhov's serpentine scan keeps two error rows of four floats and its 768 coefficients in LDS while
+    (8 w + 768) * 4 + 512 <= 158 * 1024 for palettes of up to 64 colours: w = 4900 needs 160 384 bytes of the 161 792 and
+    runs one wave per frame, w = 5001 needs 163 616 and runs the lane = frame kernel with its error rows in global memory.
+    (Which kernel ran cannot be seen from here and is not asserted.)  Same bytes as the oracle either way, with a whole-palette
+    scan that ends in an exact tie at pixel (0, 0): no error has arrived there, so the query is the pixel itself, the midpoint
+    of two entries of a 40-colour palette -- above the KD-tree's leaf size, so the tie replays the tree.  (The tie is exact
+    without gamma only: under gamma the query is the linearised pixel among linearised entries, which need not tie; those
+    cases check the two kernels' bytes all the same.  The frame's seed is its width.)"""
+    tie_a, tie_b = (100, 100, 100), (104, 100, 100)
+    mid = (102, 100, 100)
+    pal40 = orc.palr(38, 5) + [tie_a, tie_b]
+    d = ((np.array(pal40, np.int64) - np.array(mid, np.int64)) ** 2).sum(1)
+    assert sorted(np.argsort(d, kind="stable")[:2].tolist()) == [38, 39] and d[38] == d[39] and np.sort(d)[2] > d[38]
+    params = {"serpentine": "true"}
+    for w in (4900, 5001):
+        arr = orc.rnd(5, w, w)
+        arr[0, 0] = mid
+        for pal in (orc.palr(16, 3), pal40):
+            for gamma in (False, True):
+                out = _run_case(be, orc, arr, pal, "ostromoukhov", params, gamma)
+                _assert_same(out, orc.apply_dithering(arr, pal, "ostromoukhov", params, gamma), f"w={w} K={len(pal)} gamma={gamma}")
+
+
 def _fuzz_ordered():
     import importlib.util
     import os

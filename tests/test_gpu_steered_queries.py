@@ -25,10 +25,14 @@ from the points the oracle itself reports, that the frames ask what they are mea
       frames hundreds to thousands of units beyond the cube (also adaptive variance with every gate on) in a few-frames shape
       and a persistent one
   palettes of <= 16 colours (nearest_ext, the coarse and expanded lists), 17 .. 256 (nearest_ext16, H4) and 257 .. 1024 (wide lists)
+  (the per-lane searches named here are written once, in csrc/ed_nearest.hip.h: nearest_color, nearest_color_cells, nearest_ext,
+  nearest_ext16, nearest_h4; so is wave_nearest, the per-wave scan of os_rowserial_kernel and riemersma_kernel -- ed_rowserial_kernel
+  has its own copy of that scan in ediff.hip)
 
 Left to the tests they have: the python-arithmetic ed_serial_kernel (test_serpentine_wide_rows_use_the_frame_parallel_kernel)
 and var_serial_kernel, which is reached only by Ostromoukhov's serpentine scan on rows too wide for LDS (about 5000 pixels) or
-at w >= 60000; neither layout here reaches them.
+at w >= 60000; neither layout here reaches them (test_ostromoukhov_serpentine_wide_rows in tests/test_gpu_kernels.py does, with
+an exact tie at its first pixel).
 
 A mismatch is a bug of the library at that point: the failure names the query point, its cell, the kind of target and the rung,
 and the device's and the oracle's palette indices."""
