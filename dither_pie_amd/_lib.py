@@ -188,6 +188,14 @@ _SIGS_CELLS = {
     "dp_cells_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _i, _i, _u32, _vp, _i, _i, _i, _vp]),
 }
 EXPORTS_CELLS = tuple(_SIGS_CELLS)
+# include/ditherpie_hip_voidcluster.h: void-and-cluster rank matrices (blue-noise masks that tile, generated on the device)
+# and the thresholds made of one; a table of its own for the same reason.
+_SIGS_VOIDCLUSTER = {
+    "dp_void_cluster_u16": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "dp_void_cluster_host": (_i, [_vp, _i, _i, _u32, _i]),
+    "dp_thresholds_void_cluster": (_i, [_i, _i, _u32, _i, _vp, C.POINTER(_vp)]),
+}
+EXPORTS_VOIDCLUSTER = tuple(_SIGS_VOIDCLUSTER)
 
 
 def build(force=False):
@@ -232,7 +240,7 @@ def load():
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
-                                          + list(_SIGS_CELLS.items())):
+                                          + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -145,6 +145,15 @@ class Thresholds:
         check(_lib.load().dp_thresholds_blue_noise(int(size), int(seed) & 0xFFFFFFFF, _stream(), C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def void_cluster(cls, h, w, seed, sigma=1.5):
+        """The void-and-cluster matrix of include/ditherpie_hip_voidcluster.h, generated on the device, as thresholds."""
+        h, w, s256 = _void_cluster_args(h, w, sigma)
+        require_gpu()
+        t = C.c_void_p()
+        check(_lib.load().dp_thresholds_void_cluster(h, w, int(seed) & 0xFFFFFFFF, s256, _stream(), C.byref(t)))
+        return cls(t)
+
     def numpy(self):
         out = np.empty(self.shape, np.float32)
         check(_lib.load().dp_thresholds_download(self._h, _np_ptr(out)))
@@ -408,6 +417,74 @@ def dotdiff(frames, pal: Palette, classes, strength256, out=None):
         check(L.dp_dotdiff_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, _np_ptr(c), int(c.shape[0]), int(strength256),
                               _stream()))
     return out.view(frames.shape)
+
+
+VOID_CLUSTER_SIZES = (8, 128)        # h and w of a void-and-cluster matrix (include/ditherpie_hip_voidcluster.h), inclusive
+VOID_CLUSTER_SIGMA256 = (256, 768)   # its sigma in 1/256, inclusive
+
+
+def _void_cluster_args(h, w, sigma):
+    """-> (h, w, sigma256) as ints; ValueError outside the ranges of the header."""
+    lo, hi = VOID_CLUSTER_SIZES
+    for v in (h, w):
+        if not (isinstance(v, (int, np.integer)) and not isinstance(v, bool) and lo <= v <= hi):
+            raise ValueError(f"void-and-cluster: h and w must be integers in {lo} .. {hi}, not {h!r} x {w!r}")
+    try:
+        s256 = int(round(float(sigma) * 256))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"void-and-cluster: sigma must be a number, not {sigma!r}") from None
+    if not VOID_CLUSTER_SIGMA256[0] <= s256 <= VOID_CLUSTER_SIGMA256[1]:
+        raise ValueError(f"void-and-cluster: sigma must lie in {VOID_CLUSTER_SIGMA256[0] / 256} .. {VOID_CLUSTER_SIGMA256[1] / 256}, "
+                         f"not {sigma!r}")
+    return int(h), int(w), s256
+
+
+def _void_cluster_seeds(seeds):
+    try:
+        a = np.atleast_1d(np.asarray(seeds))
+    except Exception:
+        raise ValueError("void-and-cluster: seeds must be integers") from None
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError(f"void-and-cluster: seeds must be an integer or a list of integers, not {seeds!r}")
+    return np.ascontiguousarray(a.astype(np.int64) & 0xFFFFFFFF, np.uint32)
+
+
+def void_cluster_ranks(h, w, seeds, sigma=1.5, device=None, out=None):
+    """Void-and-cluster rank matrices (dp_void_cluster_u16; include/ditherpie_hip_voidcluster.h) generated on the device, one
+    per seed: an int16 tensor [n, h, w], each matrix a permutation of 0 .. h*w-1 (at most 16383).  Launches only, so a call
+    may be captured into a graph; `out`, a contiguous int16 tensor [n, h, w] on the device, is filled instead of a new one."""
+    h, w, s256 = _void_cluster_args(h, w, sigma)
+    sd = _void_cluster_seeds(seeds)
+    require_gpu()
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty((len(sd), h, w), dtype=torch.int16, device=dev)
+    else:
+        if not (out.is_cuda and out.dtype == torch.int16 and tuple(out.shape) == (len(sd), h, w) and out.is_contiguous()):
+            raise ValueError(f"void-and-cluster: out must be a contiguous int16 tensor {(len(sd), h, w)} on the device")
+        dev = out.device
+    with torch.cuda.device(dev), _Launch(dev, None):
+        check(_lib.load().dp_void_cluster_u16(out.data_ptr(), len(sd), _np_ptr(sd), h, w, s256, _stream()))
+    return out
+
+
+def void_cluster_ranks_host(h, w, seed, sigma=1.5):
+    """The same matrix by the library's host statement (dp_void_cluster_host): uint16 [h, w].  No device is needed."""
+    h, w, s256 = _void_cluster_args(h, w, sigma)
+    sd = _void_cluster_seeds(seed)
+    if len(sd) != 1:
+        raise ValueError("void-and-cluster: the host entry point takes one seed")
+    out = np.empty((h, w), np.uint16)
+    check(_lib.load().dp_void_cluster_host(_np_ptr(out), h, w, int(sd[0]), s256))
+    return out
+
+
+def void_cluster_thresholds(ranks):
+    """Step 6 of the header: float32 thresholds of a rank matrix, the centres of min(n, 4096) equal bins of (0, 1)."""
+    r = np.asarray(ranks).astype(np.int64)
+    n = r.size
+    L = min(n, 4096)
+    return ((2 * (r * L // n) + 1).astype(np.float64) / (2 * L)).astype(np.float32)
 
 
 CELL_SIZES = (4, 8, 16)     # cells of dp_cells_u8 are cw x ch pixels, each of these

@@ -272,6 +272,8 @@ int launch_wavelet(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
 int pattern_check_palette(const char *fn, const dp_palette *p);
 int pattern_ensure_table(const dp_palette *pal, hipStream_t s);
 PatDev pattern_snapshot(const dp_palette *pal);
+// void-and-cluster rank matrices (voidcluster.hip): launches only; the arguments are checked by the callers
+int launch_void_cluster(uint16_t *ranks_dev, int n_matrices, const uint32_t *seeds_host, int h, int w, int sigma256, hipStream_t s);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,
                           hipStream_t s);
 }  // namespace dp

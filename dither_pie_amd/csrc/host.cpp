@@ -9,6 +9,7 @@
 #include "dp_internal.h"
 #include "../../include/ditherpie_hip_dotdiff.h"
 #include "../../include/ditherpie_hip_cells.h"
+#include "../../include/ditherpie_hip_voidcluster.h"
 
 namespace dp {
 
@@ -1052,6 +1053,49 @@ int dp_cells_candidates(int K, int colours, uint32_t fixed_mask, const uint16_t 
 {
     CellsPlan plan;
     return cells_plan(K, colours, fixed_mask, groups_host, n_groups, plan);
+}
+
+// include/ditherpie_hip_voidcluster.h: the host statement and the dp_thresholds built from a device-made matrix (the device
+// entry point is in voidcluster.hip)
+int dp_void_cluster_host(uint16_t *ranks_host, int h, int w, uint32_t seed, int sigma256)
+{
+    if (!ranks_host || !vac_args_ok(h, w, sigma256)) {
+        set_error("dp_void_cluster_host: bad argument (a pointer, h and w in %d .. %d, sigma256 in %d .. %d)", kVacMinSize, kVacMaxSize,
+                  kVacMinSigma256, kVacMaxSigma256);
+        return DP_EINVAL;
+    }
+    vac_generate(h, w, seed, sigma256, ranks_host, nullptr);
+    return DP_OK;
+}
+
+int dp_thresholds_void_cluster(int h, int w, uint32_t seed, int sigma256, void *stream, dp_thresholds **out)
+{
+    if (!out || !vac_args_ok(h, w, sigma256)) {
+        set_error("dp_thresholds_void_cluster: bad argument (out, h and w in %d .. %d, sigma256 in %d .. %d)", kVacMinSize, kVacMaxSize,
+                  kVacMinSigma256, kVacMaxSigma256);
+        return DP_EINVAL;
+    }
+    const int n = h * w;
+    float *d = nullptr;
+    DP_HIP(hipMalloc((void **)&d, sizeof(float) * 2 * (size_t)n));
+    // the ranks land in the half of the allocation that the integer form takes afterwards
+    uint16_t *ranks_dev = reinterpret_cast<uint16_t *>(d + n);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = launch_void_cluster(ranks_dev, 1, &seed, h, w, sigma256, s);
+    std::vector<uint16_t> ranks(n);
+    std::vector<float> host(n);
+    if (rc == DP_OK) {
+        hipError_t e = hipMemcpyAsync(ranks.data(), ranks_dev, sizeof(uint16_t) * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) {
+            vac_thresholds(ranks.data(), n, host.data());
+            e = hipMemcpy(d, host.data(), sizeof(float) * n, hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) rc = hip_fail(e, "void-and-cluster download");
+    }
+    if (rc == DP_OK) rc = thresholds_from_device_f32(d, h, w, host.data(), out);
+    if (rc != DP_OK) (void)hipFree(d);
+    return rc;
 }
 
 int dp_profile_enable(int on)

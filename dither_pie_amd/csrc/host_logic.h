@@ -2420,4 +2420,130 @@ inline void cells_perturbation(const int m, const int spread, int8_t *t)
         }
 }
 
+// ---- Void-and-cluster rank matrices (voidcluster.hip, include/ditherpie_hip_voidcluster.h) ---------------------------------
+//
+// Ulichney's generator on a torus in integer arithmetic: the energy of a cell is the sum of W[squared minimum-image distance]
+// over the set cells, W a Gaussian in units of 2^-20 that is zero beyond d2 = D.  What decides a value is a DP_HD function,
+// run by this statement and by the kernel alike; the kernel replaces only the schedule.
+constexpr int kVacMinSize = 8, kVacMaxSize = 128, kVacMinSigma256 = 256, kVacMaxSigma256 = 768;
+constexpr int kVacMaxWeights = 263;   // D + 1 at sigma256 = 768
+
+struct VacWeights {
+    int32_t w[kVacMaxWeights];   // w[d2], 0 beyond D
+    int D;                       // the last squared distance of a non-zero weight
+};
+
+inline bool vac_args_ok(const int h, const int w, const int sigma256)
+{
+    return h >= kVacMinSize && h <= kVacMaxSize && w >= kVacMinSize && w <= kVacMaxSize && sigma256 >= kVacMinSigma256 &&
+           sigma256 <= kVacMaxSigma256;
+}
+
+inline void vac_weights(const int sigma256, VacWeights &W)
+{
+    W.D = -1;
+    for (int d2 = 0; d2 < kVacMaxWeights; ++d2) {
+        const double v = std::floor(std::exp(-((double)d2 * 32768.0) / ((double)sigma256 * (double)sigma256)) * 1048576.0 + 0.5);
+        W.w[d2] = (int32_t)v;
+        if (W.w[d2] > 0) W.D = d2;   // (the weights fall monotonically: nothing follows the first zero)
+    }
+}
+
+DP_HD inline uint32_t vac_mix32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The seed order of cell i.  mix32 is a bijection of uint32, so the keys of distinct cells differ: (key, i) orders like key.
+DP_HD inline uint32_t vac_key(const uint32_t i, const uint32_t seed) { return vac_mix32(vac_mix32(i) ^ seed); }
+
+// a^2 + b^2 of the minimum image between (y, x) and (qy, qx)
+DP_HD inline int vac_d2(const int y, const int x, const int qy, const int qx, const int h, const int w)
+{
+    int a = y > qy ? y - qy : qy - y, b = x > qx ? x - qx : qx - x;
+    a = a < h - a ? a : h - a;
+    b = b < w - b ? b : w - b;
+    return a * a + b * b;
+}
+
+// ranks[h * w]; *rounds (may be null) receives the number of relaxation rounds
+inline void vac_generate(const int h, const int w, const uint32_t seed, const int sigma256, uint16_t *ranks, int *rounds)
+{
+    const int n = h * w;
+    VacWeights W;
+    vac_weights(sigma256, W);
+    int R = 0;
+    while ((R + 1) * (R + 1) <= W.D) ++R;
+    std::vector<int32_t> E((size_t)n, 0);
+    std::vector<uint8_t> on((size_t)n, 0), proto;
+    // the rows and columns a flip at (qy, qx) reaches, each once: the window where it is narrower than the matrix, else all
+    const auto flip = [&](const int q, const int sign) {
+        const int qy = q / w, qx = q - qy * w;
+        const int ny = 2 * R + 1 < h ? 2 * R + 1 : h, nx = 2 * R + 1 < w ? 2 * R + 1 : w;
+        for (int i = 0; i < ny; ++i) {
+            const int y = ny < h ? (qy - R + i + h) % h : i;
+            for (int j = 0; j < nx; ++j) {
+                const int x = nx < w ? (qx - R + j + w) % w : j;
+                const int d2 = vac_d2(y, x, qy, qx, h, w);
+                if (d2 <= W.D) E[(size_t)y * w + x] += sign * W.w[d2];
+            }
+        }
+        on[q] = sign > 0;
+    };
+    const auto tightest = [&]() {   // the set cell of the largest energy, the lowest index on ties
+        int best = -1;
+        for (int i = 0; i < n; ++i)
+            if (on[i] && (best < 0 || E[i] > E[best])) best = i;
+        return best;
+    };
+    const auto emptiest = [&]() {   // the unset cell of the smallest energy, the lowest index on ties
+        int best = -1;
+        for (int i = 0; i < n; ++i)
+            if (!on[i] && (best < 0 || E[i] < E[best])) best = i;
+        return best;
+    };
+    const int n1 = std::max(1, n / 10);
+    std::vector<uint32_t> keys((size_t)n);
+    for (int i = 0; i < n; ++i) keys[i] = vac_key((uint32_t)i, seed);
+    std::vector<uint32_t> sorted(keys);
+    std::nth_element(sorted.begin(), sorted.begin() + (n1 - 1), sorted.end());
+    const uint32_t last = sorted[n1 - 1];
+    for (int i = 0; i < n; ++i)
+        if (keys[i] <= last) flip(i, +1);
+    int r = 0;
+    for (bool done = false; r < 4 * n && !done; ++r) {
+        const int c = tightest();
+        flip(c, -1);
+        const int v = emptiest();
+        flip(v, +1);
+        done = v == c;
+    }
+    if (rounds) *rounds = r;
+    proto = on;
+    for (int k = n1 - 1; k >= 0; --k) {
+        const int c = tightest();
+        flip(c, -1);
+        ranks[c] = (uint16_t)k;
+    }
+    for (int i = 0; i < n; ++i)   // the energy is zero again: integer weights
+        if (proto[i]) flip(i, +1);
+    for (int k = n1; k < n; ++k) {
+        const int v = emptiest();
+        flip(v, +1);
+        ranks[v] = (uint16_t)k;
+    }
+}
+
+// thr[i] = float32((2 floor(rank L / n) + 1) / (2 L)), L = min(n, 4096)
+inline void vac_thresholds(const uint16_t *ranks, const int n, float *thr)
+{
+    const int L = std::min(n, 4096);
+    for (int i = 0; i < n; ++i) thr[i] = (float)((double)(2 * ((int)ranks[i] * L / n) + 1) / (double)(2 * L));
+}
+
 }  // namespace dp

@@ -630,10 +630,44 @@ static int run_orderedplan(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- void-and-cluster rank matrices ------------------------------------------------------------------------------
+static int run_voidcluster(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[4];   // h, w, seed (its bits), sigma256
+        if (fread(head, sizeof(int32_t), 4, f) != 4 || !vac_args_ok(head[0], head[1], head[3])) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const int n = head[0] * head[1];
+        std::vector<uint16_t> ranks((size_t)n);   // exactly as many as the statement may write
+        std::vector<float> thr((size_t)n);
+        int rounds = 0;
+        vac_generate(head[0], head[1], (uint32_t)head[2], head[3], ranks.data(), &rounds);
+        vac_thresholds(ranks.data(), n, thr.data());
+        printf("ranks %d %d", c, rounds);
+        for (int i = 0; i < n; ++i) printf(" %u", (unsigned)ranks[(size_t)i]);
+        printf("\nthr %d", c);
+        for (int i = 0; i < n; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, &thr[(size_t)i], sizeof(bits));
+            printf(" %08x", bits);
+        }
+        printf("\n");
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -643,6 +677,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "pngdyn") return run_pngdeflate(argv[2], atoi(argv[3]), true);
     if (std::string(argv[1]) == "pngfile") return run_pngfile(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "orderedplan") return run_orderedplan(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "voidcluster") return run_voidcluster(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

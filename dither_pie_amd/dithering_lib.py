@@ -84,7 +84,7 @@ __all__ = [
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
     "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "CellPaletteDitherStrategy",
-    "generate_blue_noise",
+    "generate_blue_noise", "generate_void_and_cluster", "VoidAndClusterDitherStrategy",
 ]
 
 
@@ -322,6 +322,12 @@ def _device_thresholds_blue(size, seed):
     return _THRESHOLDS.get_or_make(key, lambda: backend.Thresholds.blue_noise(size, seed))
 
 
+def _device_thresholds_vac(h, w, seed, sigma256):
+    from . import backend
+    key = (_device_index(), "vac", int(h), int(w), int(seed), int(sigma256))
+    return _THRESHOLDS.get_or_make(key, lambda: backend.Thresholds.void_cluster(h, w, seed, sigma256 / 256.0))
+
+
 def prepare_palette(palette, use_gamma):
     """Host-side palette conversion of ImageDitherer.apply_dithering.
 
@@ -479,6 +485,75 @@ class BlueNoiseDitherStrategy(MatrixDitherStrategy):
 
     def __getstate__(self):
         return {"size": self.size, "seed": self.seed, "_matrix": None}
+
+
+def _vac_settings(size, seed, sigma):
+    """(size, seed, sigma) as given to generate_void_and_cluster -> (h, w, seed, sigma256); ValueError outside the ranges."""
+    from . import backend
+    hw = (size, size) if isinstance(size, (int, np.integer)) else tuple(size) if isinstance(size, (tuple, list)) else None
+    if hw is None or len(hw) != 2:
+        raise ValueError(f"void-and-cluster: size must be an integer or (h, w), not {size!r}")
+    if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
+        raise ValueError(f"void-and-cluster: seed must be an integer, not {seed!r}")
+    h, w, s256 = backend._void_cluster_args(hw[0], hw[1], sigma)
+    return h, w, int(seed) & 0xFFFFFFFF, s256
+
+
+def generate_void_and_cluster(size=64, seed: int = 42, sigma: float = 1.5) -> np.ndarray:
+    """A void-and-cluster threshold matrix (Ulichney 1993 on a torus; include/ditherpie_hip_voidcluster.h), float32 [h, w]:
+    blue noise at every grey level, and it tiles.  size is an int or (h, w), each 8 .. 128; sigma 1.0 .. 3.0.  Generated on
+    the device when there is one, by the library's host statement otherwise: the bytes are the same either way."""
+    import torch
+    from . import backend
+    h, w, seed, s256 = _vac_settings(size, seed, sigma)
+    if torch.cuda.is_available():
+        return _device_thresholds_vac(h, w, seed, s256).numpy()
+    return backend.void_cluster_thresholds(backend.void_cluster_ranks_host(h, w, seed, s256 / 256.0))
+
+
+class VoidAndClusterDitherStrategy(MatrixDitherStrategy):
+    """Ordered dithering with a void-and-cluster matrix generated and cached on the device per (size, seed, sigma).  Not in
+    the reference: given to ImageDitherer as dither_mode=<instance>.  Position-only like every matrix mode, so bands, tiles,
+    indexed output and the file writers take it as they take blue noise."""
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            "size": {
+                "type": "int", "default": 64, "min": 8, "max": 128, "label": "Matrix Size",
+                "description": "Size of the void-and-cluster matrix (an integer, or (h, w) in code)",
+            },
+            "seed": {
+                "type": "int", "default": 42, "min": 0, "max": 9999, "label": "Random Seed",
+                "description": "Seed of the initial pattern (different seeds = different matrices)",
+            },
+            "sigma": {
+                "type": "float", "default": 1.5, "min": 1.0, "max": 3.0, "step": 0.1, "label": "Sigma",
+                "description": "Width of the Gaussian that measures voids and clusters, in pixels",
+            },
+        }
+
+    def __init__(self, size=64, seed: int = 42, sigma: float = 1.5):
+        _vac_settings(size, seed, sigma)
+        self.size = size
+        self.seed = seed
+        self.sigma = sigma
+        self._matrix = None
+
+    @property
+    def threshold_matrix(self):
+        if self._matrix is None:
+            self._matrix = generate_void_and_cluster(self.size, self.seed, self.sigma)
+        return self._matrix
+
+    def _thresholds(self):
+        return _device_thresholds_vac(*_vac_settings(self.size, self.seed, self.sigma))
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {"size": self.size, "seed": self.seed, "sigma": self.sigma}
+
+    def __getstate__(self):
+        return {"size": self.size, "seed": self.seed, "sigma": self.sigma, "_matrix": None}
 
 
 class PolkaDotDitherStrategy(MatrixDitherStrategy):
@@ -1441,7 +1516,7 @@ class ImageDitherer:
         unknown mode -> ValueError, unknown parameter -> TypeError from the constructor.  An addition to the reference's
         interface: a BaseDitherStrategy INSTANCE as the mode is returned as it is (dither_params do not apply to it) --
         how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, CellPaletteDitherStrategy,
-        HalftoneDitherStrategy, WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
+        VoidAndClusterDitherStrategy, HalftoneDitherStrategy, WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
         if isinstance(mode, BaseDitherStrategy):
             return mode
         if mode in _OUT_OF_SCOPE:
