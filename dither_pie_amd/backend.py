@@ -40,7 +40,7 @@ class Palette:
     # = seven 4K frames at 256, 0.9 Gpixel at 16) and builds it then -- never more than twice the cost of the better choice,
     # whatever follows.  One image or a GUI preview never builds it; a video does within its first frames.  build_accel() forces
     # it (long-running jobs that know what is coming).
-    ACCEL_BUILD_SECONDS = 0.0035
+    ACCEL_BUILD_SECONDS = 0.0038                 # (3.7-3.9 ms at 256 colours since the scan also keeps the nearest sets of the 8-wide sub-cells)
     ACCEL_BUILD_SECONDS_LARGE = 0.025            # more than 256 colours (128-byte membership masks, deeper tables)
     BRUTE_SECONDS_PER_PIXEL_PER_COLOUR = 2.46e-13
 

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "dp_internal.h"
+#include "ordered_fine.h"
 #include "tree_query.hip.h"
 
 namespace dp {
@@ -45,14 +46,13 @@ constexpr int kExcCap = 1 << 16;  // colours with an outcome outside the codes (
 
 template <int MW, int CAP>  // MW: mask words (32 palette entries each); CAP: traversal queue of the tie queries
 __global__ __launch_bounds__(256) void accel_scan_kernel(const PalDev pal, uint32_t *__restrict__ masks,
-                                                         uint32_t *__restrict__ nmasks, uint32_t *__restrict__ code1,
+                                                         uint32_t *__restrict__ nmasks, uint32_t *__restrict__ nsub, uint32_t *__restrict__ code1,
                                                          uint32_t *__restrict__ code2, uint4 *__restrict__ exc,
                                                          uint32_t *__restrict__ exc_count)
 {
     __shared__ uint32_t s_mask[9][MW];  // [0] the whole cell, [1+s] its 8x8x8 sub-cell s
-    __shared__ uint32_t s_nmask[MW];    // N(cell): the entries that are NEAREST (ties included) to some colour of the cell
-    for (int i = threadIdx.x; i < 9 * MW; i += 256) (&s_mask[0][0])[i] = 0;
-    if (threadIdx.x < MW) s_nmask[threadIdx.x] = 0;
+    __shared__ uint32_t s_nmask[9][MW];  // N: the entries that are NEAREST (ties included) to some colour of the cell / sub-cell
+    for (int i = threadIdx.x; i < 9 * MW; i += 256) (&s_mask[0][0])[i] = (&s_nmask[0][0])[i] = 0;
     __syncthreads();
     const int cell = blockIdx.x;
     const int rc = cell >> 8, gc = (cell >> 4) & 15, bc = cell & 15;
@@ -94,14 +94,18 @@ __global__ __launch_bounds__(256) void accel_scan_kernel(const PalDev pal, uint3
             }
         }
         // the nearest set: everything at the smallest distance
-        atomicOr(&s_nmask[c0 >> 5], 1u << (c0 & 31));
-        if (K > 1 && d1 == d0) atomicOr(&s_nmask[c1 >> 5], 1u << (c1 & 31));
-        if (K > 2 && d2 == d0) atomicOr(&s_nmask[c2 >> 5], 1u << (c2 & 31));
+        auto mark_near = [&](int j) {
+            atomicOr(&s_nmask[0][j >> 5], 1u << (j & 31));
+            atomicOr(&s_nmask[sub][j >> 5], 1u << (j & 31));
+        };
+        mark_near(c0);
+        if (K > 1 && d1 == d0) mark_near(c1);
+        if (K > 2 && d2 == d0) mark_near(c2);
         if (K > 3 && d3 == d0) {
             for (int j = 0; j < K; ++j) {
                 const int dot = (int)__builtin_amdgcn_udot4(x4, pal.p4[j], 0u, false);
                 const int dj = (pal.nkey[j] - (dot << (kIdxBits + 1))) >> kIdxBits;
-                if (dj <= d0) atomicOr(&s_nmask[j >> 5], 1u << (j & 31));
+                if (dj <= d0) mark_near(j);
             }
         }
         if (K < 2) continue;
@@ -144,7 +148,8 @@ __global__ __launch_bounds__(256) void accel_scan_kernel(const PalDev pal, uint3
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 9 * MW; i += 256) masks[(size_t)cell * 9 * MW + i] = (&s_mask[0][0])[i];
-    if (threadIdx.x < MW) nmasks[(size_t)cell * MW + threadIdx.x] = s_nmask[threadIdx.x];
+    if (threadIdx.x < MW) nmasks[(size_t)cell * MW + threadIdx.x] = s_nmask[0][threadIdx.x];
+    for (int i = threadIdx.x; i < 8 * MW; i += 256) nsub[(size_t)cell * 8 * MW + i] = (&s_nmask[1][0])[i];
 }
 
 
@@ -402,10 +407,15 @@ int run_box_kernel(const std::vector<B> &boxes, std::vector<uint32_t> &bm, Launc
 
 // Builds the accelerator for an integer palette whose output colours equal its search colours.
 // On success fills the accel fields of `dev` and returns the device allocation through *blob_out.
-int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_out, size_t *blob_bytes)
+// fine_masks / fine_dev: for palettes that can have a fine table (build_fine below), the sets of the 8-wide cells and the table's
+// place in the blob; left empty otherwise.
+int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_out, size_t *blob_bytes, std::vector<uint32_t> *fine_masks,
+                uint32_t **fine_dev)
 {
     *blob_out = nullptr;
     *blob_bytes = 0;
+    fine_masks->clear();
+    *fine_dev = nullptr;
     const int K = dev.K;
     constexpr size_t kCodeWords = (size_t)1 << 20;  // 2^24 colours x 2 bits (k=1); the k=2 table has twice as many
     uint32_t *d_masks = nullptr;
@@ -417,8 +427,9 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
     //         4-entry table [2 x 4096 words]
     //         | the flat lists of their split cells [2 x kWideCap x kWideList words]
     //         | the compact (one byte per entry) copy of the crowded table [kCompactMaxWords]
+    //         | the fine table as ordered_fine_kernel stages it [kLeanTabBytes at most]
     const size_t bytes = sizeof(uint32_t) * (3 * kCodeWords + 2 * kTabMaxWords + kTabCapWords) + sizeof(uint4) * kExcCap + 16 + 768 +
-                         sizeof(uint32_t) * (2 * kCells + 2 * kWideCap * kWideList + kCompactMaxWords);
+                         sizeof(uint32_t) * (2 * kCells + 2 * kWideCap * kWideList + kCompactMaxWords) + kLeanTabBytes;
     DP_HIP(hipMalloc((void **)&blob, bytes));
     struct DevFree {  // frees the scan masks on every way out
         void *p = nullptr;
@@ -427,9 +438,9 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
             if (p) (void)hipFree(p);
         }
     } masks_guard;
-    hipError_t e = hipMalloc((void **)&d_masks, sizeof(uint32_t) * kCells * 10 * mw);  // T masks [9] + N mask [1] per cell
+    hipError_t e = hipMalloc((void **)&d_masks, sizeof(uint32_t) * kCells * 18 * mw);  // T masks [9] + N masks [1 + 8] per cell
     masks_guard.p = d_masks;
-    uint32_t *d_nmasks = d_masks + (size_t)kCells * 9 * mw;
+    uint32_t *d_nmasks = d_masks + (size_t)kCells * 9 * mw, *d_nsub = d_nmasks + (size_t)kCells * mw;
     if (e == hipSuccess) e = hipMemset(blob, 0, sizeof(uint32_t) * 3 * kCodeWords);
     if (e != hipSuccess) {
         (void)hipFree(blob);
@@ -445,14 +456,14 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
         (void)hipFree(blob);
         return hip_fail(e, "accelerator allocation");
     }
-#define DP_SCAN(MW, C) hipLaunchKernelGGL((accel_scan_kernel<MW, C>), dim3(kCells), dim3(256), 0, 0, dev, d_masks, d_nmasks, code1, code2, d_exc, d_exc_count)
+#define DP_SCAN(MW, C) hipLaunchKernelGGL((accel_scan_kernel<MW, C>), dim3(kCells), dim3(256), 0, 0, dev, d_masks, d_nmasks, d_nsub, code1, code2, d_exc, d_exc_count)
     if (mw == 8) {
         if (big_q) DP_SCAN(8, kQueueLarge); else DP_SCAN(8, kQueueSmall);
     } else {
         if (big_q) DP_SCAN(32, kQueueLarge); else DP_SCAN(32, kQueueSmall);
     }
 #undef DP_SCAN
-    std::vector<uint32_t> masks((size_t)kCells * 9 * mw), nmasks((size_t)kCells * mw);
+    std::vector<uint32_t> masks((size_t)kCells * 9 * mw), nmasks((size_t)kCells * 9 * mw);  // (nmasks: the cells, then their sub-cells)
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(masks.data(), d_masks, sizeof(uint32_t) * masks.size(), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(nmasks.data(), d_nmasks, sizeof(uint32_t) * nmasks.size(), hipMemcpyDeviceToHost);
@@ -698,6 +709,23 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
                 fprintf(stderr, "accel K=%d: compact table over %s cells: %zu bytes\n", K, from_warp ? "warped" : "plain", ct.size() * 4);
         }
     }
+    // The fine table (build_fine below) is for the palettes the plain lean kernel serves on 8-entry blocks: keep the sets of the
+    // 8^3 sub-cells the scan has just made, by fine cell -- T masks, then N masks -- for whoever builds it.  The deferred pixels of
+    // ordered_fine_kernel read the index-ordered table in global memory, so that one must be whole.
+    dev.fine_tab = nullptr;
+    dev.fine_words = dev.fine_win = dev.fine_wide = 0;
+    if (have8 && !st.too_big && !use4 && wbw == 0 && !dev.adapt && mw == 8 && K >= kWideList && !exp_env("DP_NO_FINE")) {
+        fine_masks->resize((size_t)2 * kFineCells * mw);
+        uint32_t *ftm = fine_masks->data(), *fnm = ftm + (size_t)kFineCells * mw;
+        for (int cell = 0; cell < kCells; ++cell)
+            for (int sub = 0; sub < 8; ++sub) {
+                const int rc = cell >> 8, gc = (cell >> 4) & 15, bc = cell & 15;
+                const size_t fc = (size_t)fine_cell(rc * 16 + ((sub >> 2) & 1) * 8, gc * 16 + ((sub >> 1) & 1) * 8, bc * 16 + (sub & 1) * 8);
+                std::copy_n(&masks[((size_t)cell * 9 + 1 + sub) * mw], mw, &ftm[fc * mw]);
+                std::copy_n(&nmasks[((size_t)kCells + (size_t)cell * 8 + sub) * mw], mw, &fnm[fc * mw]);
+            }
+        *fine_dev = d_wide4 + kWideCap * kWideList + kCompactMaxWords;
+    }
     if (have8 && !st.too_big) {
         e = hipMemcpy(d_tab, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
@@ -749,6 +777,28 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
     }
     *blob_out = blob;
     *blob_bytes = bytes;
+    return DP_OK;
+}
+
+// The fine table of ordered_fine_kernel (host_logic.h: fine_pack): windows of 4 + 2 candidates shared by the 8-wide cells, packed
+// from the sets build_accel kept (eight mask words per cell) and uploaded to its place in the accelerator's blob.  Fills the fine
+// fields of `dev`; a palette whose sets or table exceed the budget (ordered_fine.h) simply gets none.
+int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev)
+{
+    constexpr int mw = 8;
+    FineTable ft;
+    fine_pack(fine_masks.data(), fine_masks.data() + (size_t)kFineCells * mw, mw, dev.K, p4_host, fine_table_fits, ft);
+    if (exp_env("DP_DEBUG_ACCEL"))
+        fprintf(stderr, "accel K=%d: fine table: %s, %d windows, %d wide cells, %lld bytes\n", dev.K, ft.ok ? "yes" : "no", ft.n_win, ft.n_wide,
+                (long long)fine_table_bytes(ft.n_win, ft.n_wide));
+    if (!ft.ok) return DP_OK;
+    const std::vector<uint32_t> im = ft.lds_image();
+    const hipError_t e = hipMemcpy(fine_dev, im.data(), sizeof(uint32_t) * im.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "accelerator upload (fine table)");
+    dev.fine_tab = fine_dev;
+    dev.fine_words = (int)im.size();
+    dev.fine_win = ft.n_win;
+    dev.fine_wide = ft.n_wide;
     return DP_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -91,6 +92,11 @@ struct PalDev {
     const uint32_t *comp_tab;
     int comp_words;             // (4096 + 8 * nodes) * 2
     int comp_warp;              // its cells are the warped ones (warp_lut)
+    // uncrowded palettes on the plain 8-entry table: candidate windows shared by the 32^3 cells of 8 colours a side, as
+    // ordered_fine_kernel copies them to LDS (host_logic.h: FineTable::lds_image); nullptr when absent
+    const uint32_t *fine_tab;
+    int fine_words;             // words of the image
+    int fine_win, fine_wide;    // its windows (4 + 2 entries each) and the flat lists of its wide cells
     int n_split;
     int n_slow_blocks;
     int n_split_cells;          // 16^3 cells of cell_tab that are split (a palette crowded into few cells has many)
@@ -192,6 +198,13 @@ struct dp_palette {
     // dp_pattern_u8 / dp_pattern_prepare with the palette under build_mu and published under dev_mu like `dev`
     dp::PatDev pat;
     void *pat_blob;    // the one allocation behind `pat` (may be null); freed by dp_palette_destroy
+    // the fine table of ordered_fine_kernel (accel.hip: build_fine) is packed at the first matrix-mode call that can use it
+    // (host.cpp: ensure_fine_table; 4 ms at 256 colours, outside the accelerator's own build) from the sets of the
+    // 8-wide cells that build_accel's scan left here: T masks, then N masks, [2][kFineCells][8]; empty when the palette gets
+    // none or once it is built
+    std::vector<uint32_t> fine_masks;
+    uint32_t *fine_dev;              // its place in accel_blob
+    std::atomic<bool> fine_pending;  // fine_masks is waiting (read without build_mu by every matrix-mode call)
 };
 
 struct dp_thresholds {
@@ -216,7 +229,9 @@ void prof_end(ProfMark *m, hipStream_t s);
 
 // launchers (defined in the .hip files)
 namespace dp {
-int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_out, size_t *blob_bytes);
+int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_out, size_t *blob_bytes, std::vector<uint32_t> *fine_masks,
+                uint32_t **fine_dev);
+int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev);
 int build_accel_float(PalDev &dev, const float *pal_f32, const uint8_t *lut_host, void **blob_out, size_t *blob_bytes);
 int build_ed_cells(PalDev &dev, const double *pts_host, void **blob_out);
 int build_ed_ext(PalDev &dev, const double *pts_host, void **blob_out);   // the unclamped diffusers' extended lists (ediff.hip)

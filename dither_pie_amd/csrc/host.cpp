@@ -261,6 +261,8 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     p->ext_tried = false;
     p->pat = dp::PatDev{nullptr, nullptr, nullptr, 0, 0};   // the pattern-dither table: built when first needed (pattern.hip)
     p->pat_blob = nullptr;
+    p->fine_dev = nullptr;
+    p->fine_pending = false;
     *out = p;
     return DP_OK;
 }
@@ -311,6 +313,25 @@ static int ensure_ed_ext(const dp_palette *pal_c)
     return DP_OK;
 }
 
+// The fine table of ordered_fine_kernel: packed (4 ms at 256 colours) at the first matrix-mode call with integer thresholds after
+// the accelerator was built, so that nearest-only, IGN and diffusion users never pay for it and the accelerator's build stays
+// what it was.  Not inside a stream capture: the upload is a copy.
+static int ensure_fine_table(const dp_palette *pal_c, hipStream_t s)
+{
+    dp_palette *p = const_cast<dp_palette *>(pal_c);
+    std::lock_guard<std::mutex> lock(p->build_mu);
+    if (!p->fine_pending.load()) return DP_OK;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return DP_OK;
+    p->fine_pending = false;
+    dp::PalDev d = snapshot(p);
+    const int rc = build_fine(d, p->p4_host, p->fine_masks, p->fine_dev);
+    std::vector<uint32_t>().swap(p->fine_masks);
+    if (rc != DP_OK) return rc;
+    publish(p, d);
+    return DP_OK;
+}
+
 void dp_palette_destroy(dp_palette *p)
 {
     if (!p) return;
@@ -351,8 +372,9 @@ int dp_palette_build_accel(dp_palette *p)
         rc = build_accel_float(d, p->pal_host.data(), p->lut_host.empty() ? nullptr : p->lut_host.data(), &p->accel_blob,
                                &p->accel_bytes);
     else  // cell lists + tie codes: integer palettes whose output bytes are the palette colours themselves
-        rc = build_accel(d, p->p4_host, &p->accel_blob, &p->accel_bytes);
+        rc = build_accel(d, p->p4_host, &p->accel_blob, &p->accel_bytes, &p->fine_masks, &p->fine_dev);
     if (rc == DP_OK) publish(p, d);
+    if (rc == DP_OK && !p->fine_masks.empty()) p->fine_pending = true;
     return rc;
 }
 
@@ -585,6 +607,10 @@ int dp_ordered_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
         set_error("dp_ordered_u8: workspace too small or misaligned (need %zu bytes, 16-byte aligned)",
                   dp_ordered_workspace_bytes(n_frames, h, w));
         return DP_EWORKSPACE;
+    }
+    if (mode == DP_MODE_MATRIX && thr->dev.mpad && pal->fine_pending.load(std::memory_order_relaxed)) {
+        const int rc = ensure_fine_table(pal, (hipStream_t)stream);
+        if (rc != DP_OK) return rc;
     }
     return launch_ordered(in_dev, out_dev, n_frames, h, w, y0, x0, snapshot(pal), mode, thr ? &thr->dev : nullptr,
                           ign_scale, ign_seed, workspace_dev, workspace_bytes, (hipStream_t)stream);

@@ -491,6 +491,224 @@ inline int entries_in_split_cells(const std::vector<uint32_t> &tab, const int bw
 
 
 // ---------------------------------------------------------------------------------------------
+// The fine table of ordered_fine_kernel (ordered.hip): candidate WINDOWS shared by the 32^3 cells of 8 colours a side.
+//
+// On 8-wide cells the sets are short -- palr(256,7): a nearest set N above 4 entries in 0.8 % of the cells, a set T (everything
+// up to the second distance) above 6 in 0.5 % -- so a nearest-only slot of the kernel ranks 4 candidates and a full slot 6.  A
+// direct table (32768 x 24 bytes) does not fit LDS, but a block may hold ANY real entry besides the cell's own (see make_block),
+// so many cells share one block: a window is a quad A of four and a pair B of two palette entries, six distinct ones, and
+// serves every cell with N inside A and T inside A + B.  Cells whose sets are longer are WIDE: they map to the reserved window
+// 0 (six times entry 0: its keys tie, so the kernel defers the pixel without a test of its own) and their whole T sits in a
+// flat list of kWideList entries in index order, as for the split cells of the fast kernel.
+// Cells are numbered r>>3 | (g>>3)<<5 | (b>>3)<<10.
+// ---------------------------------------------------------------------------------------------
+constexpr int kFineCells = 32 * 32 * 32;
+constexpr int kFineQuad = 4, kFineWindow = 6;  // entries of A, of A + B
+constexpr int kFineIds = kWideCap;             // the ascending cell numbers of the wide cells, padded to this many with 0xffff
+
+inline int fine_cell(const int r, const int g, const int b) { return (r >> 3) | ((g >> 3) << 5) | ((b >> 3) << 10); }
+
+struct FineTable {
+    bool ok = false;             // false: no fine table for this palette (a set above kWideList, too many wide cells or windows)
+    int n_win = 0, n_wide = 0;   // windows (the reserved one included), wide cells
+    std::vector<uint16_t> off;   // [kFineCells] the window of the cell; 0: a wide cell
+    std::vector<uint32_t> quad;  // [n_win][4] A: packed colours
+    std::vector<uint32_t> pair;  // [n_win][2] B
+    std::vector<uint16_t> win_idx;   // [n_win][6] the same entries as palette indices
+    std::vector<uint16_t> wide_cell; // [n_wide] ascending
+    std::vector<uint32_t> wide;      // [n_wide][kWideList] T(cell) in index order, padded with further entries
+    std::vector<uint16_t> wide_idx;  // ... as palette indices
+    // the image the kernel copies to LDS: A | wide lists | B | off (two per word) | wide cell numbers (kFineIds, two per word)
+    std::vector<uint32_t> lds_image() const
+    {
+        std::vector<uint32_t> im;
+        im.reserve(quad.size() + wide.size() + pair.size() + kFineCells / 2 + kFineIds / 2);
+        im.insert(im.end(), quad.begin(), quad.end());
+        im.insert(im.end(), wide.begin(), wide.end());
+        im.insert(im.end(), pair.begin(), pair.end());
+        for (int c = 0; c < kFineCells; c += 2) im.push_back((uint32_t)off[c] | ((uint32_t)off[c + 1] << 16));
+        for (int i = 0; i < kFineIds; i += 2) {
+            const uint32_t lo = i < n_wide ? wide_cell[i] : 0xffffu, hi = i + 1 < n_wide ? wide_cell[i + 1] : 0xffffu;
+            im.push_back(lo | (hi << 16));
+        }
+        return im;
+    }
+};
+
+// tmask / nmask: [kFineCells][mw] membership of T(cell) / N(cell), cells numbered by fine_cell.  fits(n_win, n_wide): whether
+// the caller's LDS budget admits a table of that size (ordered_fine.h).  Deterministic and single-threaded: the cells are taken
+// longest T first, then longest N, then by number; a cell whose pair (N, T) was met before takes that cell's window; any other
+// goes into the window -- among those that hold its rarest member of N in their quad -- that needs the fewest new entries (the
+// lowest numbered among equals), or into a new window when none takes it.  Sets are 256-bit masks throughout (K <= 256).
+template <class Fits>
+void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const int K, const std::vector<uint32_t> &coord4, Fits fits,
+               FineTable &ft)
+{
+    ft = FineTable{};
+    if (K < kWideList || K > 256 || K > 32 * mw) return;
+    struct Mask {
+        uint64_t w[4];
+        int count() const  // (a handful of members: clearing them one by one beats a population count without hardware support)
+        {
+            int n = 0;
+            for (int i = 0; i < 4; ++i)
+                for (uint64_t bits = w[i]; bits; bits &= bits - 1ull) ++n;
+            return n;
+        }
+        bool any() const { return (w[0] | w[1] | w[2] | w[3]) != 0; }
+        bool operator==(const Mask &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
+        Mask without(const Mask &o) const { return Mask{{w[0] & ~o.w[0], w[1] & ~o.w[1], w[2] & ~o.w[2], w[3] & ~o.w[3]}}; }
+        Mask with(const Mask &o) const { return Mask{{w[0] | o.w[0], w[1] | o.w[1], w[2] | o.w[2], w[3] | o.w[3]}}; }
+        void set(const int j) { w[j >> 6] |= 1ull << (j & 63); }
+    };
+    auto load = [&](const uint32_t *m) {  // the members below K
+        Mask r{{0, 0, 0, 0}};
+        for (int wi = 0; wi < mw && wi < 8; ++wi) r.w[wi >> 1] |= (uint64_t)m[wi] << (32 * (wi & 1));
+        for (int j = K; j < 256; ++j) r.w[j >> 6] &= ~(1ull << (j & 63));
+        return r;
+    };
+    // calls f(j) for the members in ascending order
+    auto each = [](const Mask &m, auto f) {
+        for (int wi = 0; wi < 4; ++wi)
+            for (uint64_t bits = m.w[wi]; bits; bits &= bits - 1ull) f(64 * wi + __builtin_ctzll(bits));
+    };
+    ft.off.assign(kFineCells, 0);
+    std::vector<Mask> tms(kFineCells), nms(kFineCells);
+    constexpr int kClasses = (kFineWindow + 1) * (kFineQuad + 1);
+    int class_count[kClasses + 1] = {0};
+    std::vector<uint8_t> cls(kFineCells, 0xff);  // 0xff: wide
+    for (int cell = 0; cell < kFineCells; ++cell) {
+        const Mask tm = tms[cell] = load(tmask + (size_t)cell * mw), nm = nms[cell] = load(nmask + (size_t)cell * mw);
+        const int nt = tm.count(), nn = nm.count();
+        if (nt > kWideList) return;  // not even a flat list holds it
+        if (nn > kFineQuad || nt > kFineWindow) {
+            if (ft.n_wide == kFineIds || !fits(1, ft.n_wide + 1)) return;
+            ++ft.n_wide;
+            ft.wide_cell.push_back((uint16_t)cell);
+            // the whole list, padded with the lowest unused indices (any real entry is harmless), in index order
+            Mask list = tm;
+            for (int j = 0, n = nt; n < kWideList; ++j)
+                if (!(tm.w[j >> 6] >> (j & 63) & 1ull)) {
+                    list.set(j);
+                    ++n;
+                }
+            each(list, [&](const int j) {
+                ft.wide_idx.push_back((uint16_t)j);
+                ft.wide.push_back(coord4[j]);
+            });
+            continue;
+        }
+        cls[cell] = (uint8_t)((kFineWindow - nt) * (kFineQuad + 1) + (kFineQuad - nn));  // longest T first, then longest N
+        ++class_count[cls[cell] + 1];
+    }
+    for (int c = 0; c < kClasses; ++c) class_count[c + 1] += class_count[c];
+    std::vector<int> order(class_count[kClasses]);
+    for (int cell = 0; cell < kFineCells; ++cell)
+        if (cls[cell] != 0xff) order[class_count[cls[cell]]++] = cell;
+    struct Win {
+        Mask a, ab;  // the quad, the whole window
+        int na, nb;
+    };
+    std::vector<Win> wins(1, Win{Mask{{0, 0, 0, 0}}, Mask{{0, 0, 0, 0}}, kFineQuad, kFineWindow - kFineQuad});  // (window 0: reserved)
+    std::vector<std::vector<int>> holds(K);       // entry -> the windows that hold it in their quad
+    constexpr int kSlots = 1 << 16;               // the pairs met so far: open addressing, cell number + 1
+    std::vector<int> seen(kSlots, 0);
+    for (const int cell : order) {
+        const Mask &nm = nms[cell], &tm = tms[cell];
+        uint64_t h = 0x9e3779b97f4a7c15ull;
+        for (int wi = 0; wi < 4; ++wi) h = (h ^ nm.w[wi]) * 0xff51afd7ed558ccdull, h = (h ^ (h >> 29) ^ tm.w[wi]) * 0xc4ceb9fe1a85ec53ull;
+        int slot = (int)((h >> 40) & (kSlots - 1));
+        bool met = false;
+        for (; seen[slot] != 0; slot = (slot + 1) & (kSlots - 1))
+            if (nms[seen[slot] - 1] == nm && tms[seen[slot] - 1] == tm) {
+                ft.off[cell] = ft.off[seen[slot] - 1];
+                met = true;
+                break;
+            }
+        if (met) continue;
+        seen[slot] = cell + 1;
+        const Mask rest = tm.without(nm);
+        int best = -1, best_cost = kFineWindow + 1;
+        // (the windows that hold the member of N with the fewest windows: every window that holds all of N is among them)
+        int rarest = -1;
+        each(nm, [&](const int j) {
+            if (rarest < 0 || holds[j].size() < holds[rarest].size()) rarest = j;
+        });
+        {
+            for (const int wi : holds[rarest]) {
+                const Win &w = wins[wi];
+                // what the window would need: nothing of N may sit in its pair, N must find room in the quad, the rest anywhere
+                const Mask need_a = nm.without(w.a), need_r = rest.without(w.ab);
+                int c = 0;
+                if (need_a.any() || need_r.any()) {
+                    if (w.na + w.nb == kFineWindow || need_a.without(w.ab).w[0] != need_a.w[0] || need_a.without(w.ab).w[1] != need_a.w[1] ||
+                        need_a.without(w.ab).w[2] != need_a.w[2] || need_a.without(w.ab).w[3] != need_a.w[3])
+                        continue;
+                    const int add_a = need_a.count();
+                    if (w.na + add_a > kFineQuad) continue;
+                    const int add_r = need_r.count();
+                    if (add_r > (kFineQuad - w.na - add_a) + (kFineWindow - kFineQuad - w.nb)) continue;
+                    c = add_a + add_r;
+                }
+                if (c < best_cost || (c == best_cost && wi < best)) {
+                    best = wi;
+                    best_cost = c;
+                }
+            }
+        }
+        if (best < 0) {
+            if (wins.size() == 0xffffu || !fits((int)wins.size() + 1, ft.n_wide)) return;
+            best = (int)wins.size();
+            wins.push_back(Win{Mask{{0, 0, 0, 0}}, Mask{{0, 0, 0, 0}}, 0, 0});
+        }
+        Win &w = wins[best];
+        each(nm.without(w.a), [&](const int j) {
+            w.a.set(j);
+            w.ab.set(j);
+            ++w.na;
+            holds[j].push_back(best);
+        });
+        each(rest.without(w.ab), [&](const int j) {  // the rest of T: into the pair while it has room (the quad's places are the scarce ones)
+            w.ab.set(j);
+            if (w.nb < kFineWindow - kFineQuad) {
+                ++w.nb;
+            } else {
+                w.a.set(j);
+                ++w.na;
+                holds[j].push_back(best);
+            }
+        });
+        ft.off[cell] = (uint16_t)best;
+    }
+    // free places: the lowest indices the window does not hold yet; the reserved window: entry 0 six times
+    ft.n_win = (int)wins.size();
+    ft.win_idx.assign((size_t)ft.n_win * kFineWindow, 0);
+    for (int wi = 1; wi < ft.n_win; ++wi) {
+        Win &w = wins[wi];
+        for (int j = 0; w.na + w.nb < kFineWindow; ++j)
+            if (!(w.ab.w[j >> 6] >> (j & 63) & 1ull)) {
+                w.ab.set(j);
+                if (w.na < kFineQuad) w.a.set(j), ++w.na;
+                else ++w.nb;
+            }
+        uint16_t *e = &ft.win_idx[(size_t)wi * kFineWindow];
+        int pa = 0, pb = kFineQuad;
+        each(w.a, [&](const int j) { e[pa++] = (uint16_t)j; });
+        each(w.ab.without(w.a), [&](const int j) { e[pb++] = (uint16_t)j; });
+    }
+    ft.quad.resize((size_t)ft.n_win * kFineQuad);
+    ft.pair.resize((size_t)ft.n_win * (kFineWindow - kFineQuad));
+    for (int wi = 0; wi < ft.n_win; ++wi)
+        for (int p = 0; p < kFineWindow; ++p) {
+            const uint32_t c = coord4[ft.win_idx[(size_t)wi * kFineWindow + p]];
+            if (p < kFineQuad) ft.quad[(size_t)wi * kFineQuad + p] = c;
+            else ft.pair[(size_t)wi * (kFineWindow - kFineQuad) + p - kFineQuad] = c;
+        }
+    ft.ok = true;
+}
+
+
+// ---------------------------------------------------------------------------------------------
 // Candidate tables of the diffusion kernels (ediff.hip / vardiff.hip): everything that happens on the host between the
 // download of ed_cells_kernel's geometric lists and the upload of the finished tables.
 // ---------------------------------------------------------------------------------------------

@@ -32,6 +32,13 @@
 //   host_xxx orderedplan <cases.bin> <n>   the kernel choice of the ordered dither (ordered_plan.h: plan_ordered): n records of
 //                                     one OrderedFacts and one OrderedSwitches (int32 fields in declaration order); prints one
 //                                     plan per line (compared with tests/ordered_plan_ref.py by the test)
+//   host_xxx finepack <pal.u8> <K> <out.bin>   the fine table of the ordered dither (host_logic.h: fine_pack) from brute-force
+//                                     sets N and T of the 32^3 cells (what accel_scan_kernel computes on the device) within the
+//                                     budget of ordered_fine.h; writes int32 ok, n_win, n_wide, image words, then off, the windows
+//                                     and the wide lists as palette indices (uint16), then quads, pairs, lists and the LDS image
+//                                     (uint32) for tests/test_ordered_fine_cpu.py to check against numpy
+//   host_xxx fineplan <cases.bin> <n>   whether the fine kernel replaces a plan (ordered_fine.h: fine_replaces): n records of one
+//                                     OrderedFacts, one OrderedSwitches and one FineFacts; prints 0 / 1 per line
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +47,7 @@
 
 #include "host_logic.h"
 #include "ordered_plan.h"
+#include "ordered_fine.h"
 
 using namespace dp;
 
@@ -630,6 +638,129 @@ static int run_orderedplan(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- ordered dither: the fine table and the choice of its kernel ---------------------------------------------------
+// N(x): the entries at the smallest distance; T(x): everything up to the second smallest (counted with multiplicity).  Only
+// entries whose smallest distance to the cell is within the second smallest LARGEST distance of any entry can be members.
+static void fine_masks(const std::vector<uint8_t> &pal, const int K, const int mw, std::vector<uint32_t> &tm, std::vector<uint32_t> &nm)
+{
+    tm.assign((size_t)kFineCells * mw, 0u);
+    nm.assign((size_t)kFineCells * mw, 0u);
+    parallel_cells(kFineCells, [&](const int lo, const int hi) {
+        std::vector<int> cand, d;
+        for (int cell = lo; cell < hi; ++cell) {
+            const int c0[3] = {(cell & 31) * 8, ((cell >> 5) & 31) * 8, (cell >> 10) * 8};
+            int u0 = 1 << 30, u1 = 1 << 30;  // the two smallest upper bounds
+            std::vector<int> dmin(K);
+            for (int j = 0; j < K; ++j) {
+                int lo2 = 0, hi2 = 0;
+                for (int k = 0; k < 3; ++k) {
+                    const int p = pal[3 * j + k], a = c0[k], b = c0[k] + 7;
+                    const int near = p < a ? a - p : (p > b ? p - b : 0), far = std::max(std::abs(p - a), std::abs(p - b));
+                    lo2 += near * near;
+                    hi2 += far * far;
+                }
+                dmin[j] = lo2;
+                if (hi2 < u0) {
+                    u1 = u0;
+                    u0 = hi2;
+                } else if (hi2 < u1) {
+                    u1 = hi2;
+                }
+            }
+            cand.clear();
+            for (int j = 0; j < K; ++j)
+                if (dmin[j] <= u1) cand.push_back(j);
+            d.resize(cand.size());
+            uint32_t *t = &tm[(size_t)cell * mw], *n = &nm[(size_t)cell * mw];
+            for (int i = 0; i < 512; ++i) {
+                const int r = c0[0] + (i & 7), g = c0[1] + ((i >> 3) & 7), b = c0[2] + (i >> 6);
+                int d0 = 1 << 30, d1 = 1 << 30;
+                for (size_t q = 0; q < cand.size(); ++q) {
+                    const uint8_t *p = &pal[3 * (size_t)cand[q]];
+                    d[q] = (r - p[0]) * (r - p[0]) + (g - p[1]) * (g - p[1]) + (b - p[2]) * (b - p[2]);
+                    if (d[q] < d0) {
+                        d1 = d0;
+                        d0 = d[q];
+                    } else if (d[q] < d1) {
+                        d1 = d[q];
+                    }
+                }
+                for (size_t q = 0; q < cand.size(); ++q) {
+                    const int j = cand[q];
+                    if (d[q] <= d1) t[j >> 5] |= 1u << (j & 31);
+                    if (d[q] == d0) n[j >> 5] |= 1u << (j & 31);
+                }
+            }
+        }
+    });
+}
+
+static int run_finepack(const char *path, const int K, const char *out_path)
+{
+    if (K < 2 || K > 256) {
+        fprintf(stderr, "finepack: 2 <= K <= 256\n");
+        return 2;
+    }
+    std::vector<uint8_t> pal((size_t)K * 3);
+    FILE *f = fopen(path, "rb");
+    if (!f || fread(pal.data(), 1, pal.size(), f) != pal.size()) {
+        fprintf(stderr, "cannot read %d colours from %s\n", K, path);
+        return 2;
+    }
+    fclose(f);
+    const int mw = 8;
+    std::vector<uint32_t> coord4(K), tm, nm;
+    for (int j = 0; j < K; ++j) coord4[j] = (uint32_t)pal[3 * j] | ((uint32_t)pal[3 * j + 1] << 8) | ((uint32_t)pal[3 * j + 2] << 16);
+    fine_masks(pal, K, mw, tm, nm);
+    FineTable ft, again;
+    fine_pack(tm.data(), nm.data(), mw, K, coord4, fine_table_fits, ft);
+    fine_pack(tm.data(), nm.data(), mw, K, coord4, fine_table_fits, again);  // the same answer every time
+    const std::vector<uint32_t> im = ft.ok ? ft.lds_image() : std::vector<uint32_t>();
+    int bad = ft.ok != again.ok || ft.off != again.off || ft.win_idx != again.win_idx || ft.wide_idx != again.wide_idx;
+    if (ft.ok) bad += (int64_t)im.size() * 4 != fine_table_bytes(ft.n_win, ft.n_wide) || !fine_table_fits(ft.n_win, ft.n_wide);
+    f = fopen(out_path, "wb");
+    if (!f) return 2;
+    const int32_t head[4] = {ft.ok ? 1 : 0, ft.n_win, ft.n_wide, (int32_t)im.size()};
+    fwrite(head, sizeof(int32_t), 4, f);
+    if (ft.ok) {
+        fwrite(ft.off.data(), 2, ft.off.size(), f);
+        fwrite(ft.win_idx.data(), 2, ft.win_idx.size(), f);
+        fwrite(ft.wide_cell.data(), 2, ft.wide_cell.size(), f);
+        fwrite(ft.wide_idx.data(), 2, ft.wide_idx.size(), f);
+        fwrite(ft.quad.data(), 4, ft.quad.size(), f);
+        fwrite(ft.pair.data(), 4, ft.pair.size(), f);
+        fwrite(ft.wide.data(), 4, ft.wide.size(), f);
+        fwrite(im.data(), 4, im.size(), f);
+    }
+    fclose(f);
+    printf("finepack K=%d ok=%d windows=%d wide=%d bytes=%lld bad=%d\n", K, (int)ft.ok, ft.n_win, ft.n_wide,
+           (long long)(ft.ok ? fine_table_bytes(ft.n_win, ft.n_wide) : 0), bad);
+    return bad ? 1 : 0;
+}
+
+static int run_fineplan(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        OrderedFacts facts;
+        OrderedSwitches sw;
+        FineFacts ff;
+        if (fread(&facts, sizeof(facts), 1, f) != 1 || fread(&sw, sizeof(sw), 1, f) != 1 || fread(&ff, sizeof(ff), 1, f) != 1 || facts.hw < 1 ||
+            facts.w < 1 || facts.n_cus < 1) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const OrderedPlan p = plan_ordered(facts, sw);
+        printf("fine %d %s %d\n", c, family_name(p.family), (int)fine_replaces(p, ff));
+    }
+    fclose(f);
+    return 0;
+}
+
 // ---- void-and-cluster rank matrices ------------------------------------------------------------------------------
 static int run_voidcluster(const char *path, const int n_cases)
 {
@@ -667,7 +798,7 @@ static int run_voidcluster(const char *path, const int n_cases)
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -678,6 +809,8 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "pngfile") return run_pngfile(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "orderedplan") return run_orderedplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "voidcluster") return run_voidcluster(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
+    if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

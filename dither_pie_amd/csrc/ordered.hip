@@ -10,7 +10,9 @@
 // Which kernel runs: launch_ordered fills the facts of a call, plan_ordered (ordered_plan.h) decides -- the order of
 // precedence of the seven families and the measurements behind it are written down there, and
 // tests/test_ordered_plan_cpu.py checks the decision without a GPU -- and tile_kernel / brute_kernel / fix_kernel at the
-// end of this file map a plan to one of the instantiations the library ships.
+// end of this file map a plan to one of the instantiations the library ships.  One refinement comes after the plan: where the
+// palette has a fine table and it fits, ordered_fine_kernel runs in place of the lean kernel on plain 8-entry blocks with integer
+// thresholds (ordered_fine.h: fine_replaces; tests/test_ordered_fine_cpu.py).
 // Pixels whose result depends on scipy's visiting order in a way no table expresses, and near ties of the
 // float path, only set a flag bit; fixup_kernel compacts the flagged pixels per workgroup into LDS and
 // resolves them through the scipy-order KD-tree emulation (tree_query) and the literal float64 chain.
@@ -18,6 +20,7 @@
 
 #include "dp_internal.h"
 #include "ordered_plan.h"
+#include "ordered_fine.h"
 #include "tree_query.hip.h"
 
 namespace dp {
@@ -2022,6 +2025,324 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// ordered_fine_kernel: the lean kernel's main loop on FOUR candidates per nearest-only slot and SIX per full slot.
+//
+// The lean kernel is bound by the vector instructions it issues, and those are dominated by the candidate count: four
+// instructions per key and three per insertion, times eight because the cells are 16 wide.  On cells 8 wide the sets are
+// short enough for 4 + 2 (host_logic.h: fine_pack), and the 32768 cells share ~1800 windows, which fit LDS:
+//   per pixel  cell number -> ds_read_u16 (the window of the cell) -> ds_read_b128 (quad A), full slots also ds_read_b64 (pair B)
+// The window numbers of a tile are read one tile ahead (the pixels are loaded two tiles ahead), so the dependent read is off
+// the critical path.  Wide cells map to window 0, six equal entries: their keys tie and the pixel is deferred like any tie.
+// Deferred pixels (wave-private queue, drained 64 at a time as in the lean kernel): a wide cell's on its flat list in LDS
+// (resolve_wide); ties, exact equality, straddling groups, the partial last group and whatever resolve_wide passes on through
+// the index-ordered table in global memory with the complete code (fast_pixel_global's path), which is where the tie codes
+// are defined.  MODE 1 only (integer thresholds in LDS).
+// LDS (words): quads A | wide lists | pairs B | windows of the cells (u16) | wide cell numbers (u16) | thresholds | ... | queues
+// ---------------------------------------------------------------------------------------------
+
+// Keys of the six candidates of a window and the three smallest (see cand8)
+__device__ __forceinline__ void cand6(const uint32_t x, const uint4 ca, const uint32_t c4, const uint32_t c5, const int neg2, int &m0,
+                                      int &m1, int &m2)
+{
+    int n0, n1, n2, n3, n4, n5, p0, p1, p2, p3, p4, p5;
+    asm volatile(
+        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
+        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
+        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
+        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
+        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
+        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
+        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
+        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
+        "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
+        "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
+        "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
+        "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
+        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
+        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
+        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
+        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
+        "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
+        "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
+        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
+        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
+        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
+        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
+        "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
+        "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
+        // top-3 insertion network (m0 <= m1 <= m2)
+        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
+        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
+        "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
+        "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
+        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
+        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
+        "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
+        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
+        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
+        "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
+        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
+        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
+        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
+          [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
+          [m2] "=&v"(m2)
+        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5),
+          [ng] "s"(neg2));
+}
+
+// byte offset of the window number of x's cell: cell = r>>3 | (g>>3)<<5 | (b>>3)<<10 (host_logic.h: fine_cell), times 2
+__device__ __forceinline__ uint32_t fine_cell_offset(const uint32_t x)
+{
+    return ((x >> 2) & 0x3eu) | ((x >> 5) & 0x7c0u) | ((x >> 8) & 0xf800u);
+}
+
+struct FineLds {  // where the parts of the table are, in bytes from the start of LDS
+    uint32_t wide_at, pair_at, off_at, ids_at, thr_at;
+};
+
+// The deferred path (see lean_pixel_full): the lowest deferred pixel of a queue entry, from its bytes in memory to its bytes
+// in memory; returns the entry without that pixel.
+template <int MODE>
+__device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                    unsigned long long *__restrict__ flags, const Geo &g, const PalDev &pal,
+                                                    const ThrDev &thr, const uint32_t *s_words, const FineLds &at)
+{
+    const uint32_t mask = entry & 15u;
+    const uint32_t p = (entry >> 4) * 4u + (uint32_t)__builtin_ctz(mask | 16u);
+    const uint8_t *s_bytes = reinterpret_cast<const uint8_t *>(s_words);
+    const uint8_t *b = in + (size_t)p * 3;
+    const uint32_t x = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+    LeanThr th;
+    pixel_threshold<MODE>(p, g, thr, s_words + at.thr_at / 4, 0.0f, 0.0f, 0.0f, th);
+    const uint32_t cell2 = fine_cell_offset(x);
+    uint32_t c = 0;
+    bool done = false, slow = false;
+    if (*reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2) == 0) {
+        // a wide cell: its place in the ascending list of their numbers (padded to kFineIds with 0xffff) is its flat list's
+        const uint16_t *ids = reinterpret_cast<const uint16_t *>(s_bytes + at.ids_at);
+        const uint32_t cell = cell2 >> 1;
+        uint32_t lo = 0;
+#pragma unroll
+        for (uint32_t step = kFineIds / 2; step != 0u; step >>= 1)
+            if ((uint32_t)ids[lo + step] <= cell) lo += step;
+        done = resolve_wide<MODE>(x, th, thr.sh, s_words + at.wide_at / 4 + lo * kWideList, kWideList, c);
+    }
+    if (!done) {
+        bool hard;
+        Leaf lf;
+        leaf_find_global<8>(x, pal, lf);
+        c = resolve_pixel<MODE, 8>(x, th, lf, g, pal, thr, nullptr, slow, hard);
+    }
+    uint8_t *o = out + (size_t)p * 3;
+    o[0] = (uint8_t)c;
+    o[1] = (uint8_t)(c >> 8);
+    o[2] = (uint8_t)(c >> 16);
+    if (slow) flag_slow_pixel(p, flags, g);
+    const uint32_t rest = mask & (mask - 1u);
+    return rest ? ((entry & ~15u) | rest) : 0u;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                                    unsigned long long *__restrict__ flags, const Geo g,
+                                                                    const PalDev pal, const ThrDev thr, const float sx, const float sy,
+                                                                    const float sc, const uint32_t n_tiles)
+{
+    static_assert(MODE == 1, "integer thresholds in LDS only");
+    (void)sx, (void)sy, (void)sc;
+    __shared__ __align__(16) uint32_t smem[kLeanLdsWords];
+    // (two words at a time: every part is a whole number of word pairs, the pairs B of an odd number of windows no more than that,
+    // and the thresholds right behind the table are written by other lanes)
+    for (int i = threadIdx.x * 2; i < pal.fine_words; i += kCellBlock * 2)
+        *reinterpret_cast<uint2 *>(&smem[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[i]);
+    {
+        const int n = thr.th_h * thr.tw_pad;
+        for (int i = threadIdx.x; i < n; i += kCellBlock) smem[pal.fine_words + i] = thr.mpad[i];
+    }
+    __syncthreads();
+    FineLds at;
+    at.wide_at = (uint32_t)pal.fine_win * (kFineQuad * 4);
+    at.pair_at = at.wide_at + (uint32_t)pal.fine_wide * (kWideList * 4);
+    at.off_at = at.pair_at + (uint32_t)pal.fine_win * ((kFineWindow - kFineQuad) * 4);
+    at.ids_at = at.off_at + kFineCells * 2;
+    at.thr_at = at.ids_at + kFineIds * 2;
+    const uint8_t *s_bytes = reinterpret_cast<const uint8_t *>(smem);
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t *s_queue = smem + (kLeanLdsWords - kLeanQueueWords) + (threadIdx.x >> 6) * kLeanQueue;
+    uint32_t qcount = 0;  // wave-uniform
+    const uint3 *in3 = reinterpret_cast<const uint3 *>(in);
+    uint3 *out3 = reinterpret_cast<uint3 *>(out);
+    const uint32_t n_full = g.n_px >> 2;  // groups of four whole pixels; a partial last group goes through the queue
+
+    auto unpack = [](const uint3 w, uint32_t xq[4]) {
+        xq[0] = w.x & 0xffffffu;
+        xq[1] = __builtin_amdgcn_perm(w.y, w.x, 0x0c050403u);
+        xq[2] = __builtin_amdgcn_perm(w.z, w.y, 0x0c040302u);
+        xq[3] = w.z >> 8;
+    };
+    // the window numbers of a group's four pixels
+    auto windows = [&](const uint32_t xq[4], uint32_t win[4]) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + fine_cell_offset(xq[q]));
+    };
+    auto drain = [&](const uint32_t n) {
+        qcount -= n;
+        __threadfence_block();  // the group stores that are about to be overwritten
+        uint32_t rest = 0u;
+        if (lane < n) rest = fine_pixel_full<MODE>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
+        const unsigned long long mb = __ballot(rest != 0u);  // groups with a further deferred pixel go back
+        if (mb != 0ull) {
+            if (rest != 0u)
+                s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qcount))] = rest;
+            qcount += (uint32_t)__popcll(mb);
+        }
+    };
+
+    uint32_t tile = blockIdx.x;
+    uint32_t fy = 0, fx = 0;
+    uint3 wn = make_uint3(0u, 0u, 0u), wnn = make_uint3(0u, 0u, 0u);  // the groups of the next tile and of the one after it
+    uint32_t xn[4], winn[4];                                          // the next tile's pixels and their windows
+    if (tile < n_tiles) {
+        const uint32_t gidx0 = tile * kCellBlock + threadIdx.x;
+        if (gidx0 < n_full) wn = in3[gidx0];
+        if (gidx0 * 4u < g.n_px) locate(g, gidx0 * 4u, fy, fx);
+        const uint32_t gidx1 = gidx0 + gridDim.x * kCellBlock;
+        if (tile + gridDim.x < n_tiles && gidx1 < n_full) wnn = in3[gidx1];
+    }
+    unpack(wn, xn);
+    windows(xn, winn);
+    // (classes of the wave tiles: see ordered_lean_kernel)
+    const bool use_cls = thr.has_cls != 0;
+    uint32_t cls_word = 0, cls_shift = 0;  // wave-uniform
+    auto tile_class = [&](const uint32_t ty, const uint32_t tx, const uint32_t gi) {
+        cls_word = 0;
+        cls_shift = 0;
+        if (!use_cls) return;
+        const uint32_t y0l = (uint32_t)__builtin_amdgcn_readfirstlane((int)ty), x0l = (uint32_t)__builtin_amdgcn_readfirstlane((int)tx);
+        const uint32_t g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)gi);
+        if (x0l + 256u > g.w || g0 + 64u > n_full) return;
+        const uint32_t row = ((uint32_t)g.y0 + y0l) & (uint32_t)(thr.th_h - 1), col = ((uint32_t)g.x0 + x0l) & (uint32_t)(thr.th_w - 1);
+        const uint32_t idx = row * (uint32_t)thr.th_w + col;  // < 256
+        cls_word = thr.cls_nib[idx >> 3];
+        cls_shift = (idx & 7u) * 4u;
+    };
+    if (tile < n_tiles) tile_class(fy, fx, tile * kCellBlock + threadIdx.x);
+    for (; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t gidx = tile * kCellBlock + threadIdx.x;
+        uint32_t xq[4], win[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xq[q] = xn[q];
+            win[q] = winn[q];
+        }
+        const uint32_t cls = (cls_word >> cls_shift) & 15u;  // wave-uniform
+        const uint32_t cy = fy, cx = fx;  // this tile's position; fy / fx move on to the next tile's
+        {
+            // the next tile's groups arrived during the last one: ask for their windows now, and for the groups after them
+            unpack(wnn, xn);
+            windows(xn, winn);
+            const uint32_t next = tile + gridDim.x, next2 = next + gridDim.x;
+            const uint32_t gn = next * kCellBlock + threadIdx.x, gn2 = next2 * kCellBlock + threadIdx.x;
+            wnn = make_uint3(0u, 0u, 0u);
+            if (next2 < n_tiles && gn2 < n_full) wnn = in3[gn2];
+            fx += g.adv_x;
+            fy += g.adv_y;
+            if (fx >= g.w) {
+                fx -= g.w;
+                ++fy;
+            }
+            if (fy >= g.h) fy -= g.h;
+            cls_word = 0;
+            if (next < n_tiles) tile_class(fy, fx, gn);
+        }
+        // all clear; the deferred path ORs in the bits of the pixels it leaves to the fix-up pass later
+        if (lane < 4u) flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+        bool rare[4] = {false, false, false, false};
+        if (gidx < n_full) {
+            uint4 ca[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ca[q] = *reinterpret_cast<const uint4 *>(s_bytes + (win[q] << 4));
+            // one straight-line body per class pattern (bit q: slot q takes its nearest entry whatever the second one is)
+            auto body = [&](auto cls_c) {
+                constexpr uint32_t CLS = (uint32_t)decltype(cls_c)::value;
+                uint32_t pb[4];  // byte offset of the pair B, less the quad's sixteen: position 4 of the window is at + 16
+                uint2 cb[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if ((CLS >> q) & 1u) continue;
+                    pb[q] = (win[q] << 3) + (at.pair_at - 16u);
+                    cb[q] = *reinterpret_cast<const uint2 *>(s_bytes + pb[q] + 16u);
+                }
+                LeanThr th[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    th[q].mt = 0;
+                    th[q].t = 0.0f;
+                }
+                if (CLS != 15u) {
+                    uint32_t row, col;
+                    thr_pos(thr, (uint32_t)g.y0 + cy, (uint32_t)g.x0 + cx, row, col);
+                    const uint32_t ta = row * (uint32_t)thr.tw_pad + col;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if ((CLS >> q) & 1u) continue;
+                        th[q].mt = *reinterpret_cast<const uint32_t *>(s_bytes + at.thr_at + (ta + q) * 4u);
+                    }
+                }
+                // the group runs over the end of its row: all four through the queue (their positions differ)
+                const bool straddle = cx + 3u >= g.w;
+                uint32_t col[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t x = xq[q];
+                    if ((CLS >> q) & 1u) {
+                        int m0, m1;
+                        cand4n(x, ca[q], g.neg2, m0, m1);
+                        rare[q] = ((uint32_t)(m0 ^ m1) < (1u << kLocalBits)) | straddle;  // a tie for the nearest entry; also: any wide cell
+                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((win[q] << 4) | ((uint32_t)m0 & 0xfcu)));
+                    } else {
+                        int m0, m1, m2;
+                        cand6(x, ca[q], cb[q].x, cb[q].y, g.neg2, m0, m1, m2);
+                        const int a0 = m0 >> kLocalBits, a1 = m1 >> kLocalBits;
+                        const bool tie = (a0 == a1) | ((uint32_t)(m1 ^ m2) < (1u << kLocalBits));  // also: any wide cell
+                        const int xx = (int)__builtin_amdgcn_udot4(x, x, 0u, false);
+                        const uint32_t d0 = (uint32_t)(a0 + xx);
+                        const uint32_t S = d0 + (uint32_t)a1 + (uint32_t)xx;
+                        bool eq;
+                        const bool nearest = lean_decide<MODE>(d0, S, th[q], thr.sh, eq);
+                        rare[q] = tie | eq | straddle;
+                        const uint32_t pos = (uint32_t)(nearest ? m0 : m1) & 0xfcu;  // 4 x the place in the window
+                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((pos < 16u ? (win[q] << 4) : pb[q]) + pos));
+                    }
+                }
+                uint3 wo;
+                wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
+                wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
+                wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
+                out3[gidx] = wo;
+            };
+            if (cls == 5u) body(std::integral_constant<int, 5>{});
+            else if (cls == 10u) body(std::integral_constant<int, 10>{});
+            else if (cls == 15u) body(std::integral_constant<int, 15>{});
+            else body(std::integral_constant<int, 0>{});
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rare[q] = gidx * 4u + (uint32_t)q < g.n_px;  // the partial last group
+        }
+        // one queue entry per group with deferred pixels: group << 4 | which of its four
+        const uint32_t rmask = (rare[0] ? 1u : 0u) | (rare[1] ? 2u : 0u) | (rare[2] ? 4u : 0u) | (rare[3] ? 8u : 0u);
+        const unsigned long long rb = __ballot(rmask != 0u);
+        if (rb != 0ull) {  // wave-uniform
+            if (rmask != 0u)
+                s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, qcount))] = (gidx << 4) | rmask;
+            qcount += (uint32_t)__popcll(rb);
+            while (qcount >= 64u) drain(64u);
+        }
+    }
+    while (qcount != 0u) drain(qcount < 64u ? qcount : 64u);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Float (gamma) palettes with a cell table (accel.hip, build_accel_float): blocks of 8 byte offsets into
 // the candidate table {x, y, z, out_rgb} held in LDS next to the cell table and lut_in.  Candidates are
 // ranked in float32 (key = distance bits with the block position in the low 3 bits); the ranking is
@@ -2764,18 +3085,20 @@ int num_cus()
 // experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel of every launch on stderr (tests that must know which
 // kernel a case reached): the family, then the template arguments and the table of the plan and the fix-up pass's queue; the
 // product library compiles to nothing here
-static inline void trace_plan(const OrderedPlan &p, bool aligned)
+// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine"
+static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine)
 {
 #ifdef DP_EXPERIMENTS
     if (std::getenv("DP_ORDERED_TRACE")) {
         constexpr const char *tables[] = {"plain8", "plain4", "warped"};
-        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d\n",
+        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s\n",
                 family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
-                p.fix_big_queue ? 1 : 0);
+                p.fix_big_queue ? 1 : 0, fine ? "fine" : family_name(p.family));
     }
 #else
     (void)p;
     (void)aligned;
+    (void)fine;
 #endif
 }
 
@@ -2915,8 +3238,11 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         g.adv_y = plan.adv_y;
         g.adv_x = plan.adv_x;
         const bool brute = plan.family == kFamBrute;
+        // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where its table exists and fits
+        const bool fine = fine_replaces(plan, FineFacts{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, thr.th_h * thr.tw_pad * 4}) &&
+                          !exp_env("DP_NO_FINE_KERNEL");
         const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
-        const TileKernel tile_k = brute ? nullptr : tile_kernel(plan);
+        const TileKernel tile_k = brute ? nullptr : (fine ? ordered_fine_kernel<1> : tile_kernel(plan));
         const FixKernel fix_k = fix_kernel(plan);
         if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
             set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
@@ -2945,7 +3271,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_plan(plan, g.aligned);
+        trace_plan(plan, g.aligned, fine);
         prof_mid(pm, s);
         hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);
