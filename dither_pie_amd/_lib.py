@@ -196,6 +196,20 @@ _SIGS_VOIDCLUSTER = {
     "dp_thresholds_void_cluster": (_i, [_i, _i, _u32, _i, _vp, C.POINTER(_vp)]),
 }
 EXPORTS_VOIDCLUSTER = tuple(_SIGS_VOIDCLUSTER)
+# include/ditherpie_hip_metric.h: palettes with a colour metric (an integer Oklab), their top-2 table, ordered dithering
+# through it and the host statements; a table of its own for the same reason.
+METRIC_RGB, METRIC_OKLAB = 0, 1
+_SIGS_METRIC = {
+    "dp_palette_create_metric": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "dp_palette_metric": (_i, [_vp]),
+    "dp_metric_prepare": (_i, [_vp]),
+    "dp_metric_table_bytes": (_sz, [_vp]),
+    "dp_metric_ordered_u8": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "dp_metric_lab_u8": (_i, [_vp, _vp, _i64, _vp]),
+    "dp_metric_lab_host": (_i, [_vp, _i64, _vp]),
+    "dp_metric_top2_host": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+}
+EXPORTS_METRIC = tuple(_SIGS_METRIC)
 
 
 def build(force=False):
@@ -240,7 +254,8 @@ def load():
                                           + list(_SIGS_SCENE.items()) + list(_SIGS_GIF.items()) + list(_SIGS_PNG.items())
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
-                                          + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())):
+                                          + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
+                                          + list(_SIGS_METRIC.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

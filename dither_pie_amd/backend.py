@@ -27,6 +27,9 @@ def require_gpu():
         raise DitherPieError(-2, "no HIP device visible: the MI355X backend has no CPU fallback")
 
 
+METRICS = ("rgb", "oklab")   # DP_METRIC_RGB, DP_METRIC_OKLAB (include/ditherpie_hip_metric.h)
+
+
 class Palette:
     """dp_palette: scipy-order KD-tree + colour tables resident in HBM.
 
@@ -56,7 +59,14 @@ class Palette:
         if self._px_served >= self.accel_break_even_pixels():
             self.build_accel()
 
-    def __init__(self, pal_f32, out_colors, lut_in=None, accel=False):
+    def __init__(self, pal_f32, out_colors, lut_in=None, accel=False, metric="rgb"):
+        """metric: "rgb" (squared Euclidean RGB distance, the reference's) or "oklab" (include/ditherpie_hip_metric.h: an
+        integer Oklab, at most 256 colours, integer palette values, no lut_in).  A metric palette is searched through its own
+        top-2 table only: ordered(), pattern() and dotdiff() use it, every other mode refuses it."""
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+        if metric != "rgb" and lut_in is not None:
+            raise ValueError(f"a palette with the {metric!r} metric takes no lut_in (Oklab linearises by itself)")
         require_gpu()
         self.pal_f32 = np.ascontiguousarray(pal_f32, dtype=np.float32).reshape(-1, 3)
         self.out_colors = np.ascontiguousarray(out_colors, dtype=np.uint8).reshape(-1, 3)
@@ -68,14 +78,19 @@ class Palette:
         self.K = self.pal_f32.shape[0]
         self._h = C.c_void_p()
         self._destroy = _lib.load().dp_palette_destroy
-        check(_lib.load().dp_palette_create(_np_ptr(self.pal_f32), _np_ptr(self.out_colors), self.K,
-                                            _np_ptr(self.lut_in), C.byref(self._h)))
+        self.metric = metric
+        if metric == "rgb":
+            check(_lib.load().dp_palette_create(_np_ptr(self.pal_f32), _np_ptr(self.out_colors), self.K,
+                                                _np_ptr(self.lut_in), C.byref(self._h)))
+        else:
+            check(_lib.load().dp_palette_create_metric(_np_ptr(self.pal_f32), _np_ptr(self.out_colors), self.K,
+                                                       METRICS.index(metric), C.byref(self._h)))
         k, integer, nodes = C.c_int(), C.c_int(), C.c_int()
         check(_lib.load().dp_palette_info(self._h, C.byref(k), C.byref(integer), C.byref(nodes)))
         self.is_integer = bool(integer.value)
         self.n_nodes = nodes.value
         self.accel_entries = self.accel_max_list = 0
-        self._accel_done = False
+        self._accel_done = metric != "rgb"   # a metric palette never builds the accelerator: its table is its only search
         self._px_served = 0
         self._accel_lock = threading.Lock()
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -109,6 +124,16 @@ class Palette:
         with torch.cuda.device(self.device), _Launch(self.device, None):
             check(_lib.load().dp_pattern_prepare(self._h))
         return int(_lib.load().dp_pattern_table_bytes(self._h))
+
+    def metric_prepare(self):
+        """Build the top-2 table of a metric palette now (dp_metric_prepare: 32 MiB of device memory, synchronous, idempotent,
+        on the device's null stream) instead of at the first ordered() / pattern() / dotdiff() call with it -- which is also
+        what a caller who captures one of them into a graph has to do first.  Returns the table's size in bytes."""
+        if self.metric == "rgb":
+            raise ValueError("metric_prepare() needs a palette with a metric (Palette(..., metric='oklab'))")
+        with torch.cuda.device(self.device), _Launch(self.device, None):
+            check(_lib.load().dp_metric_prepare(self._h))
+        return int(_lib.load().dp_metric_table_bytes(self._h))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -271,6 +296,13 @@ def ordered(frames, pal: Palette, mode, thr: Thresholds | None = None, ign_scale
     out = _check_out(out, f)
     _check_palette_device(pal, f)
     L = _lib.load()
+    if getattr(pal, "metric", "rgb") != "rgb":   # a metric palette: one gather per pixel from its top-2 table (dp_metric_ordered_u8)
+        if int(mode) == MODE_IGN:
+            raise ValueError(f"interleaved gradient noise is not supported with the {pal.metric!r} metric")
+        with torch.cuda.device(f.device), _Launch(f.device, None):
+            check(L.dp_metric_ordered_u8(f.data_ptr(), out.data_ptr(), n, h, w, int(y0), int(x0), pal._h, int(mode),
+                                         thr._h if thr is not None else None, _stream()))
+        return out.view(frames.shape)
     ws_bytes = L.dp_ordered_workspace_bytes(n, h, w)
     with torch.cuda.device(f.device):
         pal.note_pixels(n * h * w)
@@ -279,6 +311,47 @@ def ordered(frames, pal: Palette, mode, thr: Thresholds | None = None, ign_scale
                                   thr._h if thr is not None else None, float(ign_scale), int(ign_seed),
                                   ws.data_ptr(), ws.numel(), _stream()))
     return out.view(frames.shape)
+
+
+def metric_lab(pixels):
+    """(L, a, b) of uint8 RGB pixels in HBM ([..., 3], contiguous) under the Oklab metric -> int32 tensor of the same shape
+    (dp_metric_lab_u8: the device function the metric's kernels use)."""
+    if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() >= 1
+            and pixels.shape[-1] == 3):
+        raise TypeError("pixels must be a CUDA uint8 tensor [..., 3]")
+    p = pixels.contiguous()
+    out = torch.empty(p.shape, dtype=torch.int32, device=p.device)
+    with torch.cuda.device(p.device), _Launch(p.device, None):
+        check(_lib.load().dp_metric_lab_u8(p.data_ptr(), out.data_ptr(), p.numel() // 3, _stream()))
+    return out
+
+
+def _rgb_host(rgb):
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("rgb must be [..., 3]")
+    return a
+
+
+def metric_lab_host(rgb):
+    """The host statement of metric_lab (dp_metric_lab_host; no device): uint8 [..., 3] -> int32 [..., 3]."""
+    a = _rgb_host(rgb)
+    out = np.empty(a.shape, np.int32)
+    check(_lib.load().dp_metric_lab_host(_np_ptr(a), a.size // 3, _np_ptr(out)))
+    return out
+
+
+def metric_top2_host(rgb, pal_f32, metric="oklab"):
+    """The host statement of a metric palette's table (dp_metric_top2_host; no device): uint8 [..., 3] -> (nearest, second),
+    uint8 [...] each: the two smallest (distance, index) pairs, the lowest index first on equal distance."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+    a = _rgb_host(rgb)
+    pal = np.ascontiguousarray(pal_f32, dtype=np.float32).reshape(-1, 3)
+    i0, i1 = np.empty(a.shape[:-1], np.uint8), np.empty(a.shape[:-1], np.uint8)
+    check(_lib.load().dp_metric_top2_host(_np_ptr(a), a.size // 3, _np_ptr(pal), pal.shape[0], METRICS.index(metric), _np_ptr(i0),
+                                          _np_ptr(i1)))
+    return i0, i1
 
 
 def error_diffusion(frames, pal: Palette, taps, divisor, serpentine=False, out=None, arithmetic="python"):

@@ -218,6 +218,7 @@ int dp_cells_u8(const uint8_t *in_dev, uint8_t *out_dev, uint16_t *sets_dev, int
                 int cw, int ch, int colours, uint32_t fixed_mask, const uint16_t *groups_host, int n_groups, int m, int spread,
                 void *stream)
 {
+    if (metric_refused("dp_cells_u8", pal)) return DP_EUNSUPPORTED;
     const bool sizes_ok = n_frames >= 0 && h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)1 << 30;
     if (!pal || !groups_host || !sizes_ok || (n_frames > 0 && (!in_dev || !out_dev))) {
         set_error("dp_cells_u8: bad argument (pointers, n_frames >= 0, h, w >= 1, h * w <= 2^30)");

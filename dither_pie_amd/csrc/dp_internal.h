@@ -167,6 +167,15 @@ struct PatDev {
     int brick;                 // table addressed by 4x4x4 bricks of the cube (64-byte lines) instead of r | g<<8 | b<<16
 };
 
+// Device view of a metric palette's top-2 table (metric.hip; passed to the kernels by value); tab == nullptr: not built
+struct MetDev {
+    const uint16_t *tab;       // 2^24 entries in brick order (pattern_tab.hip.h): nearest | second << 8
+    const int4 *lab;           // 256: {L, a, b, 0} of entry k (zeros from K on)
+    const uint32_t *out_rgb;   // 256: its output bytes, r | g<<8 | b<<16
+    const uint16_t *cbrt;      // experiments build with DP_METRIC_CBRT_TABLE: the 65536 cube roots; otherwise nullptr
+    int K;
+};
+
 }  // namespace dp
 
 struct dp_palette {
@@ -205,6 +214,11 @@ struct dp_palette {
     std::vector<uint32_t> fine_masks;
     uint32_t *fine_dev;              // its place in accel_blob
     std::atomic<bool> fine_pending;  // fine_masks is waiting (read without build_mu by every matrix-mode call)
+    // the colour metric (include/ditherpie_hip_metric.h), fixed at birth.  A palette of DP_METRIC_OKLAB is searched only through
+    // its top-2 table (metric.hip), built at the first call that needs it under build_mu and published under dev_mu like `pat`
+    int metric;
+    dp::MetDev met;
+    void *met_blob;    // the one allocation behind `met` (may be null); freed by dp_palette_destroy
 };
 
 struct dp_thresholds {
@@ -287,6 +301,14 @@ int launch_wavelet(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
 int pattern_check_palette(const char *fn, const dp_palette *p);
 int pattern_ensure_table(const dp_palette *pal, hipStream_t s);
 PatDev pattern_snapshot(const dp_palette *pal);
+// metric palettes (metric.hip).  metric_refused: THE refusal of the entry points that would search a metric palette in RGB --
+// true (and the error set, naming `fn`) when pal is one.  metric_ensure_table_locked: the top-2 table, built on `s` and waited
+// for; the caller holds pal->build_mu.  launch_metric_rank_table: tab[a] = rank_of[nearest(a)], the pattern table of a metric palette
+bool metric_refused(const char *fn, const dp_palette *pal);
+int palette_create_impl(const char *fn, const float *pal_f32, const uint8_t *out_colors, int K, const uint8_t *lut_in, int metric,
+                        dp_palette **out);
+int metric_ensure_table_locked(dp_palette *p, hipStream_t s);
+int launch_metric_rank_table(const MetDev &md, const uint32_t *rank_of, uint8_t *tab, hipStream_t s);
 // void-and-cluster rank matrices (voidcluster.hip): launches only; the arguments are checked by the callers
 int launch_void_cluster(uint16_t *ranks_dev, int n_matrices, const uint32_t *seeds_host, int h, int w, int sigma256, hipStream_t s);
 int launch_resize_nearest(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, int oh, int ow,

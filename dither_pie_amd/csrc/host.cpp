@@ -128,12 +128,21 @@ int dp_kdtree_build_host(const double *pts, int K, int32_t *indices, int32_t *sp
 int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, const uint8_t *lut_in,
                       dp_palette **out)
 {
+    return dp::palette_create_impl("dp_palette_create", pal_f32, out_colors, K, lut_in, 0, out);
+}
+
+}  // extern "C"
+
+// dp_palette_create and dp_palette_create_metric (metric.hip); `metric` was checked by the caller
+int dp::palette_create_impl(const char *fn, const float *pal_f32, const uint8_t *out_colors, int K, const uint8_t *lut_in, int metric,
+                            dp_palette **out)
+{
     if (!pal_f32 || !out_colors || !out || K < 1) {
-        set_error("dp_palette_create: bad argument");
+        set_error("%s: bad argument", fn);
         return DP_EINVAL;
     }
     if (K > DP_MAX_COLORS) {
-        set_error("dp_palette_create: %d colours requested, this backend supports at most %d", K,
+        set_error("%s: %d colours requested, this backend supports at most %d", fn, K,
                   DP_MAX_COLORS);
         return DP_EUNSUPPORTED;
     }
@@ -142,7 +151,7 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     for (int i = 0; i < K * 3; ++i) {
         const float v = pal_f32[i];
         if (!std::isfinite(v)) {
-            set_error("dp_palette_create: non-finite palette value");
+            set_error("%s: non-finite palette value", fn);
             return DP_EINVAL;
         }
         pts[i] = (double)v;
@@ -154,7 +163,7 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     int inner = 0;
     for (int i = 0; i < nn; ++i) inner += t.split_dim[i] >= 0;
     if (inner > kQueueLarge) {
-        set_error("dp_palette_create: KD-tree with %d inner nodes exceeds the device traversal queue (%d)", inner,
+        set_error("%s: KD-tree with %d inner nodes exceeds the device traversal queue (%d)", fn, inner,
                   kQueueLarge);
         return DP_EUNSUPPORTED;
     }
@@ -263,9 +272,14 @@ int dp_palette_create(const float *pal_f32, const uint8_t *out_colors, int K, co
     p->pat_blob = nullptr;
     p->fine_dev = nullptr;
     p->fine_pending = false;
+    p->metric = metric;
+    p->met = dp::MetDev{nullptr, nullptr, nullptr, nullptr, 0};   // the top-2 table of a metric palette: built when first needed (metric.hip)
+    p->met_blob = nullptr;
     *out = p;
     return DP_OK;
 }
+
+extern "C" {
 
 // The candidate lists of the diffusion kernels (a 512 KB table from one small kernel, sharpened and padded on the host,
 // plus the 16^3 tables: 3 / 5 / 19 ms at 16 / 64 / 256 colours): built once, at the first diffusion call with the palette.
@@ -340,6 +354,7 @@ void dp_palette_destroy(dp_palette *p)
     if (p->blob) (void)hipFree(p->blob);
     if (p->accel_blob) (void)hipFree(p->accel_blob);
     if (p->pat_blob) (void)hipFree(p->pat_blob);
+    if (p->met_blob) (void)hipFree(p->met_blob);
     delete p;
 }
 
@@ -361,6 +376,7 @@ int dp_palette_build_accel(dp_palette *p)
         set_error("dp_palette_build_accel: NULL palette");
         return DP_EINVAL;
     }
+    if (p->metric != 0) return DP_OK;   // a metric palette is searched through its own table only (metric.hip)
     std::lock_guard<std::mutex> lock(p->build_mu);
     if (p->accel_tried || !(p->same_out || p->float_accel)) return DP_OK;
     p->accel_tried = true;
@@ -584,6 +600,7 @@ int dp_ordered_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
                   const dp_palette *pal, int mode, const dp_thresholds *thr, float ign_scale, int ign_seed,
                   void *workspace_dev, size_t workspace_bytes, void *stream)
 {
+    if (metric_refused("dp_ordered_u8", pal)) return DP_EUNSUPPORTED;
     if (n_frames == 0 && pal && h >= 1 && w >= 1) return DP_OK;  // nothing to do (pointers may be null)
     if (!in_dev || !out_dev || !pal || n_frames < 0 || h < 1 || w < 1 || y0 < 0 || x0 < 0) {
         set_error("dp_ordered_u8: bad argument");
@@ -673,6 +690,7 @@ static int error_diffusion_common(const uint8_t *in_dev, uint8_t *out_dev, int64
                                   const double *wq64, int ntaps, int serpentine, void *workspace_dev, size_t workspace_bytes,
                                   void *stream, const char *fn, const double *hybrid)
 {
+    if (metric_refused(fn, pal)) return DP_EUNSUPPORTED;
     if (n_frames == 0 && pal && h >= 1 && w >= 1) return DP_OK;  // nothing to do (pointers may be null)
     if (!in_dev || !out_dev || !pal || n_frames < 0 || h < 1 || w < 1 || ntaps < 0 || ntaps > 16 ||
         (ntaps && (!dx || !dy || !wq))) {
@@ -702,6 +720,7 @@ int dp_variable_diffusion_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_
                              const uint8_t *gate_dev, const float *coef_dev, void *workspace_dev,
                              size_t workspace_bytes, void *stream)
 {
+    if (metric_refused("dp_variable_diffusion_u8", pal)) return DP_EUNSUPPORTED;
     if (n_frames == 0 && pal && h >= 1 && w >= 1) return DP_OK;
     if (!in_dev || !out_dev || !pal || n_frames < 0 || h < 1 || w < 1 || model < 1 || model > 4 ||
         (model == DP_DIFFUSER_ADAPTIVE_VARIANCE && !gate_dev) || (model == DP_DIFFUSER_OSTROMOUKHOV && !coef_dev)) {
@@ -725,6 +744,7 @@ int dp_variable_diffusion_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_
 
 int dp_riemersma_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal, void *stream)
 {
+    if (metric_refused("dp_riemersma_u8", pal)) return DP_EUNSUPPORTED;
     if (!pal || n_frames < 0 || h < 0 || w < 0) {
         set_error("dp_riemersma_u8: bad argument (NULL palette or negative size)");
         return DP_EINVAL;
@@ -787,6 +807,7 @@ size_t dp_halftone_workspace_bytes(int64_t n_frames, int h, int w, const dp_half
 int dp_halftone_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
                    const dp_halftone_params *params, void *workspace_dev, size_t workspace_bytes, void *stream)
 {
+    if (metric_refused("dp_halftone_u8", pal)) return DP_EUNSUPPORTED;
     if (!pal || n_frames < 0 || h < 0 || w < 0) {
         set_error("dp_halftone_u8: bad argument (NULL palette or negative size)");
         return DP_EINVAL;
@@ -868,6 +889,7 @@ size_t dp_wavelet_workspace_bytes(int64_t n_frames, int h, int w, const dp_wavel
 int dp_wavelet_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
                   const dp_wavelet_params *params, void *workspace_dev, size_t workspace_bytes, void *stream)
 {
+    if (metric_refused("dp_wavelet_u8", pal)) return DP_EUNSUPPORTED;
     if (!pal || n_frames < 0 || h < 0 || w < 0) {
         set_error("dp_wavelet_u8: bad argument (NULL palette or negative size)");
         return DP_EINVAL;
@@ -911,6 +933,7 @@ int dp_variance_gate_u8(const uint8_t *in_dev, uint8_t *gate_dev, int64_t n_fram
                         float var_threshold, int window_radius, void *workspace_dev, size_t workspace_bytes,
                         void *stream)
 {
+    if (metric_refused("dp_variance_gate_u8", pal)) return DP_EUNSUPPORTED;
     if (n_frames == 0 && pal && h >= 1 && w >= 1) return DP_OK;
     if (!in_dev || !gate_dev || !pal || n_frames < 0 || h < 1 || w < 1 || window_radius < 0 || window_radius > 64) {
         set_error("dp_variance_gate_u8: bad argument");

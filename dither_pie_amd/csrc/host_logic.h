@@ -2764,4 +2764,123 @@ inline void vac_thresholds(const uint16_t *ranks, const int n, float *thr)
     for (int i = 0; i < n; ++i) thr[i] = (float)((double)(2 * ((int)ranks[i] * L / n) + 1) / (double)(2 * L));
 }
 
+// ---- the Oklab colour metric (include/ditherpie_hip_metric.h; tests/metric_ref.py states it in numpy) -------------------------------
+// All integer arithmetic.  LIN[v] = round(65535 f(v / 255)), f the sRGB decoding function: the literal (one for the host and,
+// through metric.hip's __constant__ copy, the device); tests/test_metric_cpu.py checks it against the formula.
+#define DP_METRIC_LIN_VALUES \
+    0, 20, 40, 60, 80, 99, 119, 139, 159, 179, 199, 219, 241, 264, 288, 313, \
+    340, 367, 396, 427, 458, 491, 526, 562, 599, 637, 677, 718, 761, 805, 851, 898, \
+    947, 997, 1048, 1101, 1156, 1212, 1270, 1330, 1391, 1453, 1517, 1583, 1651, 1720, 1790, 1863, \
+    1937, 2013, 2090, 2170, 2250, 2333, 2418, 2504, 2592, 2681, 2773, 2866, 2961, 3058, 3157, 3258, \
+    3360, 3464, 3570, 3678, 3788, 3900, 4014, 4129, 4247, 4366, 4488, 4611, 4736, 4864, 4993, 5124, \
+    5257, 5392, 5530, 5669, 5810, 5953, 6099, 6246, 6395, 6547, 6700, 6856, 7014, 7174, 7335, 7500, \
+    7666, 7834, 8004, 8177, 8352, 8528, 8708, 8889, 9072, 9258, 9445, 9635, 9828, 10022, 10219, 10417, \
+    10619, 10822, 11028, 11235, 11446, 11658, 11873, 12090, 12309, 12530, 12754, 12980, 13209, 13440, 13673, 13909, \
+    14146, 14387, 14629, 14874, 15122, 15371, 15623, 15878, 16135, 16394, 16656, 16920, 17187, 17456, 17727, 18001, \
+    18277, 18556, 18837, 19121, 19407, 19696, 19987, 20281, 20577, 20876, 21177, 21481, 21787, 22096, 22407, 22721, \
+    23038, 23357, 23678, 24002, 24329, 24658, 24990, 25325, 25662, 26001, 26344, 26688, 27036, 27386, 27739, 28094, \
+    28452, 28813, 29176, 29542, 29911, 30282, 30656, 31033, 31412, 31794, 32179, 32567, 32957, 33350, 33745, 34143, \
+    34544, 34948, 35355, 35764, 36176, 36591, 37008, 37429, 37852, 38278, 38706, 39138, 39572, 40009, 40449, 40891, \
+    41337, 41785, 42236, 42690, 43147, 43606, 44069, 44534, 45002, 45473, 45947, 46423, 46903, 47385, 47871, 48359, \
+    48850, 49344, 49841, 50341, 50844, 51349, 51858, 52369, 52884, 53401, 53921, 54445, 54971, 55500, 56032, 56567, \
+    57105, 57646, 58190, 58737, 59287, 59840, 60396, 60955, 61517, 62082, 62650, 63221, 63795, 64372, 64952, 65535
+static const uint16_t kMetricLin[256] = {DP_METRIC_LIN_VALUES};
+static const uint32_t kMetricA[3][3] = {{27015, 35149, 3372}, {13887, 44611, 7038}, {5787, 18463, 41286}};   // rows sum to 65536
+static const int32_t kMetricB[3][3] = {{862, 3251, -17}, {8102, -9948, 1846}, {106, 3206, -3312}};           // rows sum to 4096, 0, 0
+
+// floor(cbrt(x * 2^32)), x < 2^16: the largest c in 0 .. 65535 with c^3 <= x << 32, by bisection
+inline uint32_t metric_icbrt(const uint32_t x)
+{
+    const uint64_t big = (uint64_t)x << 32;
+    uint32_t c = 0;
+    for (uint32_t bit = 1u << 15; bit; bit >>= 1) {
+        const uint64_t t = c | bit;
+        if (t * t * t <= big) c |= bit;
+    }
+    return c;
+}
+
+// the 65536 values of metric_icbrt, computed once
+inline const uint16_t *metric_cbrt_table()
+{
+    static const std::vector<uint16_t> tab = [] {
+        std::vector<uint16_t> t(65536);
+        for (uint32_t x = 0; x < 65536; ++x) t[x] = (uint16_t)metric_icbrt(x);
+        return t;
+    }();
+    return tab.data();
+}
+
+// (L, a, b) of an sRGB colour; cbrt_tab = metric_cbrt_table() (or nullptr: bisection per component)
+inline void metric_lab(const uint32_t r, const uint32_t g, const uint32_t b, const uint16_t *cbrt_tab, int32_t lab[3])
+{
+    const uint32_t lin[3] = {kMetricLin[r & 255u], kMetricLin[g & 255u], kMetricLin[b & 255u]};
+    int32_t c[3];
+    for (int i = 0; i < 3; ++i) {
+        const uint32_t x = (kMetricA[i][0] * lin[0] + kMetricA[i][1] * lin[1] + kMetricA[i][2] * lin[2]) >> 16;   // < 2^32 before the shift
+        c[i] = (int32_t)(cbrt_tab ? cbrt_tab[x] : metric_icbrt(x));
+    }
+    for (int i = 0; i < 3; ++i) {
+        const int32_t v = kMetricB[i][0] * c[0] + kMetricB[i][1] * c[1] + kMetricB[i][2] * c[2];
+        lab[i] = v >= 0 ? v >> 14 : -((-v + 16383) >> 14);   // floor, spelled without a shift of a negative value
+    }
+}
+
+// K <= 256 and every value an integer in [0, 255]: what the metric's table and dp_metric_top2_host take
+inline bool metric_palette_ok(const float *pal_f32, const int K)
+{
+    if (K < 1 || K > 256) return false;
+    for (int i = 0; i < 3 * K; ++i)
+        if (!(pal_f32[i] >= 0.0f && pal_f32[i] <= 255.0f && pal_f32[i] == std::floor(pal_f32[i]))) return false;
+    return true;
+}
+
+// coordinates of the palette under the metric: K x 3 (metric 0: the bytes themselves)
+inline void metric_palette_coords(const float *pal_f32, const int K, const int oklab, int32_t *coords)
+{
+    const uint16_t *ct = oklab ? metric_cbrt_table() : nullptr;
+    for (int k = 0; k < K; ++k) {
+        const uint32_t r = (uint32_t)pal_f32[3 * k], g = (uint32_t)pal_f32[3 * k + 1], b = (uint32_t)pal_f32[3 * k + 2];
+        if (oklab) metric_lab(r, g, b, ct, coords + 3 * k);
+        else coords[3 * k] = (int32_t)r, coords[3 * k + 1] = (int32_t)g, coords[3 * k + 2] = (int32_t)b;
+    }
+}
+
+// The two smallest (d(q, k), k) of n colours, compared as pairs: the lowest index wins on equal distance; K = 1: both 0.
+// d0 / d1 (may be null) receive the two distances.
+inline void metric_top2(const uint8_t *rgb, const int64_t n, const int32_t *coords, const int K, const int oklab, uint8_t *idx0, uint8_t *idx1,
+                        int32_t *d0_out, int32_t *d1_out)
+{
+    const uint16_t *ct = oklab ? metric_cbrt_table() : nullptr;
+    for (int64_t i = 0; i < n; ++i) {
+        int32_t q[3] = {rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]};
+        if (oklab) metric_lab(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], ct, q);
+        int32_t d0 = std::numeric_limits<int32_t>::max(), d1 = d0;
+        int i0 = 0, i1 = 0;
+        for (int k = 0; k < K; ++k) {   // ascending k and strict comparisons: an equal distance never displaces a lower index
+            const int32_t x = q[0] - coords[3 * k], y = q[1] - coords[3 * k + 1], z = q[2] - coords[3 * k + 2];
+            const int32_t d = x * x + y * y + z * z;   // <= 408 098 306
+            if (d < d0) {
+                d1 = d0, i1 = i0;
+                d0 = d, i0 = k;
+            } else if (d < d1) {
+                d1 = d, i1 = k;
+            }
+        }
+        if (K == 1) d1 = d0, i1 = 0;
+        idx0[i] = (uint8_t)i0;
+        idx1[i] = (uint8_t)i1;
+        if (d0_out) d0_out[i] = d0;
+        if (d1_out) d1_out[i] = d1;
+    }
+}
+
+// the ordered decision: nearest iff d0 / (d0 + d1) <= t in IEEE float64, the quotient 0 when the sum is 0
+inline bool metric_takes_nearest(const int32_t d0, const int32_t d1, const float t)
+{
+    const double s = (double)d0 + (double)d1;
+    const double f = s > 0.0 ? (double)d0 / s : 0.0;
+    return f <= (double)t;
+}
+
 }  // namespace dp

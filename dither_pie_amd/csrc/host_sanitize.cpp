@@ -795,10 +795,48 @@ static int run_voidcluster(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- the Oklab colour metric ---------------------------------------------------------------------------------------
+// record: K, n (int32), K * 3 float32 palette values, n float32 thresholds, n * 3 bytes of colours
+static int run_metric(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[2];
+        if (fread(head, sizeof(int32_t), 2, f) != 2 || head[0] < 1 || head[0] > 256 || head[1] < 0 || head[1] > (1 << 20)) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const int K = head[0], n = head[1];
+        std::vector<float> pal((size_t)3 * K), thr((size_t)n);
+        std::vector<uint8_t> rgb((size_t)3 * n);
+        if (fread(pal.data(), sizeof(float), pal.size(), f) != pal.size() || fread(thr.data(), sizeof(float), thr.size(), f) != thr.size() ||
+            fread(rgb.data(), 1, rgb.size(), f) != rgb.size() || !metric_palette_ok(pal.data(), K)) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        std::vector<int32_t> lab((size_t)3 * n), coords((size_t)3 * K), d0((size_t)n), d1((size_t)n);   // exactly what the statements write
+        std::vector<uint8_t> i0((size_t)n), i1((size_t)n);
+        for (int i = 0; i < n; ++i) metric_lab(rgb[3 * (size_t)i], rgb[3 * (size_t)i + 1], rgb[3 * (size_t)i + 2], i & 1 ? metric_cbrt_table() : nullptr, &lab[3 * (size_t)i]);
+        metric_palette_coords(pal.data(), K, 1, coords.data());
+        metric_top2(rgb.data(), n, coords.data(), K, 1, i0.data(), i1.data(), d0.data(), d1.data());
+        printf("lab %d", c);
+        for (int i = 0; i < 3 * n; ++i) printf(" %d", lab[(size_t)i]);
+        printf("\ntop %d", c);
+        for (int i = 0; i < n; ++i) printf(" %u %u %d", (unsigned)i0[(size_t)i], (unsigned)i1[(size_t)i], (int)metric_takes_nearest(d0[(size_t)i], d1[(size_t)i], thr[(size_t)i]));
+        printf("\n");
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -809,6 +847,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "pngfile") return run_pngfile(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "orderedplan") return run_orderedplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "voidcluster") return run_voidcluster(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "metric") return run_metric(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);

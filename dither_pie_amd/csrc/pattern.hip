@@ -6,7 +6,8 @@
 // colours are kept by rank.  The table is built by the library's own nearest-only path (launch_ordered, DP_MODE_NEAREST,
 // brute-force pass + KD-tree fix-up of the ties) over the identity colours, with a copy of the palette record whose output
 // "colours" are the ranks, whose lut_in is dropped and whose accelerator tables are left out (those kernels write the
-// palette colours themselves, not out_rgb): the table is that path, scipy's tie order included.
+// palette colours themselves, not out_rgb): the table is that path, scipy's tie order included.  For a palette with a colour
+// metric (metric.hip) the table is packed from the metric's own top-2 table instead: only nearest(q) changes.
 //
 // pattern_identity_kernel  the colours of 2^22 consecutive table addresses as packed RGB pixels (four per lane)
 // pattern_pack_kernel      byte 0 of each pixel of the nearest-only output -> the table (four per lane, one dword store)
@@ -36,15 +37,6 @@ constexpr size_t kTabBytes = (size_t)DP_PATTERN_TABLE_BYTES;
 constexpr int kBuildSide = 2048;                                   // the table is built in "frames" of 2048 x 2048 colours
 constexpr uint32_t kBuildPx = (uint32_t)kBuildSide * kBuildSide;   // 2^22: four of them
 constexpr size_t kSideBytes = 3 * 256 * sizeof(uint32_t);          // c_rank, out_rank, the ranks by index (build only)
-
-template <bool BRICK>
-__device__ __forceinline__ uint32_t tab_colour(const uint32_t a)   // the inverse: r | g<<8 | b<<16 of table address a
-{
-    if (!BRICK) return a;
-    const uint32_t r = (((a >> 6) & 63u) << 2) | (a & 3u), g = (((a >> 12) & 63u) << 2) | ((a >> 2) & 3u),
-                   b = (((a >> 18) & 63u) << 2) | ((a >> 4) & 3u);
-    return r | (g << 8) | (b << 16);
-}
 
 // px: kBuildPx packed RGB pixels, 4-byte aligned; pixel i = the colour of table address a0 + i
 template <bool BRICK>
@@ -298,11 +290,14 @@ int pattern_ensure_table(const dp_palette *pal_c, hipStream_t s)
     const uint32_t *side_dev = reinterpret_cast<const uint32_t *>(tab + kTabBytes);
     hipError_t e = hipMemcpy(tab + kTabBytes, side.data(), kSideBytes, hipMemcpyHostToDevice);
     int rc = e == hipSuccess ? DP_OK : hip_fail(e, "pattern table upload");
-    const int brick = exp_env("DP_PATTERN_PLAIN") ? 0 : 1;
+    const int brick = (exp_env("DP_PATTERN_PLAIN") && p->metric == 0) ? 0 : 1;
     if (rc == DP_OK) {
         if (K == 1) {   // every colour maps to the one entry, rank 0
             e = hipMemsetAsync(tab, 0, kTabBytes, s);
             if (e != hipSuccess) rc = hip_fail(e, "pattern table memset");
+        } else if (p->metric != 0) {   // a metric palette (metric.hip): nearest(q) is its top-2 table's, one pack kernel; bricks always
+            rc = metric_ensure_table_locked(p, s);
+            if (rc == DP_OK) rc = launch_metric_rank_table(p->met, side_dev + 512, tab, s);
         } else {
             d.lut_in = nullptr;
             d.out_rgb = side_dev + 512;

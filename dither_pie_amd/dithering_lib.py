@@ -287,10 +287,13 @@ def _device_index():
     return torch.cuda.current_device() if torch.cuda.is_available() else -1
 
 
-def _device_palette(pal_f32, out_colors, lut_in):
+METRICS = ("rgb", "oklab")   # ImageDitherer(metric=...): how "nearest" is measured (include/ditherpie_hip_metric.h)
+
+
+def _device_palette(pal_f32, out_colors, lut_in, metric="rgb"):
     from . import backend
-    key = (_device_index(), pal_f32.tobytes(), out_colors.tobytes(), None if lut_in is None else lut_in.tobytes())
-    return _PALETTES.get_or_make(key, lambda: backend.Palette(pal_f32, out_colors, lut_in))
+    key = (_device_index(), pal_f32.tobytes(), out_colors.tobytes(), None if lut_in is None else lut_in.tobytes(), metric)
+    return _PALETTES.get_or_make(key, lambda: backend.Palette(pal_f32, out_colors, lut_in, metric=metric))
 
 
 def _device_index_map(out_colors):
@@ -375,7 +378,8 @@ def _decode(out_frame, palette_arr):
 
 # ------------------------------------------------------------------------------------- strategies
 class BaseDitherStrategy:
-    """dithering_lib.py:313-330: dither(pixels [N,3] f32, palette_arr [K,3] f32, (h, w)) -> [N,3]."""
+    """dithering_lib.py:313-330: dither(pixels [N,3] f32, palette_arr [K,3] f32, (h, w)) -> [N,3].  This strategy-level
+    call is the reference's and always searches in RGB; a colour metric is a property of ImageDitherer (metric="oklab")."""
 
     def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
         raise NotImplementedError
@@ -797,7 +801,8 @@ class OstromoukhovDitherStrategy(_VariableDiffuser):
 
 # ------------------------------------------------------------------------------------- palettes
 class ColorReducer:
-    """Palette producers (dithering_lib.py:1807-1872)."""
+    """Palette producers (dithering_lib.py:1807-1872).  They cut and cluster in RGB whatever metric the ditherer that uses the
+    palette has (ImageDitherer(metric="oklab") changes the search, not the palette)."""
 
     @staticmethod
     def find_dominant_channel(colors: List[Tuple[int, int, int]]) -> int:
@@ -1468,6 +1473,9 @@ class CellPaletteDitherStrategy(BaseDitherStrategy):
 # strategy instances (ImageDitherer(dither_mode=<instance>)) that are per-pixel independent given global coordinates, as
 # ORDERED_MODES are among the enum members: these shard by row bands / tiles (sharding.dither_band)
 ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
+# ... and the strategies that run on a palette with a colour metric (ImageDitherer(metric="oklab")): those whose searches go
+# through the palette's top-2 table (backend.ordered in nearest and matrix mode) or its rank table (pattern, dotdiff)
+_METRIC_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, PatternDitherStrategy, DotDiffusionDitherStrategy)
 
 
 # ------------------------------------------------------------------------------------- ImageDitherer
@@ -1489,14 +1497,23 @@ class ImageDitherer:
         DitherMode.RIEMERSMA: RiemersmaDitherStrategy,
     }
 
+    metric = "rgb"   # (the class default: an object pickled before the attribute existed reads as "rgb")
+
     def __init__(self, num_colors: int = 16, dither_mode: Optional[DitherMode] = DitherMode.BAYER,
                  palette: Optional[List[Tuple[int, int, int]]] = None, use_gamma: bool = False,
-                 dither_params: Optional[Dict[str, Any]] = None):
+                 dither_params: Optional[Dict[str, Any]] = None, metric: str = "rgb"):
+        """metric (an addition to the reference's interface): "rgb", the reference's squared Euclidean RGB distance, or "oklab",
+        the integer Oklab of include/ditherpie_hip_metric.h -- for NONE, BAYER, BLUE_NOISE, POLKA_DOT, any MatrixDitherStrategy
+        instance, PatternDitherStrategy and DotDiffusionDitherStrategy; every other mode, and use_gamma=True (Oklab linearises
+        by itself), raise ValueError with it.  The palette producers (median cut, k-means) and the strategy-level
+        dither(pixels, palette_arr, size) stay RGB."""
         self.num_colors = num_colors
         self.dither_mode = dither_mode
         self.palette = palette
         self.use_gamma = use_gamma
         self.dither_params = dither_params or {}
+        self.metric = metric
+        self._check_metric(None)
 
     @staticmethod
     def get_mode_parameters(mode: DitherMode) -> Optional[Dict[str, Any]]:
@@ -1534,6 +1551,25 @@ class ImageDitherer:
         settings.update(self.dither_params)
         return cls(**settings)
 
+    def _check_metric(self, strategy):
+        """The metric of this ditherer, checked against use_gamma and (when given) the strategy: before any launch."""
+        metric = self.metric
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+        if metric == "rgb":
+            return metric
+        if self.use_gamma:
+            raise ValueError(f"use_gamma=True cannot be combined with the {metric!r} metric: Oklab linearises by itself")
+        if strategy is not None and not isinstance(strategy, _METRIC_STRATEGIES):
+            name = self.dither_mode.value if isinstance(self.dither_mode, DitherMode) else type(strategy).__name__
+            raise ValueError(f"dither mode {name!r} does not support the {metric!r} metric (supported: none, bayer, blue_noise, "
+                             "polka_dot, MatrixDitherStrategy instances, PatternDitherStrategy, DotDiffusionDitherStrategy)")
+        return metric
+
+    def _palette_on_device(self, strategy=None):
+        metric = self._check_metric(strategy)
+        return _device_palette(*prepare_palette(self.palette, self.use_gamma), metric)
+
     # -- host plumbing ------------------------------------------------------------------------
     def _ensure_palette(self, first_frame_u8: np.ndarray):
         """palette=None: median cut of the (linearised, when gamma is on) image, kept on the object
@@ -1553,9 +1589,10 @@ class ImageDitherer:
             first = frames if frames.dim() == 3 else frames[0]
             self._ensure_palette(first.cpu().numpy())
         strategy = self._get_dither_strategy(self.dither_mode)
+        self._check_metric(strategy)
         import torch
         with torch.cuda.device(frames.device):  # palette, thresholds and launches on the device that holds the frames
-            pal = _device_palette(*prepare_palette(self.palette, self.use_gamma))
+            pal = self._palette_on_device(strategy)
             return strategy._run(frames, pal, y0=y0, x0=x0, out=out)
 
     def apply_dithering_frames_indexed(self, frames, y0: int = 0, x0: int = 0, out=None):
@@ -1635,8 +1672,10 @@ class ImageDitherer:
             raise ValueError("prepare() needs an explicit palette")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         with torch.cuda.device(dev):
-            pal = _device_palette(*prepare_palette(self.palette, self.use_gamma))
-            if accel:
+            pal = self._palette_on_device()
+            if accel and pal.metric != "rgb":
+                pal.metric_prepare()   # a metric palette's table is its accelerator
+            elif accel:
                 pal.build_accel()
         return self
 
