@@ -210,6 +210,13 @@ _SIGS_METRIC = {
     "dp_metric_top2_host": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
 }
 EXPORTS_METRIC = tuple(_SIGS_METRIC)
+# include/ditherpie_hip_idiff.h: integer error diffusion (the classical scans in sixteenths, searched through the palette's
+# nearest table under either metric); a table of its own for the same reason.
+_SIGS_IDIFF = {
+    "dp_idiff_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "dp_idiff_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+}
+EXPORTS_IDIFF = tuple(_SIGS_IDIFF)
 
 
 def build(force=False):
@@ -255,7 +262,7 @@ def load():
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
                                           + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
-                                          + list(_SIGS_METRIC.items())):
+                                          + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -62,7 +62,7 @@ class Palette:
     def __init__(self, pal_f32, out_colors, lut_in=None, accel=False, metric="rgb"):
         """metric: "rgb" (squared Euclidean RGB distance, the reference's) or "oklab" (include/ditherpie_hip_metric.h: an
         integer Oklab, at most 256 colours, integer palette values, no lut_in).  A metric palette is searched through its own
-        top-2 table only: ordered(), pattern() and dotdiff() use it, every other mode refuses it."""
+        top-2 table only: ordered(), pattern(), dotdiff() and idiff() use it, every other mode refuses it."""
         if metric not in METRICS:
             raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
         if metric != "rgb" and lut_in is not None:
@@ -492,7 +492,59 @@ def dotdiff(frames, pal: Palette, classes, strength256, out=None):
     return out.view(frames.shape)
 
 
-VOID_CLUSTER_SIZES = (8, 128)        # h and w of a void-and-cluster matrix (include/ditherpie_hip_voidcluster.h), inclusive
+IDIFF_MAX_TAPS = 12   # DP_IDIFF_MAX_TAPS
+
+
+def _idiff_taps(taps, divisor, strength256):
+    """The argument rules of dp_idiff_u8 (include/ditherpie_hip_idiff.h) as ValueError -> (dx, dy, weight) int32 arrays."""
+    try:
+        t = [(int(a), int(b), int(c)) for a, b, c in taps]
+        exact = all(a == ta and b == tb and c == tc for (a, b, c), (ta, tb, tc) in zip(t, taps))
+    except (TypeError, ValueError):
+        raise ValueError("integer error diffusion: taps must be (dx, dy, weight) triples of integers") from None
+    if not exact:
+        raise ValueError("integer error diffusion: taps must be (dx, dy, weight) triples of integers")
+    if not 1 <= len(t) <= IDIFF_MAX_TAPS:
+        raise ValueError(f"integer error diffusion takes 1 .. {IDIFF_MAX_TAPS} taps, not {len(t)}")
+    if not (isinstance(divisor, (int, np.integer)) and 1 <= divisor < 2 ** 31):
+        raise ValueError(f"integer error diffusion: the divisor must be an integer >= 1, not {divisor!r}")
+    if not (isinstance(strength256, (int, np.integer)) and 0 <= strength256 <= 256):
+        raise ValueError(f"integer error diffusion strength256 must be an integer in 0 .. 256, not {strength256!r}")
+    for dx, dy, wt in t:
+        if not (0 <= dy <= 2 and -2 <= dx <= 2 and (dy > 0 or dx >= 1)):
+            raise ValueError(f"integer error diffusion: tap (dx={dx}, dy={dy}) is outside dy 0 .. 2, dx -2 .. 2, dy == 0 with dx >= 1")
+        if wt < 0:
+            raise ValueError(f"integer error diffusion: tap (dx={dx}, dy={dy}) has the negative weight {wt}")
+    if len({(dx, dy) for dx, dy, _ in t}) != len(t):
+        raise ValueError("integer error diffusion: a (dx, dy) is given twice")
+    if sum(wt for _, _, wt in t) > divisor:
+        raise ValueError(f"integer error diffusion: the weights sum to more than the divisor {divisor}")
+    return tuple(np.array([x[i] for x in t], np.int32) for i in range(3))
+
+
+def idiff(frames, pal: Palette, taps, divisor, strength256, out=None):
+    """Integer error diffusion (include/ditherpie_hip_idiff.h) of uint8 frames already in HBM -> uint8 frames: the raster scan
+    with the taps [(dx, dy, weight)] over `divisor` in sixteenths, the nearest colour from the palette's 2^24-entry table
+    (shared with pattern() and dotdiff(); Palette.pattern_prepare() builds it ahead) -- under the palette's metric.
+    strength256 0 .. 256; at most 256 colours; `out` must not be the frames."""
+    dx, dy, wt = _idiff_taps(taps, divisor, strength256)
+    if pal.K > 256:
+        raise ValueError(f"integer error diffusion supports at most 256 colours, the palette has {pal.K}")
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    out = _check_out(out, f)
+    if n and out.data_ptr() == f.data_ptr():
+        raise ValueError("integer error diffusion does not work in place: out must not be the frames")
+    _check_palette_device(pal, f)
+    L = _lib.load()
+    ws_bytes = L.dp_idiff_workspace_bytes(n, h, w)
+    with torch.cuda.device(f.device), _Launch(f.device, ws_bytes) as ws:
+        check(L.dp_idiff_u8(f.data_ptr(), out.data_ptr(), n, h, w, pal._h, _np_ptr(dx), _np_ptr(dy), _np_ptr(wt), len(dx), int(divisor),
+                            int(strength256), ws.data_ptr(), ws.numel(), _stream()))
+    return out.view(frames.shape)
+
+
+VOID_CLUSTER_SIZES = (8, 128)       # h and w of a void-and-cluster matrix (include/ditherpie_hip_voidcluster.h), inclusive
 VOID_CLUSTER_SIGMA256 = (256, 768)   # its sigma in 1/256, inclusive
 
 

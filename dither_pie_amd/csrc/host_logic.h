@@ -2537,6 +2537,52 @@ inline void dotdiff_schedule(const int *level, const int m, const int reach, Dot
     for (int i = at; i < kDotDiffMaxCells; ++i) s.order[i] = 0;
 }
 
+// ---- Integer error diffusion: the taps of a scan (idiff.hip, include/ditherpie_hip_idiff.h) --------------------------------
+//
+// A tap (dx, dy, weight) hands weight / divisor of a pixel's error to the pixel dx to the right and dy below.  The kernel
+// works with q = floor(weight * strength256 * 256 / divisor), the share in 1/65536, and walks a band of rows on an
+// anti-diagonal: the row below trails by `skew` columns, the smallest s >= 1 with s * dy + dx >= 1 for every tap of a later
+// row, so that every source of a pixel is finished at least one step before the pixel.
+constexpr int kIdiffMaxTaps = 12;
+
+struct IdiffPlan {
+    int n, skew;
+    int dx[kIdiffMaxTaps], dy[kIdiffMaxTaps];
+    uint32_t q[kIdiffMaxTaps];   // sum <= 65536
+};
+
+// 0, or which rule of the header the arguments break: 1 a NULL array, 2 n_taps outside 1 .. 12, 3 divisor < 1, 4 strength256
+// outside 0 .. 256, 5 a tap outside dy 0 .. 2, dx -2 .. 2, dy == 0 => dx >= 1, 6 a (dx, dy) twice, 7 a negative weight,
+// 8 weights that sum to more than the divisor.  The plan is complete only with 0.
+inline int idiff_plan(const int32_t *dx, const int32_t *dy, const int32_t *weight, const int n_taps, const int divisor, const int strength256,
+                      IdiffPlan &p)
+{
+    p = IdiffPlan{};
+    if (n_taps < 1 || n_taps > kIdiffMaxTaps) return 2;
+    if (!dx || !dy || !weight) return 1;
+    if (divisor < 1) return 3;
+    if (strength256 < 0 || strength256 > 256) return 4;
+    int64_t sum = 0;
+    bool seen[3][5] = {};
+    for (int k = 0; k < n_taps; ++k) {
+        if (dy[k] < 0 || dy[k] > 2 || dx[k] < -2 || dx[k] > 2 || (dy[k] == 0 && dx[k] < 1)) return 5;
+        if (seen[dy[k]][dx[k] + 2]) return 6;
+        seen[dy[k]][dx[k] + 2] = true;
+        if (weight[k] < 0) return 7;
+        sum += weight[k];
+    }
+    if (sum > divisor) return 8;
+    p.n = n_taps;
+    p.skew = 1;
+    for (int k = 0; k < n_taps; ++k) {
+        p.dx[k] = dx[k];
+        p.dy[k] = dy[k];
+        p.q[k] = (uint32_t)((int64_t)weight[k] * strength256 * 256 / divisor);   // weight <= divisor: at most 65536
+        while (dy[k] >= 1 && p.skew * dy[k] + dx[k] < 1) ++p.skew;                // (at most 3: dx >= -2)
+    }
+    return 0;
+}
+
 // ---- Cell-palette dithering: the candidates of a cell and the perturbation (cells.hip, include/ditherpie_hip_cells.h) ------
 //
 // Every cell may show `colours` = k entries of its choice besides the entries of `fixed`.  The candidates are enumerated

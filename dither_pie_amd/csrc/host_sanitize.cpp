@@ -833,10 +833,41 @@ static int run_metric(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- integer error diffusion: the tap plan ---------------------------------------------------------------------------
+// record: n_taps, divisor, strength256 (int32), then n_taps dx, n_taps dy, n_taps weights (int32)
+static int run_idiffplan(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[3];
+        if (fread(head, sizeof(int32_t), 3, f) != 3 || head[0] > 64) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const size_t n = head[0] > 0 ? (size_t)head[0] : 0;
+        std::vector<int32_t> dx(n), dy(n), wt(n);   // exactly as many as the plan may read
+        if (fread(dx.data(), sizeof(int32_t), n, f) != n || fread(dy.data(), sizeof(int32_t), n, f) != n || fread(wt.data(), sizeof(int32_t), n, f) != n) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        IdiffPlan p;
+        const int rc = idiff_plan(dx.data(), dy.data(), wt.data(), head[0], head[1], head[2], p);
+        printf("idiff %d %d %d %d", c, rc, p.n, p.skew);
+        for (int k = 0; k < p.n; ++k) printf(" %u", (unsigned)p.q[k]);
+        printf("\n");
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  idiffplan <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -850,6 +881,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "metric") return run_metric(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

@@ -84,6 +84,7 @@ __all__ = [
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
     "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "CellPaletteDitherStrategy",
+    "IntegerErrorDiffusionDitherStrategy",
     "generate_blue_noise", "generate_void_and_cluster", "VoidAndClusterDitherStrategy",
 ]
 
@@ -1331,6 +1332,84 @@ class DotDiffusionDitherStrategy(BaseDitherStrategy):
             return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
 
 
+# ------------------------------------------------------------------------------------- Integer error diffusion (table scans)
+class IntegerErrorDiffusionDitherStrategy(BaseDitherStrategy):
+    """The classical raster-scan error diffusers (ErrorDiffusionKernel's eight tap sets) in integer arithmetic: values in
+    sixteenths, every share truncated on its own, the nearest colour from the palette's exact 2^24-entry table (idiff.hip;
+    include/ditherpie_hip_idiff.h has the definition).  The search costs the same for 2 and for 256 colours, and because the
+    table serves either metric this is the scan for ImageDitherer(metric="oklab") -- "Floyd-Steinberg, but perceptual".
+    DitherMode.ERROR_DIFFUSION stays the reference's float scan, bit for bit; this mode is close to it, not identical, and has
+    no serpentine.  Errors cross every band a caller could cut, so _run refuses (y0, x0) as the scans do.
+
+    variant: a name of ErrorDiffusionKernel (an unknown name falls back to Floyd-Steinberg as in the reference; anything but
+    a string is a ValueError).  strength256 = round(strength * 256).  Not in the reference and not a DitherMode member: pass
+    an instance as ImageDitherer(dither_mode=...), or use dither_frames().  A strength outside [0, 1] and a palette of more
+    than 256 colours raise ValueError at dither time."""
+
+    @staticmethod
+    def get_parameter_info() -> Dict[str, Any]:
+        return {
+            'variant': {'type': 'choice', 'default': 'floyd_steinberg', 'choices': ErrorDiffusionKernel.list_kernels(),
+                        'label': 'Algorithm', 'description': 'Error diffusion algorithm variant'},
+            'strength': {'type': 'float', 'default': 1.0, 'min': 0.0, 'max': 1.0, 'step': 0.05, 'label': 'Strength',
+                         'description': 'Share of a pixel\'s error handed to its neighbours (0 = nearest colour)'},
+        }
+
+    def __init__(self, variant: str = "floyd_steinberg", strength: float = 1.0):
+        self.variant = variant
+        self.strength = strength
+
+    def get_current_parameters(self) -> Dict[str, Any]:
+        return {'variant': self.variant, 'strength': self.strength}
+
+    def _settings(self):
+        """-> (taps [(dx, dy, weight)], divisor, strength256)."""
+        if not isinstance(self.variant, str):
+            raise ValueError(f"integer error diffusion variant must be a name of {ErrorDiffusionKernel.list_kernels()}, "
+                             f"not {self.variant!r}")
+        kernel = ErrorDiffusionKernel.get_kernel(self.variant)
+        try:
+            s256 = int(round(float(self.strength) * 256))
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"integer error diffusion strength must be a number in [0, 1], not {self.strength!r}") from None
+        if not 0 <= s256 <= 256:
+            raise ValueError(f"integer error diffusion strength must lie in [0, 1], not {self.strength!r}")
+        return [tuple(int(v) for v in t) for t in kernel["weights"]], int(kernel["divisor"]), s256
+
+    def _run(self, frames, pal, y0=0, x0=0, out=None):
+        from . import backend
+        if y0 or x0:
+            raise ValueError("integer error diffusion hands errors across every band edge and cannot be tiled by the caller")
+        taps, divisor, s256 = self._settings()
+        return backend.idiff(frames, pal, taps, divisor, s256, out=out)
+
+    def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
+        h, w = image_size
+        if h <= 0 or w <= 0:
+            raise ValueError(f"integer error diffusion needs a non-empty image, not {h} x {w}")
+        self._settings()
+        if len(palette_arr) > 256:
+            raise ValueError(f"integer error diffusion supports at most 256 colours, the palette has {len(palette_arr)}")
+        out = self._run(_pixels_to_frame(pixels, image_size), _index_palette(palette_arr))
+        return _decode(out, palette_arr)
+
+    def dither_frames(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """uint8 CUDA tensor [N,H,W,3] (or [H,W,3]) -> dithered uint8 CUDA tensor of the same shape, each frame as
+        ImageDitherer(dither_mode=self, palette=palette, use_gamma=use_gamma).apply_dithering would dither it (palette:
+        the reference's list of RGB triples).  Frames stay in HBM; `out` must not be the frames."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            pal = _device_palette(*prepare_palette(palette, use_gamma))
+            return self._run(frames_u8_cuda, pal, out=out)
+
+    def dither_frames_indexed(self, frames_u8_cuda, palette, use_gamma: bool = False, out=None):
+        """dither_frames() as palette-index planes: -> (planes [N,H,W] (or [H,W]), palette_u8 [K,3]) with
+        palette_u8[planes] == dither_frames(...); torch.uint8 (at most 256 colours)."""
+        import torch
+        with torch.cuda.device(frames_u8_cuda.device):
+            return _indexed(self.dither_frames(frames_u8_cuda, palette, use_gamma), palette, use_gamma, out)
+
+
 # ------------------------------------------------------------------------------------- Cell palettes (k colours per cell)
 class CellPaletteDitherStrategy(BaseDitherStrategy):
     """Cell-palette dithering: the picture is cut into small cells and every cell may show only a few of the palette's
@@ -1474,8 +1553,9 @@ class CellPaletteDitherStrategy(BaseDitherStrategy):
 # ORDERED_MODES are among the enum members: these shard by row bands / tiles (sharding.dither_band)
 ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
 # ... and the strategies that run on a palette with a colour metric (ImageDitherer(metric="oklab")): those whose searches go
-# through the palette's top-2 table (backend.ordered in nearest and matrix mode) or its rank table (pattern, dotdiff)
-_METRIC_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, PatternDitherStrategy, DotDiffusionDitherStrategy)
+# through the palette's top-2 table (backend.ordered in nearest and matrix mode) or its rank table (pattern, dotdiff, idiff)
+_METRIC_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, PatternDitherStrategy, DotDiffusionDitherStrategy,
+                      IntegerErrorDiffusionDitherStrategy)
 
 
 # ------------------------------------------------------------------------------------- ImageDitherer
@@ -1504,7 +1584,7 @@ class ImageDitherer:
                  dither_params: Optional[Dict[str, Any]] = None, metric: str = "rgb"):
         """metric (an addition to the reference's interface): "rgb", the reference's squared Euclidean RGB distance, or "oklab",
         the integer Oklab of include/ditherpie_hip_metric.h -- for NONE, BAYER, BLUE_NOISE, POLKA_DOT, any MatrixDitherStrategy
-        instance, PatternDitherStrategy and DotDiffusionDitherStrategy; every other mode, and use_gamma=True (Oklab linearises
+        instance, PatternDitherStrategy, DotDiffusionDitherStrategy and IntegerErrorDiffusionDitherStrategy; every other mode, and use_gamma=True (Oklab linearises
         by itself), raise ValueError with it.  The palette producers (median cut, k-means) and the strategy-level
         dither(pixels, palette_arr, size) stay RGB."""
         self.num_colors = num_colors
@@ -1532,8 +1612,8 @@ class ImageDitherer:
         """Defaults from get_parameter_info() overlaid by dither_params (dithering_lib.py:1918-1950);
         unknown mode -> ValueError, unknown parameter -> TypeError from the constructor.  An addition to the reference's
         interface: a BaseDitherStrategy INSTANCE as the mode is returned as it is (dither_params do not apply to it) --
-        how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, CellPaletteDitherStrategy,
-        VoidAndClusterDitherStrategy, HalftoneDitherStrategy, WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
+        how modes without a DitherMode member (PatternDitherStrategy, DotDiffusionDitherStrategy, IntegerErrorDiffusionDitherStrategy,
+        CellPaletteDitherStrategy, VoidAndClusterDitherStrategy, HalftoneDitherStrategy, WaveletDitherStrategy) reach every ImageDitherer / VideoProcessor path."""
         if isinstance(mode, BaseDitherStrategy):
             return mode
         if mode in _OUT_OF_SCOPE:
@@ -1563,7 +1643,8 @@ class ImageDitherer:
         if strategy is not None and not isinstance(strategy, _METRIC_STRATEGIES):
             name = self.dither_mode.value if isinstance(self.dither_mode, DitherMode) else type(strategy).__name__
             raise ValueError(f"dither mode {name!r} does not support the {metric!r} metric (supported: none, bayer, blue_noise, "
-                             "polka_dot, MatrixDitherStrategy instances, PatternDitherStrategy, DotDiffusionDitherStrategy)")
+                             "polka_dot, MatrixDitherStrategy instances, PatternDitherStrategy, DotDiffusionDitherStrategy, "
+                             "IntegerErrorDiffusionDitherStrategy)")
         return metric
 
     def _palette_on_device(self, strategy=None):

@@ -24,7 +24,8 @@
  *             f = double(d0) / (double(d0) + double(d1)), f = 0 when the sum is 0; the pixel takes nearest iff f <= double(t),
  *             else second; the output bytes are out_colors[index].
  *
- * What a metric palette means to the rest of the library: dp_pattern_u8, dp_pattern_prepare and dp_dotdiff_u8 use the metric
+ * What a metric palette means to the rest of the library: dp_pattern_u8, dp_pattern_prepare, dp_dotdiff_u8 and dp_idiff_u8
+ * (ditherpie_hip_idiff.h: the scan error diffusion that takes a metric palette) use the metric
  * (their definitions stay as they are, only nearest(q) changes; their rank table is derived from the table below, 16 MiB
  * more); dp_palette_build_accel returns DP_OK and builds nothing; every other entry point that searches a palette
  * (dp_ordered_u8, dp_error_diffusion_u8, dp_error_diffusion_numba_u8, dp_hybrid_numba_u8, dp_riemersma_u8, dp_halftone_u8,
