@@ -55,6 +55,47 @@ def skew(taps):
     return s
 
 
+WINDOW = [(1, 0), (2, 0)] + [(dx, dy) for dy in (1, 2) for dx in range(-2, 3)]   # the 12 positions a tap may take
+N_RANDOM_CASES = 12
+
+
+def tap_cases():
+    """A fixed list of (taps, divisor, strength256) beyond the eight variants: what the plan accepts and no named variant has.
+    The first part is written by hand; N_RANDOM_CASES sets from numpy.random.RandomState(7) follow (a random subset of WINDOW
+    in window order, weights 0 .. 8, the divisor their sum plus 0 .. 2 and at least 1, strength 256)."""
+    cases = [
+        ([(1, 0, 1)], 1, 256),                                          # one tap: the whole error goes right, nothing leaves a row
+        ([(2, 0, 1)], 1, 256),                                          # no dx = 1 tap: two interleaved chains per row
+        ([(0, 1, 1)], 1, 256),                                          # straight down, skew 1: columns never meet
+        ([(0, 2, 1)], 1, 256),                                          # rows 0 and 1 of a band read only the two rows above it
+        ([(-1, 2, 1)], 1, 256),                                         # skew 1 with a left-pointing tap: finished one step earlier
+        ([(-2, 2, 1)], 1, 256),                                         # skew 2 from a dy = 2 tap alone
+        ([(-2, 1, 1)], 1, 256),                                         # skew 3 from one tap
+        ([(-2, 1, 1), (2, 2, 1)], 2, 256),                              # skew * dy + dx = 8, the ring depth, in the 4-slot instance
+        ([(1, 0, 7), (0, 1, 5), (1, 1, 3), (0, 2, 1)], 16, 256),        # skew 1 with four taps: no spare slot
+        ([(2, 1, 1), (2, 2, 1)], 2, 256),                               # no (1, 0) tap, skew 1, both taps reach past the row's end
+        ([(1, 0, 5), (2, 0, 3), (-1, 1, 2), (0, 1, 4), (1, 2, 2)], 16, 256),   # 5 taps: the 7-slot instance with two spare slots
+        ([(2, 0, 1), (-1, 1, 1), (0, 1, 1), (1, 1, 1), (0, 2, 1), (2, 2, 1)], 8, 256),   # 6 taps, no (1, 0), a quarter dropped
+        ([(1, 0, 4), (2, 0, 3), (0, 1, 3), (1, 1, 2), (2, 1, 1), (0, 2, 2), (1, 2, 1)], 16, 256),   # 7 taps at skew 1: no spare slot
+        ([(1, 0, 4), (2, 0, 2), (0, 1, 4), (1, 1, 2), (2, 1, 1), (-1, 2, 1), (0, 2, 1), (1, 2, 1)], 16, 256),   # 8 taps at skew 1: 12 slots
+        ([(1, 0, 4), (2, 0, 2), (-1, 1, 2), (0, 1, 4), (1, 1, 2), (2, 1, 1), (-1, 2, 1), (0, 2, 2), (1, 2, 1)], 20, 256),   # 9 taps, skew 2
+        ([(1, 0, 8), (2, 0, 4), (-1, 1, 4), (0, 1, 8), (1, 1, 4), (2, 1, 2), (-2, 2, 1), (-1, 2, 2), (0, 2, 4), (1, 2, 2)], 42, 256),   # 10, skew 2
+        ([t for t in KERNELS["jjn"][0] if t[:2] != (-2, 2)], 48, 256),  # 11 taps: one spare slot of the 12-slot instance, skew 3
+        ([(dx, dy, 1) for dx, dy in WINDOW], 12, 256),                  # all 12 positions with equal weights
+        ([(1, 0, 7), (0, 1, 5), (1, 1, 4), (-2, 1, 0)], 16, 256),       # a zero-weight tap: it raises the skew to 3 and moves nothing
+        ([(1, 0, 1), (0, 1, 1), (1, 1, 1)], 1000, 256),                 # weights summing to 3 over 1000: shares of 65 / 65536
+        (KERNELS["floyd_steinberg"][0], 16, 255),                       # strength 255: every share one 256th short
+    ]
+    rs = np.random.RandomState(7)
+    for _ in range(N_RANDOM_CASES):
+        n = int(rs.randint(1, MAX_TAPS + 1))
+        where = sorted(rs.permutation(len(WINDOW))[:n].tolist())
+        weights = rs.randint(0, 9, n).tolist()
+        divisor = max(1, sum(weights) + int(rs.randint(0, 3)))
+        cases.append(([WINDOW[p] + (wt,) for p, wt in zip(where, weights)], divisor, 256))
+    return cases
+
+
 def idiff_indices(orc, img, pal_f32, out_colors, lut_in, taps, divisor, strength256, want_acc=False):
     """img [H,W,3] uint8 -> the chosen palette index per pixel [H,W] (int64) (and the largest |acc| seen)."""
     img = np.ascontiguousarray(img, np.uint8)

@@ -6,6 +6,14 @@ than one group.  Here every batch needs several, through the product path (dl.*S
 byte-bounded cases assert through the size queries that the batch really is split, and every frame of every batch is
 compared -- with the CPU restatement, or (4K wavelet) with the single-frame call and the reference's recorded hash.
 
+The launchers of pattern dithering, dot diffusion, cell palettes, the Oklab ordered kernel and integer error diffusion loop
+over groups of 65535 frames as well and re-derive their input, output, `sets` and workspace pointers per group: each gets
+65535 + 7 frames here, against its statement (pattern_ref, dotdiff_ref, cells_ref, metric_ref, idiff_ref).  The `sets` plane
+of the cells and the workspace of the integer diffusion (32 w bytes per frame, the one of these with a per-frame workspace)
+are carved from a guarded arena (tests/arena.py) at exactly their size, so a group that starts at the wrong offset either
+shows in a frame or in a guard.  dp_ordered_u8 (the RGB ordered kernel) had no test with more than 65535 frames either; it
+splits by pixels, not by frames (2^30 per launch), and gets the same batch.
+
 Grid-bounded batches repeat 64 distinct frames (the group sizes are not multiples of 64, so a whole-group offset error
 cannot map a frame onto an equal one)."""
 import ctypes as C
@@ -16,7 +24,13 @@ import os
 import numpy as np
 import pytest
 
+import arena as ar
+import cells_ref
+import dotdiff_ref
 import halftone_ref
+import idiff_ref
+import metric_ref
+import pattern_ref
 import riemersma_ref
 import wavelet_ref as wr
 from conftest import GOLDEN
@@ -174,3 +188,150 @@ def test_riemersma_seventy_thousand_frames(orc):
     P = backend.Palette(*orc.prepare_palette(pal, False))
     got = backend.riemersma(torch.from_numpy(frames).cuda(), P).cpu().numpy()
     _assert_every_frame(got, refs, f"riemersma {n} x {h}x{w}")
+
+
+# ------------------------------------------------------------------------------------------------ the table kernels
+N_TABLE = 65535 + 7
+MODE_NEAREST, MODE_MATRIX = 0, 1
+
+
+def _table_palette(orc, seed):
+    from dither_pie_amd import backend
+    spec = orc.prepare_palette(orc.palr(16, seed), False)
+    return spec, backend.Palette(*spec)
+
+
+@pytest.mark.parametrize("matrix,y0,x0", [(4, 1, 2), (8, 0, 0)])
+def test_pattern_in_groups_of_65535_frames(orc, matrix, y0, x0):
+    import torch
+    from dither_pie_amd import backend
+    n, h, w = N_TABLE, 2, 3
+    assert 65535 % PERIOD != 0
+    spec, P = _table_palette(orc, 21)
+    base = _base(orc, h, w, 900)
+    refs = pattern_ref.pattern_frames(orc, base, *spec, matrix, 128, y0=y0, x0=x0)
+    assert len(np.unique(refs.reshape(PERIOD, -1), axis=0)) > PERIOD // 2         # the frames differ: an offset error shows
+    got = backend.pattern(torch.from_numpy(_tile(base, n)).cuda(), P, matrix, 128, y0=y0, x0=x0).cpu().numpy()
+    _assert_every_frame(got, refs, f"pattern {matrix} {n} x {h}x{w}")
+
+
+def test_dot_diffusion_in_groups_of_65535_frames(orc):
+    import torch
+    from dither_pie_amd import backend
+    n, h, w = N_TABLE, 2, 3
+    assert 65535 % PERIOD != 0
+    spec, P = _table_palette(orc, 22)
+    base = _base(orc, h, w, 1000)
+    refs = dotdiff_ref.dotdiff_frames(orc, base, *spec, dotdiff_ref.KNUTH, 256)
+    assert len(np.unique(refs.reshape(PERIOD, -1), axis=0)) > PERIOD // 2
+    got = backend.dotdiff(torch.from_numpy(_tile(base, n)).cuda(), P, dotdiff_ref.KNUTH, 256).cpu().numpy()
+    _assert_every_frame(got, refs, f"dot diffusion {n} x {h}x{w}")
+
+
+def test_cells_and_their_sets_plane_in_groups_of_65535_frames(orc):
+    """(5, 6) frames in 4 x 4 cells: four cells per frame, three of them partial.  The sets plane is a region of a guarded arena,
+    exactly 2 bytes per cell long and 2-byte aligned, no better."""
+    import torch
+    from dither_pie_amd import backend
+    n, h, w = N_TABLE, 5, 6
+    assert 65535 % PERIOD != 0
+    spec, P = _table_palette(orc, 23)
+    base = _base(orc, h, w, 1100)
+    refs, ref_sets = cells_ref.cells_frames(base, *spec, 4, 4, 2, 0, [0xFFFF], 4, 64)
+    assert ref_sets.shape == (PERIOD, 2, 2) and len(np.unique(ref_sets.reshape(PERIOD, -1), axis=0)) > PERIOD // 2
+    g = ar.MIN_GUARD
+    A = ar.Arena(ar.capacity_for([(2 * 4 * n, g)]), "cuda", 41)
+    A.carve("sets", 2 * 4 * n, 2, g)
+    A.fill("sets", ar.noise(42))
+    assert A.ptr("sets") % 4 == 2
+    sets = A.view("sets").view(torch.uint16)
+    assert sets.data_ptr() == A.ptr("sets") and sets.numel() == 4 * n
+    out, got_sets = backend.cells(torch.from_numpy(_tile(base, n)).cuda(), P, (4, 4), 2, 4, 64, sets=sets)
+    torch.cuda.synchronize()
+    assert got_sets.data_ptr() == A.ptr("sets") and tuple(got_sets.shape) == (n, 2, 2)
+    A.check()
+    _assert_every_frame(out.cpu().numpy(), refs, f"cells {n} x {h}x{w}")
+    _assert_every_frame(A.get("sets", np.uint16).reshape(n, 2, 2), ref_sets, f"cells, the sets plane {n} x 2x2")
+    del sets, got_sets, A
+
+
+@pytest.mark.parametrize("mode", [MODE_NEAREST, MODE_MATRIX], ids=["nearest", "bayer4"])
+@pytest.mark.parametrize("h,w,residue", [(2, 3, 2), (2, 4, 0)], ids=["bytes", "dwords"])
+def test_oklab_ordered_in_groups_of_65535_frames(orc, h, w, residue, mode):
+    """Frames of 18 bytes take the byte path, frames of 24 bytes the 12-byte dword path of several frames."""
+    import torch
+    from dither_pie_amd import backend
+    n = N_TABLE
+    assert 65535 % PERIOD != 0 and (3 * h * w) % 4 == residue
+    pal, outc, _ = orc.prepare_palette(orc.palr(16, 24), False)
+    P = backend.Palette(pal, outc, metric="oklab")
+    base = _base(orc, h, w, 1200)
+    m = orc.bayer_matrix("4x4")
+    assert m.shape == (4, 4)
+    dev = torch.from_numpy(_tile(base, n)).cuda()
+    assert dev.data_ptr() % 4 == 0
+    if mode == MODE_NEAREST:
+        refs = metric_ref.ordered_u8(base, pal, outc)
+        got = backend.ordered(dev, P, MODE_NEAREST)
+    else:
+        refs = metric_ref.ordered_u8(base, pal, outc, m, 5, 3)
+        got = backend.ordered(dev, P, MODE_MATRIX, thr=backend.Thresholds.from_matrix(m), y0=5, x0=3)
+        assert not np.array_equal(refs, metric_ref.ordered_u8(base, pal, outc))
+    assert got.data_ptr() % 4 == 0
+    _assert_every_frame(got.cpu().numpy(), refs, f"oklab ordered, mode {mode}, {n} x {h}x{w}")
+
+
+def test_integer_diffusion_and_its_workspace_in_groups_of_65535_frames(orc):
+    """dp_idiff_u8 itself, as tests/test_gpu_idiff_memory.py calls it: input, output and workspace are regions of one guarded
+    arena; the workspace has exactly dp_idiff_workspace_bytes(n, 2, 3) = 32 n 3 bytes, 16-byte aligned and no better, and holds
+    noise."""
+    import torch
+    from dither_pie_amd import _lib, backend
+    L = _lib.load()
+    n, h, w = N_TABLE, 2, 3
+    assert 65535 % PERIOD != 0
+    spec, P = _table_palette(orc, 25)
+    taps, divisor = idiff_ref.KERNELS["floyd_steinberg"]
+    dx, dy, wt = (np.array([t[i] for t in taps], np.int32) for i in range(3))
+    base = _base(orc, h, w, 1300)
+    refs = idiff_ref.idiff_frames(orc, base, *spec, taps, divisor, 256)
+    assert len(np.unique(refs.reshape(PERIOD, -1), axis=0)) > PERIOD // 2
+    frames = _tile(base, n)
+    need = L.dp_idiff_workspace_bytes(n, h, w)
+    assert need == 32 * n * 3
+    g = ar.guard_bytes(frames.nbytes)
+    A = ar.Arena(ar.capacity_for([(frames.nbytes, g), (frames.nbytes, g), (need, g)]), "cuda", 51)
+    A.carve("in", frames.nbytes, 1, g)
+    A.put("in", frames)
+    A.carve("out", frames.nbytes, 7, g)
+    A.fill("out", ar.noise(52))
+    A.carve("ws", need, 0, g)
+    A.fill("ws", ar.noise(53))
+    assert A.ptr("in") % 2 == 1 and A.ptr("out") % 2 == 1 and A.ptr("ws") % 32 == 16
+    rc = L.dp_idiff_u8(A.ptr("in"), A.ptr("out"), n, h, w, P._h, dx.ctypes.data, dy.ctypes.data, wt.ctypes.data, len(taps), divisor, 256,
+                       A.ptr("ws"), need, backend._stream())
+    torch.cuda.synchronize()
+    assert rc == 0, (rc, L.dp_last_error())
+    A.check()
+    A.unchanged("in")
+    _assert_every_frame(A.get("out").reshape(n, h, w, 3), refs, f"integer diffusion {n} x {h}x{w}")
+    del A
+
+
+@pytest.mark.parametrize("mode", [MODE_NEAREST, MODE_MATRIX], ids=["nearest", "bayer4"])
+def test_rgb_ordered_more_than_65535_frames(orc, mode):
+    import torch
+    from dither_pie_amd import backend
+    n, h, w = N_TABLE, 2, 3
+    spec, P = _table_palette(orc, 26)
+    base = _base(orc, h, w, 1400)
+    m = orc.bayer_matrix("4x4")
+    dev = torch.from_numpy(_tile(base, n)).cuda()
+    if mode == MODE_NEAREST:
+        refs = np.stack([orc.ordered_u8(f, *spec, "none") for f in base])
+        got = backend.ordered(dev, P, MODE_NEAREST)
+    else:
+        refs = np.stack([orc.ordered_u8(f, *spec, "matrix", thr=m) for f in base])
+        got = backend.ordered(dev, P, MODE_MATRIX, thr=backend.Thresholds.from_matrix(m))
+        assert not np.array_equal(refs, np.stack([orc.ordered_u8(f, *spec, "none") for f in base]))
+    _assert_every_frame(got.cpu().numpy(), refs, f"rgb ordered, mode {mode}, {n} x {h}x{w}")

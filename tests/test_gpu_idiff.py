@@ -2,9 +2,12 @@
 and the instance hook of ImageDitherer) with the push-form statement tests/idiff_ref.py, which scans pixel by pixel and knows
 nothing of bands, skews, rings or periods -- under the RGB metric (the CPU oracle's nearest) and under Oklab
 (metric_ref.NearestAdapter).  The shapes are the smallest at which the schedule can go wrong (SHAPES below says what each is
-for).  A reference is computed once per case and shared (REF).  The references of this file scan about 165 000 pixels in all,
-0.1 to 0.5 s per 5 000 pixels (the file takes about 11 s on an MI355X machine): the shapes, the eight variants on (2, 70, 37), the
-palette sizes and the strengths, each under both metrics; no case takes more than a second."""
+for).  A reference is computed once per case and shared (REF).  The references of this file scan about 480 000 pixels in all
+(the file takes about 12 s on an MI355X machine, 8 s before the last three groups below were added): the shapes, the eight
+variants on (2, 70, 37), the palette sizes and the strengths, each under both metrics, 0.1 to 0.5 s per 5 000 pixels of 16-colour
+content, 165 000 pixels; the tap sets of idiff_ref.tap_cases() on (1, 66, 21), 58 000 pixels, 1.6 s; and grey content on a
+black / white palette, where every query of the statement is a grey and its memo stays small: three frames of 192 rows that put
+two bands on the workspace at once and one of 1030 rows, 256 000 pixels, 1.5 s.  No case takes more than a second."""
 import io
 
 import numpy as np
@@ -76,6 +79,29 @@ def compare(got, want, what):
     assert not len(bad), (what, len(bad), bad[:4].tolist())
 
 
+BLACK_WHITE = [(0, 0, 0), (255, 255, 255)]
+
+
+def grey_frames(n, h, w):
+    """Grey frames (r = g = b): seeded noise plus a horizontal ramp.  With BLACK_WHITE every query of the statement is (v, v, v),
+    so its memo holds at most 256 entries and the serial scan stays cheap at sizes the colour cases cannot afford."""
+    rs = np.random.RandomState(7000 + 10 * h + w)
+    v = rs.randint(0, 128, (n, h, w)) + (np.arange(w) * 127 // max(w - 1, 1))[None, None, :]
+    return np.ascontiguousarray(np.repeat(v.astype(np.uint8)[..., None], 3, axis=-1))
+
+
+def grey_case(orc, dl, taps, divisor, shape):
+    """-> (palette spec, frames, the statement's output) of a grey case at strength 256, computed once."""
+    spec = dl.prepare_palette(BLACK_WHITE, False)
+    key = ("grey", tuple(taps), divisor, shape)
+    if key not in REF:
+        frames = grey_frames(*shape)
+        REF[key] = (frames, ir.idiff_frames(orc, frames, *spec, taps, divisor, 256))
+        REF[key][1].setflags(write=False)
+        assert 0.2 < (REF[key][1] == 255).mean() < 0.8                  # both colours, neither rare
+    return (spec,) + REF[key]
+
+
 def test_the_period_is_the_kernels():
     import os
     import re
@@ -114,6 +140,85 @@ def test_all_eight_variants(gpu, orc, name, metric):
     want = reference(orc, metric, frames, spec, name, 256, ("variants",))
     got = dl.IntegerErrorDiffusionDitherStrategy(name)._run(torch.from_numpy(frames).cuda(), P).cpu().numpy()
     compare(got, want, (name, metric))
+    del P
+
+
+TAP_CASES = ir.tap_cases()
+TAP_RUNS = [(i, "rgb") for i in range(len(TAP_CASES))] + [(i, "oklab") for i in range(0, len(TAP_CASES), 4)]
+
+
+@pytest.mark.parametrize("i,metric", TAP_RUNS, ids=lambda v: str(v))
+def test_tap_sets_beyond_the_variants(gpu, orc, i, metric):
+    """idiff_ref.tap_cases() (tests/test_idiff_cpu.py says what the list covers: skew 1, every tap count 1 .. 12, spare slots in
+    each instance, a two-tap set at the ring depth) at (1, 66, 21): rows 62 .. 65 cross the band edge, and 21 columns are more
+    than the 8-column ring and the 8-step period hold.  Every case under RGB, every fourth under Oklab."""
+    import torch
+    be, dl = gpu
+    taps, divisor, s = TAP_CASES[i]
+    spec = dl.prepare_palette(palette_of(16), False)
+    P = device_palette(be, spec, metric)
+    frames = frames_of(16, 1, 66, 21)
+    want = ir.idiff_frames(adapter(orc, metric), frames, *spec, taps, divisor, s)
+    got = be.idiff(torch.from_numpy(frames).cuda(), P, taps, divisor, s).cpu().numpy()
+    compare(got, want, (i, taps, divisor, s, ir.skew(taps), metric))
+    del P
+
+
+FS4_SKEW_1 = ([(1, 0, 7), (0, 1, 5), (1, 1, 3), (0, 2, 1)], 16)
+TWO_BANDS_ON_THE_WORKSPACE = [(FS4_SKEW_1, 1, (1, 192, 192)), (ir.KERNELS["floyd_steinberg"], 2, (1, 192, 320)), (ir.KERNELS["jjn"], 3, (1, 192, 448))]
+
+
+@pytest.mark.parametrize("kernel,skew,shape", TWO_BANDS_ON_THE_WORKSPACE, ids=["skew1-192x192", "skew2-192x320", "skew3-192x448"])
+def test_two_bands_on_the_workspace_at_once(gpu, orc, kernel, skew, shape):
+    """Band b + 2 stores its boundary rows into the buffer band b wrote while band b + 1 still prefetches from that buffer.
+
+    From idiff.hip as it stands (P = kIdPeriod = 8, s = the skew, steps counted on each wave's own clock t0):
+      * lane 62 of band b + 2 works on column 0 at step 62 s; the errors of that period go to the workspace at the boundary
+        T = P * floor(62 s / P) + P <= 62 s + P.  The store comes before that boundary's own wait, so the wave only had to pass
+        the wait of boundary T - P, which asks band b + 1 for need = T + P + 2 columns of its rows 62 / 63;
+      * band b + 1 publishes t0 - P - 63 s columns at its boundary t0: at the first store of band b + 2 it is at
+        t0 >= T + 2 P + 2 + 63 s, the next boundary being at most 125 s + 4 P + 1 = 125 s + 33 (152, 272 and 400 for s = 1, 2, 3);
+      * band b + 1 issues a prefetch at every boundary with t0 + 2 P + 2 - 32 < w, that is t0 < w + 14;
+      * so both happen in the same stretch of time only for w > 125 s + 20, and only where band b + 2 has rows 62 and 63:
+        h >= 192.  The widths here leave 47, 50 and 53 columns beyond that, five I/O periods and more: the step counts are
+        read from the code, nobody has measured them.
+    The widest multi-band shape of SHAPES, (130, 70), has a two-row third band that stores nothing.
+
+    Grey content and a black / white palette keep the serial statement cheap (grey_frames) -- and are blind to a swapped
+    channel: channel handling at band edges stays with the colour cases (2, 130, 70) and (2, 70, 37).  The overlap depends on
+    the waves running close to their minimum distance, which nothing forces: the test can catch a store of band b + 2 that
+    lands where band b + 1 has yet to read, it cannot prove there is none.
+
+    What it cannot catch, by the same arithmetic: a kernel whose bands all use ONE buffer.  A band fetches column c for the last
+    time at its boundary t0 <= c + 30 - 2 P = c + 14 and stores its own column c after step c + 62 s, and the band below reads
+    that column only once it is published: per column the order is write, read, overwrite, read, whichever bands run together.
+    A library built with bprev and bnext on the same buffer passed this test, every other test of this file and frames up to
+    1024 columns wide on an MI355X: in pixels the second buffer is spare."""
+    import torch
+    be, dl = gpu
+    taps, divisor = kernel
+    n, h, w = shape
+    assert ir.skew(taps) == skew and sum(wt for _, _, wt in taps) == divisor
+    assert w > 125 * ir.skew(taps) + 20 and h >= 192
+    assert w - (125 * ir.skew(taps) + 20) >= 5 * PERIOD
+    spec, frames, want = grey_case(orc, dl, taps, divisor, shape)
+    P = be.Palette(*spec)
+    compare(be.idiff(torch.from_numpy(frames).cuda(), P, taps, divisor, 256).cpu().numpy(), want, (shape, skew))
+    del P
+
+
+SECOND_BAND_WIDE = (1, 1030, 70)
+
+
+def test_a_waves_second_band_with_real_width(gpu, orc):
+    """(1, 1030, 70): 17 bands for 16 waves as in (1, 1030, 3), but wave 0's second band wraps the 64-column ring of the rows
+    above it and runs full I/O periods.  Grey content, black / white palette (grey_frames)."""
+    import torch
+    be, dl = gpu
+    taps, divisor = ir.KERNELS["floyd_steinberg"]
+    spec, frames, want = grey_case(orc, dl, taps, divisor, SECOND_BAND_WIDE)
+    P = be.Palette(*spec)
+    compare(be.idiff(torch.from_numpy(frames).cuda(), P, taps, divisor, 256).cpu().numpy(), want, SECOND_BAND_WIDE)
     del P
 
 
@@ -240,6 +345,18 @@ def test_the_other_period_length(gpu, orc, switches, shape):
     frames = frames_of(16, n, h, w)
     want = reference(orc, "rgb", frames, spec, "floyd_steinberg", 256, ("shape", shape))
     compare(be.idiff(torch.from_numpy(frames).cuda(), P, *ir.KERNELS["floyd_steinberg"], 256).cpu().numpy(), want, shape)
+    del P
+
+
+def test_the_other_period_length_on_a_waves_second_band_with_real_width(gpu, orc, switches):
+    """(1, 1030, 70) of test_a_waves_second_band_with_real_width with 16-step periods: the same bytes."""
+    import torch
+    be, dl = gpu
+    switches.setenv("DP_IDIFF_PERIOD", str(OTHER_PERIOD))
+    taps, divisor = ir.KERNELS["floyd_steinberg"]
+    spec, frames, want = grey_case(orc, dl, taps, divisor, SECOND_BAND_WIDE)
+    P = be.Palette(*spec)
+    compare(be.idiff(torch.from_numpy(frames).cuda(), P, taps, divisor, 256).cpu().numpy(), want, SECOND_BAND_WIDE)
     del P
 
 

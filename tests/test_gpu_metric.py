@@ -17,7 +17,12 @@ pytestmark = pytest.mark.gpu
 
 DP_OK, DP_EINVAL, DP_EUNSUPPORTED = 0, 1, 2
 MODE_NEAREST, MODE_MATRIX = 0, 1
-SHAPES = [(3, 17, 33), (1, 1, 7), (2, 67, 129)]
+SHAPES = [
+    (3, 17, 33), (1, 1, 7), (2, 67, 129),
+    (3, 4, 7),                                                          # several frames of 84 bytes: the 12-byte dword path; a lane's four pixels straddle a row
+    (2, 8, 3),                                                          # w < 4: a lane's four pixels span two rows, 72-byte frames
+    (1, 12, 1),                                                         # a lane spans four rows; every matrix is wider than the image
+]
 ADAPTER = mr.NearestAdapter()
 
 
@@ -111,6 +116,8 @@ def test_ordered_matches_the_statement(gpu, k):
     pal, outc = palette_of(k), np.random.RandomState(k).randint(0, 256, (k, 3)).astype(np.uint8)
     P = be.Palette(pal, outc, metric="oklab")                           # the lazy build: the first call makes the table
     mats = matrices(dl)
+    assert any(n > 1 and 3 * h * w % 4 == 0 for n, h, w in SHAPES) and any(n > 1 and 3 * h * w % 4 for n, h, w in SHAPES)   # dword and byte path
+    assert any(n > 1 and 1 < w < 4 for n, h, w in SHAPES) and any(w == 1 and h > 8 for n, h, w in SHAPES)
     for n, h, w in SHAPES:
         frames = np.random.RandomState(10 * k + h).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
         frames[0].reshape(-1, 3)[:k] = pal.astype(np.uint8)[:h * w]     # colours equal to palette entries: d0 = 0

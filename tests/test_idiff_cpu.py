@@ -126,6 +126,52 @@ def test_plan_equals_the_definition_for_the_eight_tap_sets(harness, tmp_path):
             assert 1 <= int(got[4]) * dy + dx <= 8
 
 
+def test_tap_cases_cover_the_skews_the_counts_and_the_spare_slots():
+    """What tests/test_gpu_idiff.py runs beyond the eight variants: every case obeys the header; skews 1, 2 and 3 occur at
+    least four times each, every tap count 1 .. 12 occurs, and each of the kernel's three instances (4, 7 and 12 tap slots)
+    occurs with at least one spare slot."""
+    cases = ir.tap_cases()
+    assert cases == ir.tap_cases() and len(cases) >= 16 + ir.N_RANDOM_CASES          # a fixed list
+    named = [sorted(taps) for taps, _ in ir.KERNELS.values()]
+    for taps, divisor, s in cases:
+        assert ir.check_taps(taps, divisor, s) == taps
+        assert all(isinstance(v, int) for t in taps for v in t) and isinstance(divisor, int)
+        assert sorted(taps) not in named or s != 256                  # none repeats a variant
+    skews = [ir.skew(taps) for taps, _, _ in cases]
+    counts = [len(taps) for taps, _, _ in cases]
+    print("skews", [skews.count(v) for v in (1, 2, 3)], "tap counts", sorted(counts))
+    assert set(skews) == {1, 2, 3} and min(skews.count(v) for v in (1, 2, 3)) >= 4
+    assert set(counts) == set(range(1, ir.MAX_TAPS + 1))
+    assert any(n < 4 for n in counts) and any(5 <= n < 7 for n in counts) and any(8 <= n < 12 for n in counts)
+    for must in ([(1, 0, 1)], [(2, 0, 1)], [(0, 1, 1)], [(0, 2, 1)], [(-1, 2, 1)], [(-2, 2, 1)], [(-2, 1, 1)]):
+        assert (must, 1, 256) in cases
+    assert ([(-2, 1, 1), (2, 2, 1)], 2, 256) in cases and ([(2, 1, 1), (2, 2, 1)], 2, 256) in cases
+    assert ([(1, 0, 7), (0, 1, 5), (1, 1, 3), (0, 2, 1)], 16, 256) in cases
+    assert any(len(taps) == 2 and max(ir.skew(taps) * dy + dx for dx, dy, _ in taps) == 8 for taps, _, _ in cases)   # the ring depth
+    assert any((-2, 1, 0) in taps for taps, _, _ in cases)
+    assert any(sum(t[2] for t in taps) == 3 and divisor == 1000 for taps, divisor, _ in cases)
+    assert any(s == 255 for _, _, s in cases)
+    assert any(all(dy != 1 for _, dy, _ in taps) for taps, _, _ in cases) and any((1, 0) not in [t[:2] for t in taps] for taps, _, _ in cases)
+
+
+def test_plan_equals_the_definition_for_the_tap_cases(harness, tmp_path):
+    cases = ir.tap_cases()
+    with open(tmp_path / "cases.bin", "wb") as f:
+        for taps, divisor, s in cases:
+            f.write(_record(taps, divisor, s))
+    lines = harness("idiffplan", tmp_path / "cases.bin", len(cases))
+    assert len(lines) == len(cases)
+    for i, ((taps, divisor, s), line) in enumerate(zip(cases, lines)):
+        got = line.split()
+        assert got[:3] == ["idiff", str(i), "0"], (line, taps)
+        q = [int(v) for v in got[5:]]
+        assert int(got[3]) == len(taps) == len(q), (line, taps)
+        assert q == ir.shares(taps, divisor, s) and sum(q) <= 65536, (taps, divisor, s)
+        assert int(got[4]) == ir.skew(taps), (line, taps)
+        for dx, dy, _ in taps:
+            assert dy == 0 or 1 <= int(got[4]) * dy + dx <= 8, (line, taps)
+
+
 def test_plan_refuses_what_the_header_refuses(harness, tmp_path):
     fs, d = ir.KERNELS["floyd_steinberg"]
     jjn = ir.KERNELS["jjn"][0]

@@ -123,8 +123,9 @@ def test_c_abi_argument_errors_without_gpu(lib):
     from dither_pie_amd._lib import DP_EINVAL, DP_OK
     assert "dp_riemersma_u8" in _lib.EXPORTS and hasattr(lib, "dp_riemersma_u8")
     assert lib.dp_version() == _lib.ABI_VERSION == 103
-    # a stand-in palette handle: the checks below return before anything reads it
-    fake = C.create_string_buffer(64)
+    # a stand-in palette handle of zeros, as long as tests/test_idiff_cpu.py makes its own: the entry point reads the palette's
+    # metric field (0: RGB) before it looks at the sizes, and 64 bytes ended in front of that field
+    fake = C.create_string_buffer(8192)
     pal = C.cast(fake, C.c_void_p)
     buf = C.cast(C.create_string_buffer(16), C.c_void_p)
     assert lib.dp_riemersma_u8(buf, buf, 1, 2, 2, None, None) == DP_EINVAL
