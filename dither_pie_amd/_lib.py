@@ -217,6 +217,19 @@ _SIGS_IDIFF = {
     "dp_idiff_u8": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
 }
 EXPORTS_IDIFF = tuple(_SIGS_IDIFF)
+# include/ditherpie_hip_okfit.h: palettes fitted in the integer Oklab (point records of a colour histogram, the weighted k-means
+# over them and its host statement); a table of its own for the same reason.
+OKFIT_MAX_COLORS, OKFIT_MAX_ITER, OKFIT_MAX_POINTS, OKFIT_POINT_BYTES = 256, 10000, 1 << 24, 16
+_SIGS_OKFIT = {
+    "dp_okfit_hist_workspace_bytes": (_sz, []),
+    "dp_okfit_hist_count": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "dp_okfit_hist_points": (_i, [_vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dp_okfit_points_u32": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "dp_okfit_workspace_bytes": (_sz, [_i64, _i]),
+    "dp_okfit_fit": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, C.POINTER(_i), _vp, _sz, _vp]),
+    "dp_okfit_host": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(C.c_uint64)]),
+}
+EXPORTS_OKFIT = tuple(_SIGS_OKFIT)
 
 
 def build(force=False):
@@ -262,7 +275,8 @@ def load():
                                           + list(_SIGS_PNG_DYN.items()) + list(_SIGS_PATTERN.items())
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
                                           + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
-                                          + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())):
+                                          + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())
+                                          + list(_SIGS_OKFIT.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

@@ -1202,6 +1202,129 @@ class ColourHistogram:
         self.step_into(centers, totals, True, mean)
         return totals[:3 * K].view(K, 3), totals[3 * K:4 * K], totals[4 * K:]
 
+    def _okfit_scan(self, points, capacity):
+        dev = self.buf.device
+        n = torch.zeros(1, dtype=torch.int64, device=dev)
+        L = _lib.load()
+        with torch.cuda.device(dev), _Launch(dev, L.dp_okfit_hist_workspace_bytes()) as ws:
+            if points is None:
+                check(L.dp_okfit_hist_count(self.buf.data_ptr(), n.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+            else:
+                check(L.dp_okfit_hist_points(self.buf.data_ptr(), points.data_ptr() if capacity else None, capacity, n.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), _stream()))
+            return int(n.item())
+
+    def n_occupied(self) -> int:
+        """The number of colours with a count above zero (dp_okfit_hist_count; one host synchronisation)."""
+        if self.n == 0:
+            return 0
+        return self._okfit_scan(None, 0)
+
+    def points(self, capacity=None):
+        """The occupied colours as the point records of the Oklab fit, in ascending order of r << 16 | g << 8 | b
+        (dp_okfit_hist_points) -> uint8 tensor [n, OKFIT_POINT_BYTES] on the device; okfit_points_numpy() reads one.  With a
+        `capacity` only that many records are made room for: -> (tensor [min(n, capacity), 16], n), n the true number."""
+        dev = self.buf.device
+        if capacity is None:
+            n = self.n_occupied()
+            out = torch.empty((n, OKFIT_POINT_BYTES), dtype=torch.uint8, device=dev)
+            if n:
+                assert self._okfit_scan(out, n) == n
+            return out
+        capacity = int(capacity)
+        if not 0 <= capacity <= OKFIT_MAX_POINTS:
+            raise ValueError(f"capacity must be in [0, {OKFIT_MAX_POINTS}]")
+        out = torch.empty((capacity, OKFIT_POINT_BYTES), dtype=torch.uint8, device=dev)
+        n = self._okfit_scan(out, capacity) if self.n else 0
+        return out[:min(n, capacity)], n
+
+
+OKFIT_MAX_COLORS = _lib.OKFIT_MAX_COLORS     # DP_OKFIT_MAX_COLORS (include/ditherpie_hip_okfit.h)
+OKFIT_MAX_ITER = _lib.OKFIT_MAX_ITER
+OKFIT_MAX_POINTS = _lib.OKFIT_MAX_POINTS
+OKFIT_POINT_BYTES = _lib.OKFIT_POINT_BYTES
+OKFIT_POINT_DTYPE = np.dtype([("code", "<u4"), ("count", "<u4"), ("lab", "<i2", (3,)), ("zero", "<i2")])
+
+
+def _okfit_args(K, max_iter):
+    K, max_iter = int(K), int(max_iter)
+    if K < 1:
+        raise ValueError("num_colors must be >= 1")
+    if K > OKFIT_MAX_COLORS:
+        raise ValueError(f"an Oklab palette fit has at most {OKFIT_MAX_COLORS} colours, not {K}")
+    if not 1 <= max_iter <= OKFIT_MAX_ITER:
+        raise ValueError(f"max_iter must be in [1, {OKFIT_MAX_ITER}], not {max_iter}")
+    return K, max_iter
+
+
+def _okfit_arrays(codes, counts):
+    codes = np.ascontiguousarray(np.asarray(codes).reshape(-1))
+    counts = np.ascontiguousarray(np.asarray(counts).reshape(-1))
+    if codes.size != counts.size or codes.size < 1:
+        raise ValueError("codes and counts must have the same length, at least 1")
+    if codes.size > OKFIT_MAX_POINTS:
+        raise ValueError(f"at most {OKFIT_MAX_POINTS} points")
+    c64, n64 = codes.astype(np.int64), counts.astype(np.int64)
+    if c64.min() < 0 or c64.max() >= 1 << 24 or np.any(np.diff(c64) <= 0):
+        raise ValueError("codes must be strictly ascending and below 2^24")
+    if n64.min() < 1 or int(n64.sum()) >= 1 << 32:
+        raise ValueError("counts must be >= 1 and their sum below 2^32")
+    return c64.astype(np.uint32), n64.astype(np.uint32)
+
+
+def okfit_points(codes, counts, device=None):
+    """Point records from arrays (dp_okfit_points_u32): codes = r << 16 | g << 8 | b strictly ascending, counts >= 1 with a sum
+    below 2^32 -> uint8 tensor [n, OKFIT_POINT_BYTES] on the device."""
+    codes, counts = _okfit_arrays(codes, counts)
+    require_gpu()
+    dev = torch.device(device or "cuda")
+    c, k = torch.from_numpy(codes.view(np.int32)).to(dev), torch.from_numpy(counts.view(np.int32)).to(dev)
+    out = torch.empty((codes.size, OKFIT_POINT_BYTES), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _Launch(dev, None):
+        check(_lib.load().dp_okfit_points_u32(c.data_ptr(), k.data_ptr(), codes.size, out.data_ptr(), _stream()))
+    return out
+
+
+def okfit_points_numpy(points):
+    """A tensor of point records -> (codes uint32 [n], counts uint32 [n], lab int16 [n, 3])."""
+    rec = points.cpu().numpy().reshape(-1).view(OKFIT_POINT_DTYPE)
+    return rec["code"].copy(), rec["count"].copy(), rec["lab"].copy()
+
+
+def okfit(points_or_hist, K, max_iter=100):
+    """The Oklab palette fit (dp_okfit_fit) of a ColourHistogram or of a tensor of point records -> (palette uint8 [K, 3],
+    centres int32 [K, 3], n_iter, distortion): a weighted k-means in the integer Oklab, all integer, a pure function of the
+    colour multiset; every palette entry is a colour of the input.  Synchronises the current stream once per pass."""
+    K, max_iter = _okfit_args(K, max_iter)
+    pts = points_or_hist.points() if isinstance(points_or_hist, ColourHistogram) else points_or_hist
+    if not (isinstance(pts, torch.Tensor) and pts.is_cuda and pts.dtype == torch.uint8 and pts.dim() == 2 and pts.shape[1] == OKFIT_POINT_BYTES):
+        raise TypeError(f"points must be a ColourHistogram or a CUDA uint8 tensor [n, {OKFIT_POINT_BYTES}]")
+    pts = pts.contiguous()
+    n = pts.shape[0]
+    if n < 1:
+        raise ValueError("the fit needs at least one point")
+    dev = pts.device
+    pal = torch.empty((K, 3), dtype=torch.uint8, device=dev)
+    centres = torch.empty((K, 3), dtype=torch.int32, device=dev)
+    dist = torch.empty(1, dtype=torch.int64, device=dev)
+    n_iter = C.c_int(0)
+    L = _lib.load()
+    with torch.cuda.device(dev), _Launch(dev, L.dp_okfit_workspace_bytes(n, K)) as ws:
+        check(L.dp_okfit_fit(pts.data_ptr(), n, K, max_iter, pal.data_ptr(), centres.data_ptr(), dist.data_ptr(), C.byref(n_iter),
+                             ws.data_ptr(), ws.numel(), _stream()))
+    return pal.cpu().numpy(), centres.cpu().numpy(), int(n_iter.value), int(dist.cpu().numpy().view(np.uint64)[0])
+
+
+def okfit_host(codes, counts, K, max_iter=100):
+    """The host statement of the fit (dp_okfit_host; no device) -> (palette, centres, n_iter, distortion) as okfit()."""
+    K, max_iter = _okfit_args(K, max_iter)
+    codes, counts = _okfit_arrays(codes, counts)
+    pal, centres = np.empty((K, 3), np.uint8), np.empty((K, 3), np.int32)
+    n_iter, dist = C.c_int(0), C.c_uint64(0)
+    check(_lib.load().dp_okfit_host(_np_ptr(codes), _np_ptr(counts), codes.size, K, max_iter, _np_ptr(pal), _np_ptr(centres), C.byref(n_iter),
+                                    C.byref(dist)))
+    return pal, centres, int(n_iter.value), int(dist.value)
+
 
 def kmeans_update(totals, centers, prev, status, tol, max_iter):
     """The centre update of one Lloyd iteration on the device (dp_kmeans_update); everything stays in HBM."""

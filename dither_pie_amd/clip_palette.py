@@ -19,6 +19,9 @@ Parity definitions.
               as kmeans.fit_palette runs it.  This is deliberately not fit_palette's raster-index sample (the image path is
               untouched): above 10 000 pixels the reference samples unseeded and has no single answer, so there is nothing
               tighter to match.
+  oklab       the integer Oklab fit of include/ditherpie_hip_okfit.h over the histogram's occupied colours: all integer, no
+              random numbers, a pure function of the clip's colour multiset by construction (the points are the distinct
+              colours in code order, every sum is an integer sum); its entries are colours of the clip.  Not with use_gamma.
 """
 from __future__ import annotations
 
@@ -30,7 +33,7 @@ _LUT_CHUNK = 1 << 22   # bytes linearised per indexing step under use_gamma (the
 
 
 class ClipPalette:
-    """ClipPalette(use_gamma=False, device=None).add(frames).add(more)...  then .median_cut(n) and / or .kmeans(n)."""
+    """ClipPalette(use_gamma=False, device=None).add(frames).add(more)...  then .median_cut(n), .kmeans(n) and / or .oklab(n)."""
 
     def __init__(self, use_gamma=False, device=None):
         import torch
@@ -159,3 +162,22 @@ class ClipPalette:
         """A k-means palette of the clip -> list of num_colors (r, g, b) tuples; a pure function of the clip's colour
         multiset (module docstring).  ValueError above backend.KMEANS_HIST_MAX_K colours and for an empty clip."""
         return self.kmeans_fit(num_colors, random_state, max_iter, tol)[0]
+
+    def oklab_fit(self, num_colors, max_iter=100):
+        """-> (palette list, centres int32 [K,3] in the integer Oklab, n_iter, distortion) of backend.okfit over the clip's
+        histogram.  ValueError above backend.OKFIT_MAX_COLORS colours, for an empty clip and with use_gamma=True."""
+        import torch
+        from . import backend
+        K, max_iter = backend._okfit_args(num_colors, max_iter)
+        if self.use_gamma:
+            raise ValueError("use_gamma=True cannot be combined with the 'oklab' palette fit: Oklab linearises by itself")
+        if self.n_pixels == 0:
+            raise ValueError("the clip palette holds no pixels yet")
+        with torch.cuda.device(self.device):
+            pal, centres, n_iter, distortion = backend.okfit(self._hist, K, max_iter)
+        return [tuple(int(v) for v in c) for c in pal], centres, n_iter, distortion
+
+    def oklab(self, num_colors, max_iter=100):
+        """An Oklab-fitted palette of the clip -> list of num_colors (r, g, b) tuples, each a colour of the clip; a pure
+        function of the clip's colour multiset (module docstring)."""
+        return self.oklab_fit(num_colors, max_iter)[0]

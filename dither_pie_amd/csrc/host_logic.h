@@ -2929,4 +2929,128 @@ inline bool metric_takes_nearest(const int32_t d0, const int32_t d1, const float
     return f <= (double)t;
 }
 
+// ---- Oklab palette fitting (include/ditherpie_hip_okfit.h; tests/okfit_ref.py states it in numpy) ----------------------------------
+// The host statement of the fit: greedy k-means++ seeding, Lloyd passes with rounded integer means, the medoid of every centre.
+// Integers throughout; ascending loops with strict comparisons give the tie rules (the lowest code, the lowest centre index).
+constexpr int kOkfitMaxK = 256;
+constexpr int kOkfitMaxIter = 10000;
+constexpr int64_t kOkfitMaxPoints = (int64_t)1 << 24;
+
+// 0, or which rule the arguments break: 1 a size (n, K < 1, max_iter), 2 K above 256, 3 the codes, 4 the counts
+inline int okfit_check(const uint32_t *codes, const uint32_t *counts, const int64_t n, const int K, const int max_iter)
+{
+    if (n < 1 || n > kOkfitMaxPoints || K < 1 || max_iter < 1 || max_iter > kOkfitMaxIter) return 1;
+    if (K > kOkfitMaxK) return 2;
+    uint64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (codes[i] >= (1u << 24) || (i > 0 && codes[i] <= codes[i - 1])) return 3;
+        if (counts[i] == 0) return 4;
+        total += counts[i];
+    }
+    return total >= ((uint64_t)1 << 32) ? 4 : 0;
+}
+
+inline int64_t okfit_dist(const int32_t *p, const int32_t *c)
+{
+    const int64_t x = p[0] - c[0], y = p[1] - c[1], z = p[2] - c[2];
+    return x * x + y * y + z * z;
+}
+
+// floor(a / b), b > 0
+inline int64_t okfit_floordiv(const int64_t a, const int64_t b)
+{
+    const int64_t q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// labels[i] = the centre of least distance (the lowest index on ties), dist[i] that distance
+inline void okfit_assign(const int32_t *P, const int64_t n, const int32_t *C, const int K, int32_t *labels, int64_t *dist)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        int64_t best = okfit_dist(P + 3 * i, C);
+        int32_t at = 0;
+        for (int k = 1; k < K; ++k) {
+            const int64_t d = okfit_dist(P + 3 * i, C + 3 * k);
+            if (d < best) best = d, at = k;
+        }
+        labels[i] = at;
+        dist[i] = best;
+    }
+}
+
+// palette K x 3 bytes, centres K x 3; the arguments have passed okfit_check
+inline void okfit_host(const uint32_t *codes, const uint32_t *counts, const int64_t n, const int K, const int max_iter, uint8_t *palette,
+                       int32_t *centres, int *n_iter_out, uint64_t *distortion_out)
+{
+    const uint16_t *ct = metric_cbrt_table();
+    std::vector<int32_t> P((size_t)3 * n), C((size_t)3 * K), labels((size_t)n);
+    std::vector<int64_t> dist((size_t)n), S((size_t)3 * K);
+    std::vector<uint64_t> cnt((size_t)K);
+    for (int64_t i = 0; i < n; ++i) metric_lab(codes[i] >> 16, (codes[i] >> 8) & 255u, codes[i] & 255u, ct, &P[3 * (size_t)i]);
+    // seeding
+    int64_t first = 0;
+    for (int64_t i = 1; i < n; ++i)
+        if (counts[i] > counts[first]) first = i;
+    for (int c = 0; c < 3; ++c) C[c] = P[3 * (size_t)first + c];
+    for (int j = 1; j < K; ++j) {
+        uint64_t best = 0;
+        int64_t at = -1;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t d = okfit_dist(&P[3 * (size_t)i], &C[3 * (size_t)(j - 1)]);
+            if (j == 1 || d < dist[i]) dist[i] = d;
+            const uint64_t prod = (uint64_t)counts[i] * (uint64_t)dist[i];
+            if (at < 0 || prod > best) best = prod, at = i;
+        }
+        for (int c = 0; c < 3; ++c) C[3 * (size_t)j + c] = best > 0 ? P[3 * (size_t)at + c] : C[c];
+    }
+    // Lloyd
+    int n_iter = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        ++n_iter;
+        okfit_assign(P.data(), n, C.data(), K, labels.data(), dist.data());
+        std::fill(S.begin(), S.end(), 0);
+        std::fill(cnt.begin(), cnt.end(), 0);
+        for (int64_t i = 0; i < n; ++i) {
+            const size_t k = (size_t)labels[i];
+            cnt[k] += counts[i];
+            for (int c = 0; c < 3; ++c) S[3 * k + c] += (int64_t)counts[i] * P[3 * (size_t)i + c];
+        }
+        bool changed = false;
+        for (int k = 0; k < K; ++k) {
+            if (!cnt[k]) continue;
+            for (int c = 0; c < 3; ++c) {
+                const int32_t v = (int32_t)okfit_floordiv(2 * S[3 * (size_t)k + c] + (int64_t)cnt[k], 2 * (int64_t)cnt[k]);
+                changed |= v != C[3 * (size_t)k + c];
+                C[3 * (size_t)k + c] = v;
+            }
+        }
+        if (!changed) break;
+    }
+    // back to bytes
+    okfit_assign(P.data(), n, C.data(), K, labels.data(), dist.data());
+    std::vector<int64_t> near((size_t)K, -1);
+    uint64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t k = (size_t)labels[i];
+        total += (uint64_t)counts[i] * (uint64_t)dist[i];
+        if (near[k] < 0 || dist[i] < dist[(size_t)near[k]]) near[k] = i;
+    }
+    for (int k = 0; k < K; ++k) {
+        int64_t at = near[(size_t)k];
+        if (at < 0) {
+            int64_t best = 0;
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t d = okfit_dist(&P[3 * (size_t)i], &C[3 * (size_t)k]);
+                if (at < 0 || d < best) best = d, at = i;
+            }
+        }
+        palette[3 * k] = (uint8_t)(codes[at] >> 16);
+        palette[3 * k + 1] = (uint8_t)(codes[at] >> 8);
+        palette[3 * k + 2] = (uint8_t)codes[at];
+        for (int c = 0; c < 3; ++c) centres[3 * k + c] = C[3 * (size_t)k + c];
+    }
+    *n_iter_out = n_iter;
+    *distortion_out = total;
+}
+
 }  // namespace dp

@@ -864,10 +864,49 @@ static int run_idiffplan(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- Oklab palette fitting: the host statement -------------------------------------------------------------------------
+// record: n, K, max_iter (int32), then n codes, n counts (uint32)
+static int run_okfit(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[3];
+        if (fread(head, sizeof(int32_t), 3, f) != 3 || head[0] < 0 || head[0] > (1 << 24)) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const size_t n = (size_t)head[0];
+        std::vector<uint32_t> codes(n), counts(n);   // exactly as many as the statement may read
+        if (fread(codes.data(), sizeof(uint32_t), n, f) != n || fread(counts.data(), sizeof(uint32_t), n, f) != n) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const int K = head[1], rule = okfit_check(codes.data(), counts.data(), (int64_t)n, K, head[2]);
+        printf("okfit %d %d", c, rule);
+        if (!rule) {
+            std::vector<uint8_t> pal((size_t)3 * K);   // exactly what the statement writes
+            std::vector<int32_t> centres((size_t)3 * K);
+            int n_iter = 0;
+            uint64_t distortion = 0;
+            okfit_host(codes.data(), counts.data(), (int64_t)n, K, head[2], pal.data(), centres.data(), &n_iter, &distortion);
+            printf(" %d %llu", n_iter, (unsigned long long)distortion);
+            for (int i = 0; i < 3 * K; ++i) printf(" %u", (unsigned)pal[(size_t)i]);
+            for (int i = 0; i < 3 * K; ++i) printf(" %d", centres[(size_t)i]);
+        }
+        printf("\n");
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  idiffplan <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -882,6 +921,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

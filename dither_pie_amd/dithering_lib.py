@@ -289,6 +289,7 @@ def _device_index():
 
 
 METRICS = ("rgb", "oklab")   # ImageDitherer(metric=...): how "nearest" is measured (include/ditherpie_hip_metric.h)
+PALETTE_FITS = ("median_cut", "oklab")   # ImageDitherer(palette_fit=...): how palette=None is fitted (include/ditherpie_hip_okfit.h)
 
 
 def _device_palette(pal_f32, out_colors, lut_in, metric="rgb"):
@@ -802,8 +803,9 @@ class OstromoukhovDitherStrategy(_VariableDiffuser):
 
 # ------------------------------------------------------------------------------------- palettes
 class ColorReducer:
-    """Palette producers (dithering_lib.py:1807-1872).  They cut and cluster in RGB whatever metric the ditherer that uses the
-    palette has (ImageDitherer(metric="oklab") changes the search, not the palette)."""
+    """Palette producers (dithering_lib.py:1807-1872).  Median cut and k-means cut and cluster in RGB whatever metric the ditherer
+    that uses the palette has (ImageDitherer(metric="oklab") changes the search, not the palette); generate_oklab_palette (an
+    addition to the reference's interface) clusters in the integer Oklab of that metric."""
 
     @staticmethod
     def find_dominant_channel(colors: List[Tuple[int, int, int]]) -> int:
@@ -974,6 +976,28 @@ class ColorReducer:
         histogram)."""
         from .clip_palette import ClipPalette
         return ClipPalette(use_gamma=use_gamma, device=frames.device).add(frames, every=every).kmeans(num_colors, random_state)
+
+    @staticmethod
+    def generate_oklab_palette(img, num_colors: int, max_iter: int = 100) -> List[Tuple[int, int, int]]:
+        """A palette fitted in the integer Oklab (include/ditherpie_hip_okfit.h): a weighted k-means over the image's colour
+        histogram on the GPU, all integer and exact -- a pure function of the image's colour multiset, no random numbers; every
+        entry is a colour of the image (the member of its cluster nearest to the cluster's mean), so duplicates appear when the
+        image has fewer distinct colours than num_colors.  At most 256 colours."""
+        import torch
+        from . import backend
+        backend._okfit_args(num_colors, max_iter)
+        rgb = img if img.mode == "RGB" else img.convert("RGB")
+        frame = torch.from_numpy(np.asarray(rgb, dtype=np.uint8).copy()).cuda()
+        return ColorReducer.generate_oklab_palette_frames(frame, num_colors, 1, max_iter)
+
+    @staticmethod
+    def generate_oklab_palette_frames(frames, num_colors: int, every: int = 1, max_iter: int = 100) -> List[Tuple[int, int, int]]:
+        """generate_oklab_palette of a CLIP that is resident on the GPU (uint8 CUDA tensor [N,H,W,3] or [H,W,3]): one palette
+        fitted to the colour multiset of every `every`-th frame (clip_palette.ClipPalette.oklab is the streaming form)."""
+        from .clip_palette import ClipPalette
+        from . import backend
+        backend._okfit_args(num_colors, max_iter)
+        return ClipPalette(device=frames.device).add(frames, every=every).oklab(num_colors, max_iter)
 
     @staticmethod
     def generate_uniform_palette(num_colors: int) -> List[Tuple[int, int, int]]:
@@ -1578,22 +1602,27 @@ class ImageDitherer:
     }
 
     metric = "rgb"   # (the class default: an object pickled before the attribute existed reads as "rgb")
+    palette_fit = "median_cut"   # (likewise: what palette=None meant before the attribute existed)
 
     def __init__(self, num_colors: int = 16, dither_mode: Optional[DitherMode] = DitherMode.BAYER,
                  palette: Optional[List[Tuple[int, int, int]]] = None, use_gamma: bool = False,
-                 dither_params: Optional[Dict[str, Any]] = None, metric: str = "rgb"):
+                 dither_params: Optional[Dict[str, Any]] = None, palette_fit: str = "median_cut", metric: str = "rgb"):
         """metric (an addition to the reference's interface): "rgb", the reference's squared Euclidean RGB distance, or "oklab",
         the integer Oklab of include/ditherpie_hip_metric.h -- for NONE, BAYER, BLUE_NOISE, POLKA_DOT, any MatrixDitherStrategy
         instance, PatternDitherStrategy, DotDiffusionDitherStrategy and IntegerErrorDiffusionDitherStrategy; every other mode, and use_gamma=True (Oklab linearises
-        by itself), raise ValueError with it.  The palette producers (median cut, k-means) and the strategy-level
-        dither(pixels, palette_arr, size) stay RGB."""
+        by itself), raise ValueError with it.  The strategy-level dither(pixels, palette_arr, size) stays RGB.
+        palette_fit (another addition, independent of metric; pass both by keyword): what palette=None means -- "median_cut", the
+        reference's RGB median cut of the first frame, or "oklab", ColorReducer.generate_oklab_palette of it (at most 256
+        colours; ValueError together with use_gamma=True)."""
         self.num_colors = num_colors
         self.dither_mode = dither_mode
         self.palette = palette
         self.use_gamma = use_gamma
         self.dither_params = dither_params or {}
+        self.palette_fit = palette_fit
         self.metric = metric
         self._check_metric(None)
+        self._check_palette_fit()
 
     @staticmethod
     def get_mode_parameters(mode: DitherMode) -> Optional[Dict[str, Any]]:
@@ -1647,6 +1676,15 @@ class ImageDitherer:
                              "IntegerErrorDiffusionDitherStrategy)")
         return metric
 
+    def _check_palette_fit(self):
+        """How palette=None is fitted, checked against use_gamma: before any launch."""
+        fit = self.palette_fit
+        if fit not in PALETTE_FITS:
+            raise ValueError(f"palette_fit must be one of {PALETTE_FITS}, not {fit!r}")
+        if fit == "oklab" and self.use_gamma:
+            raise ValueError("use_gamma=True cannot be combined with the 'oklab' palette fit: Oklab linearises by itself")
+        return fit
+
     def _palette_on_device(self, strategy=None):
         metric = self._check_metric(strategy)
         return _device_palette(*prepare_palette(self.palette, self.use_gamma), metric)
@@ -1654,7 +1692,10 @@ class ImageDitherer:
     # -- host plumbing ------------------------------------------------------------------------
     def _ensure_palette(self, first_frame_u8: np.ndarray):
         """palette=None: median cut of the (linearised, when gamma is on) image, kept on the object
-        (dithering_lib.py:1960-1966)."""
+        (dithering_lib.py:1960-1966); with palette_fit="oklab" the Oklab fit of the image instead."""
+        if self.palette is None and self._check_palette_fit() == "oklab":
+            from PIL import Image
+            self.palette = ColorReducer.generate_oklab_palette(Image.fromarray(first_frame_u8, "RGB"), self.num_colors)
         if self.palette is None:
             from PIL import Image
             src = _tables.LUT_IN[first_frame_u8] if self.use_gamma else first_frame_u8

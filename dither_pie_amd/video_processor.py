@@ -159,6 +159,23 @@ def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_me
         return False
 
 
+def _check_oklab_source(num_colors, use_gamma):
+    """What ClipPalette.oklab would refuse, before a frame is decoded."""
+    from . import backend
+    backend._okfit_args(num_colors, 100)
+    if use_gamma:
+        raise ValueError("use_gamma=True cannot be combined with the 'oklab' palette fit: Oklab linearises by itself")
+
+
+def _fit_clip(clip, source, num_colors, random_state):
+    """The palette of a clip_palette.ClipPalette for a scan's `source`."""
+    if source == "median_cut":
+        return clip.median_cut(num_colors)
+    if source == "oklab":
+        return clip.oklab(num_colors)
+    return clip.kmeans(num_colors, random_state)
+
+
 class _PipeSplicer:
     """vmsplice(2) of a buffer's pages into a pipe: the kernel takes references to the pages instead of copying them into pipe
     buffers of its own -- no copy and no page allocation on the writing side, which on the bench box also speeds the READER of
@@ -547,16 +564,19 @@ class VideoProcessor:
         path (the same decoder command line, reader thread, rotating pinned slots and failure policy as
         _stream_through_pipes; no encoder) feeding every `every`-th frame into a clip_palette.ClipPalette.
         source: "median_cut" (the reference's reduce_colors on the taken frames stacked top to bottom) or "kmeans" (a pure
-        function of the clip's colour multiset; clip_palette's parity definitions).  max_frames: look at the first that
+        function of the clip's colour multiset; clip_palette's parity definitions) or "oklab" (ClipPalette.oklab: the integer
+        Oklab fit, at most 256 colours, not with use_gamma).  max_frames: look at the first that
         many frames of the stream only.  Failure policy: a batch that fails is retried frame by frame and a frame that
         keeps failing is left out of the palette; a device failure, a malformed stream or a decoder that exits with an
         error raises, as in the pipes path.  Progress goes through progress_callback."""
         import torch
         from .clip_palette import ClipPalette
-        if source not in ("median_cut", "kmeans"):
-            raise ValueError(f"source must be 'median_cut' or 'kmeans', not {source!r}")
+        if source not in ("median_cut", "kmeans", "oklab"):
+            raise ValueError(f"source must be 'median_cut', 'kmeans' or 'oklab', not {source!r}")
         if max_frames is not None and int(max_frames) < 1:
             raise ValueError("max_frames must be >= 1")
+        if source == "oklab":
+            _check_oklab_source(num_colors, use_gamma)
         made = {}
 
         def setup(dev, gpu_stream, h, w, stats):
@@ -570,7 +590,7 @@ class VideoProcessor:
         self._report_progress(0.9, "Fitting the palette...")
         self.last_clip_palette = clip
         with torch.cuda.device(dev):
-            palette = clip.median_cut(num_colors) if source == "median_cut" else clip.kmeans(num_colors, random_state)
+            palette = _fit_clip(clip, source, num_colors, random_state)
         self._report_progress(1.0, "Palette scan complete!")
         return palette
 
@@ -583,7 +603,7 @@ class VideoProcessor:
         the device (backend.SceneStream), the N distances read back -- one small synchronising copy per batch --,
         scenes.scene_cuts, the batch split at the cuts (scenes.split_at), every piece into ONE clip_palette.ClipPalette; at
         each cut the finished scene's palette is fitted and the accumulator reset.
-        source: "median_cut" / "kmeans" as in scan_palette -- a scene's palette is what a fresh
+        source: "median_cut" / "kmeans" / "oklab" as in scan_palette -- a scene's palette is what a fresh
         ClipPalette(use_gamma).add(frames[start:end], every) gives for that source; None: boundaries only, every palette is
         None and no accumulator is made.  every: every that-many-th frame of each scene, counted from the scene's first
         frame.  Frame i starts a scene when its distance exceeds threshold * 2 * H * W and the open scene holds at least
@@ -599,8 +619,8 @@ class VideoProcessor:
         from . import backend
         from .clip_palette import ClipPalette
         from .scenes import Scene, _check_cut_parameters, scene_cuts, split_at
-        if source not in (None, "median_cut", "kmeans"):
-            raise ValueError(f"source must be None, 'median_cut' or 'kmeans', not {source!r}")
+        if source not in (None, "median_cut", "kmeans", "oklab"):
+            raise ValueError(f"source must be None, 'median_cut', 'kmeans' or 'oklab', not {source!r}")
         if max_frames is not None and int(max_frames) < 1:
             raise ValueError("max_frames must be >= 1")
         _check_cut_parameters(threshold, min_scene_frames)
@@ -610,12 +630,14 @@ class VideoProcessor:
             raise ValueError("num_colors must be >= 1")
         if source == "kmeans" and int(num_colors) > backend.KMEANS_HIST_MAX_K:
             raise ValueError(f"a clip k-means palette has at most {backend.KMEANS_HIST_MAX_K} colours, not {num_colors}")
+        if source == "oklab":
+            _check_oklab_source(num_colors, use_gamma)
         scenes = []
         made = {"clip": None}
         cur = {"open": 0, "carry": 0, "starts": set()}
 
         def fit(clip):
-            return clip.median_cut(num_colors) if source == "median_cut" else clip.kmeans(num_colors, random_state)
+            return _fit_clip(clip, source, num_colors, random_state)
 
         def close(end, stats):
             """the open scene ends in front of stream frame `end`"""
