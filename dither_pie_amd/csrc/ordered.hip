@@ -44,6 +44,9 @@ struct Geo {
     uint32_t *dirty;        // workspace word: number of waves that flagged a pixel (zeroed per launch)
 };
 
+// Median of three in plain C++, for the running top-3 of the scans over a palette or a flat list (ordered_int_kernel,
+// resolve_pixel, resolve_wide).  med3_i32 below is the other form; each set of callers compiles to different code with the
+// other one (these scans to shorter code, the float kernels to longer), so merging the two is a change to measure on its own.
 __device__ __forceinline__ int med3i(const int a, const int b, const int c)
 {
     return max(min(a, b), min(max(a, b), c));
@@ -158,6 +161,64 @@ __device__ __forceinline__ void store_flags(unsigned long long *__restrict__ fla
         const uint32_t slot = atomicAdd(dirty, 1u);
         if (slot < (uint32_t)kQueueTiles) dirty[1 + slot] = tile;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-lane steps shared by the persistent tile kernels below (cell, lean, compact, fast, fine, lean_float,
+// compact_float): a lane's group of four pixels is the three dwords `w`, its position (fy, fx) is frame-local.
+// These are the steps that compile to the same code from a helper as written out.  Others repeat in the kernels on purpose --
+// the first-tile and prefetch loads, the thresholds of a quad (`LeanThr th[4]`, `tq[4]`), the tile class, the float top-3
+// chain, and the main-loop queue push of the lean and fine kernels (their drain loop sits inside the push's branch): moved
+// behind a call, each of them changed register allocation or operand order in some instantiation.
+// ---------------------------------------------------------------------------------------------
+
+// three dwords -> four packed pixels (0x00bbggrr)
+__device__ __forceinline__ void unpack4(const uint3 w, uint32_t x[4])
+{
+    x[0] = w.x & 0xffffffu;
+    x[1] = __builtin_amdgcn_perm(w.y, w.x, 0x0c050403u);
+    x[2] = __builtin_amdgcn_perm(w.z, w.y, 0x0c040302u);
+    x[3] = w.z >> 8;
+}
+
+// four colours -> three dwords
+__device__ __forceinline__ uint3 pack4(const uint32_t c[4])
+{
+    uint3 w;
+    w.x = __builtin_amdgcn_perm(c[1], c[0], 0x04020100u);
+    w.y = __builtin_amdgcn_perm(c[2], c[1], 0x05040201u);
+    w.z = __builtin_amdgcn_perm(c[3], c[2], 0x06050402u);
+    return w;
+}
+
+// this lane's position in the workgroup's next tile (no division: Geo.adv_y / adv_x)
+__device__ __forceinline__ void tile_advance(const Geo &g, uint32_t &fy, uint32_t &fx)
+{
+    fx += g.adv_x;
+    fy += g.adv_y;
+    if (fx >= g.w) {
+        fx -= g.w;
+        ++fy;
+    }
+    if (fy >= g.h) fy -= g.h;
+}
+
+// all clear for the wave tile of group gidx (its four flag words); a deferred path ORs in the bits of the pixels it leaves
+// to the fix-up pass later (flag_slow_pixel)
+__device__ __forceinline__ void clear_flags(unsigned long long *flags, const uint32_t gidx, const uint32_t lane)
+{
+    if (lane < 4u) flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+}
+
+// Wave-private deferral queue in LDS, `qcount` entries (wave-uniform): the lanes that `want` append their entry, densely.
+// Returns whether any lane did.
+__device__ __forceinline__ bool queue_push(uint32_t *s_queue, uint32_t &qcount, const bool want, const uint32_t entry)
+{
+    const unsigned long long mb = __ballot(want);
+    if (mb == 0ull) return false;
+    if (want) s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qcount))] = entry;
+    qcount += (uint32_t)__popcll(mb);
+    return true;
 }
 
 // MODE: 0 nearest only; 1 matrix in integer form (uint32 compare); 2 matrix f32; 3 IGN
@@ -612,13 +673,7 @@ __global__ __launch_bounds__(kCellBlock) void ordered_cell_kernel(const uint8_t 
         store_flags(flags, g.dirty, gidx, slow);
 
         // advance this lane's coordinates to its group in the next tile (no division)
-        fx += g.adv_x;
-        fy += g.adv_y;
-        if (fx >= g.w) {
-            fx -= g.w;
-            ++fy;
-        }
-        if (fy >= g.h) fy -= g.h;
+        tile_advance(g, fy, fx);
     }
 }
 
@@ -995,18 +1050,11 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
             const uint32_t next = tile + gridDim.x;
             const uint32_t gn = next * kCellBlock + threadIdx.x;
             if (next < n_tiles && gn < n_full) wn = in3[gn];  // prefetch the next tile
-            fx += g.adv_x;
-            fy += g.adv_y;
-            if (fx >= g.w) {
-                fx -= g.w;
-                ++fy;
-            }
-            if (fy >= g.h) fy -= g.h;
+            tile_advance(g, fy, fx);
             cls_word = 0;
             if (next < n_tiles) tile_class(fy, fx, gn);
         }
-        // all clear; lean_pixel_full ORs in the bits of the pixels it leaves to the fix-up pass later
-        if (lane < 4u) flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+        clear_flags(flags, gidx, lane);
         bool rare[4] = {false, false, false, false};
         uint32_t n_hard = 0;  // deep mode: pixels of this wave tile that needed more than their cell's block
         if (ADAPT && deep && gidx < n_full) {
@@ -1014,10 +1062,7 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
             // their colours exactly where the pixels are): resolve the four pixels completely right here instead of
             // computing a throw-away result and queueing them.
             uint32_t xq[4];
-            xq[0] = wc.x & 0xffffffu;
-            xq[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xq[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xq[3] = wc.z >> 8;
+            unpack4(wc, xq);
             LeanThr th[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1063,19 +1108,12 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
                     if (slow) flag_slow_pixel(gidx * 4u + (uint32_t)q, flags, g);
                     hard_bits += hard ? 1u : 0u;
                 }
-                uint3 wo;
-                wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-                wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-                wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-                out3[gidx] = wo;
+                out3[gidx] = pack4(col);
                 n_hard = hard_bits;
             }
         } else if (gidx < n_full) {
             uint32_t xq[4];
-            xq[0] = wc.x & 0xffffffu;
-            xq[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xq[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xq[3] = wc.z >> 8;
+            unpack4(wc, xq);
             uint32_t blk[4];
             uint4 ca[4], cb[4];
 #pragma unroll
@@ -1150,11 +1188,7 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
                     }
                     col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + (blk[q] | ((uint32_t)sel & 0xfcu)));
                 }
-                uint3 wo;
-                wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-                wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-                wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-                out3[gidx] = wo;
+                out3[gidx] = pack4(col);
             };
             if (MODE == 0) body(std::integral_constant<int, 15>{});
             else if (MODE == 3 || ADAPT) body(std::integral_constant<int, 0>{});
@@ -1184,12 +1218,7 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
                 __threadfence_block();  // the group stores that are about to be overwritten
                 uint32_t rest = 0u;
                 if (!HALF || lane < nq) rest = lean_pixel_full<MODE, BW, WARP>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, sx, sy, sc);
-                const unsigned long long mb = __ballot(rest != 0u);  // groups with a further deferred pixel go back
-                if (mb != 0ull) {
-                    if (rest != 0u)
-                        s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qcount))] = rest;
-                    qcount += (uint32_t)__popcll(mb);
-                }
+                queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
             }
         }
         // adapt: more than a third of the last 256 pixels rare -> deep mode; fewer than an eighth hard -> back
@@ -1208,12 +1237,7 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
         __threadfence_block();
         uint32_t rest = 0u;
         if (lane < n) rest = lean_pixel_full<MODE, BW, WARP>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, sx, sy, sc);
-        const unsigned long long mb = __ballot(rest != 0u);
-        if (mb != 0ull) {
-            if (rest != 0u)
-                s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qcount))] = rest;
-            qcount += (uint32_t)__popcll(mb);
-        }
+        queue_push(s_queue, qcount, rest != 0u, rest);
     }
 }
 
@@ -1457,21 +1481,12 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_compact_kern
             const uint32_t next = tile + gridDim.x;
             const uint32_t gn = next * kCellBlock + threadIdx.x;
             if (next < n_tiles && gn < n_full) wn = in3[gn];  // prefetch the next tile
-            fx += g.adv_x;
-            fy += g.adv_y;
-            if (fx >= g.w) {
-                fx -= g.w;
-                ++fy;
-            }
-            if (fy >= g.h) fy -= g.h;
+            tile_advance(g, fy, fx);
         }
         bool slowq[4] = {false, false, false, false};  // pixels left to the fix-up pass (single colours with more than 8 candidates, codes no pair expresses)
         if (gidx < n_full && !((MODE != 0) && (cx + 3u >= g.w))) {
             uint32_t xq[4];
-            xq[0] = wc.x & 0xffffffu;
-            xq[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xq[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xq[3] = wc.z >> 8;
+            unpack4(wc, xq);
             LeanThr th[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1518,11 +1533,7 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_compact_kern
                 col[q] = pick(xq[q], m0[q], m1[q], m2[q], nearest[q], code[q], slow);
                 slowq[q] = slow;
             }
-            uint3 wo;
-            wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-            wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-            wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-            out3[gidx] = wo;
+            out3[gidx] = pack4(col);
         } else {
             // a group that runs over the end of its row (its pixels' threshold positions differ) or the partial last group
 #pragma unroll 1
@@ -1539,8 +1550,8 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_compact_kern
         // the wave tile's flag words: plain stores of the four ballots (usually zero), the tile queued for the fix-up pass if not
         if (__ballot(slowq[0] | slowq[1] | slowq[2] | slowq[3]) != 0ull)
             store_flags(flags, g.dirty, gidx, slowq);
-        else if (lane < 4u)
-            flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+        else
+            clear_flags(flags, gidx, lane);
     }
 }
 
@@ -1810,14 +1821,9 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
         if (lane < n) fast_pixel_global<MODE, BW>(s_qb[qb + lane], in, out, flags, g, pal, thr, s_thr, sx, sy, sc);
     };
     auto push_b = [&](const bool want, const uint32_t p) {
-        const unsigned long long mb = __ballot(want);
-        if (mb != 0ull) {
-            if (want) s_qb[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qb))] = p;
-            qb += (uint32_t)__popcll(mb);
-            if (qb >= 64u) {
-                __threadfence_block();  // the stores of the main loop that the drain overwrites
-                drain_b(64u);
-            }
+        if (queue_push(s_qb, qb, want, p) && qb >= 64u) {
+            __threadfence_block();  // the stores of the main loop that the drain overwrites
+            drain_b(64u);
         }
     };
     // queue A, second half: the bytes asked for one tile ago have arrived.  Pixels of split cells are resolved on the
@@ -1827,10 +1833,7 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
         uint32_t mask = pend_e & 15u;
         const uint32_t group = pend_e >> 4;
         uint32_t xq[4];
-        xq[0] = pend_w.x & 0xffffffu;
-        xq[1] = __builtin_amdgcn_perm(pend_w.y, pend_w.x, 0x0c050403u);
-        xq[2] = __builtin_amdgcn_perm(pend_w.z, pend_w.y, 0x0c040302u);
-        xq[3] = pend_w.z >> 8;
+        unpack4(pend_w, xq);
         while (__ballot(mask != 0u) != 0ull) {  // wave-uniform: nearly always one round (one deferred pixel per group)
             const bool have = mask != 0u;
             const uint32_t k = (uint32_t)__builtin_ctz(mask | 16u) & 3u;
@@ -1904,24 +1907,14 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
             const uint32_t gn = next * kCellBlock + threadIdx.x;
             if (next < n_tiles && gn < n_full) wn = in3[gn];  // prefetch the next tile
             // ... and its position and class
-            fx += g.adv_x;
-            fy += g.adv_y;
-            if (fx >= g.w) {
-                fx -= g.w;
-                ++fy;
-            }
-            if (fy >= g.h) fy -= g.h;
+            tile_advance(g, fy, fx);
             cls_next = next < n_tiles ? tile_class(fy, fx, gn) : 0u;
         }
-        // all clear; the deferred paths OR in the bits of the pixels they leave to the fix-up pass later
-        if (lane < 4u) flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+        clear_flags(flags, gidx, lane);
         bool rare[4] = {false, false, false, false};
         if (gidx < n_full) {
             uint32_t xq[4];
-            xq[0] = wc.x & 0xffffffu;
-            xq[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xq[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xq[3] = wc.z >> 8;
+            unpack4(wc, xq);
             uint32_t blk[4];
             uint4 ca[4], cb[4];
 #pragma unroll
@@ -1992,20 +1985,11 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
                 }
                 col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + (blk[q] | ((uint32_t)sel & 0xfcu)));
             }
-            uint3 wo;
-            wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-            wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-            wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-            out3[gidx] = wo;
+            out3[gidx] = pack4(col);
         }
         // one queue entry per group with deferred pixels: group << 4 | which of its four
         const uint32_t rmask = (rare[0] ? 1u : 0u) | (rare[1] ? 2u : 0u) | (rare[2] ? 4u : 0u) | (rare[3] ? 8u : 0u);
-        const unsigned long long rb = __ballot(rmask != 0u);
-        if (rb != 0ull) {  // wave-uniform
-            if (rmask != 0u)
-                s_qa[__builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, qa))] = (gidx << 4) | rmask;
-            qa += (uint32_t)__popcll(rb);
-        }
+        queue_push(s_qa, qa, rmask != 0u, (gidx << 4) | rmask);
         // the partial last group (its twelve bytes may not all exist): pixel by pixel through queue B
         if ((tile + 1u) * kCellBlock > n_full) {  // scalar: the last tile of the launch only
 #pragma unroll
@@ -2174,12 +2158,6 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
     uint3 *out3 = reinterpret_cast<uint3 *>(out);
     const uint32_t n_full = g.n_px >> 2;  // groups of four whole pixels; a partial last group goes through the queue
 
-    auto unpack = [](const uint3 w, uint32_t xq[4]) {
-        xq[0] = w.x & 0xffffffu;
-        xq[1] = __builtin_amdgcn_perm(w.y, w.x, 0x0c050403u);
-        xq[2] = __builtin_amdgcn_perm(w.z, w.y, 0x0c040302u);
-        xq[3] = w.z >> 8;
-    };
     // the window numbers of a group's four pixels
     auto windows = [&](const uint32_t xq[4], uint32_t win[4]) {
 #pragma unroll
@@ -2190,12 +2168,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         __threadfence_block();  // the group stores that are about to be overwritten
         uint32_t rest = 0u;
         if (lane < n) rest = fine_pixel_full<MODE>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
-        const unsigned long long mb = __ballot(rest != 0u);  // groups with a further deferred pixel go back
-        if (mb != 0ull) {
-            if (rest != 0u)
-                s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, qcount))] = rest;
-            qcount += (uint32_t)__popcll(mb);
-        }
+        queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
     };
 
     uint32_t tile = blockIdx.x;
@@ -2209,7 +2182,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         const uint32_t gidx1 = gidx0 + gridDim.x * kCellBlock;
         if (tile + gridDim.x < n_tiles && gidx1 < n_full) wnn = in3[gidx1];
     }
-    unpack(wn, xn);
+    unpack4(wn, xn);
     windows(xn, winn);
     // (classes of the wave tiles: see ordered_lean_kernel)
     const bool use_cls = thr.has_cls != 0;
@@ -2239,24 +2212,17 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         const uint32_t cy = fy, cx = fx;  // this tile's position; fy / fx move on to the next tile's
         {
             // the next tile's groups arrived during the last one: ask for their windows now, and for the groups after them
-            unpack(wnn, xn);
+            unpack4(wnn, xn);
             windows(xn, winn);
             const uint32_t next = tile + gridDim.x, next2 = next + gridDim.x;
             const uint32_t gn = next * kCellBlock + threadIdx.x, gn2 = next2 * kCellBlock + threadIdx.x;
             wnn = make_uint3(0u, 0u, 0u);
             if (next2 < n_tiles && gn2 < n_full) wnn = in3[gn2];
-            fx += g.adv_x;
-            fy += g.adv_y;
-            if (fx >= g.w) {
-                fx -= g.w;
-                ++fy;
-            }
-            if (fy >= g.h) fy -= g.h;
+            tile_advance(g, fy, fx);
             cls_word = 0;
             if (next < n_tiles) tile_class(fy, fx, gn);
         }
-        // all clear; the deferred path ORs in the bits of the pixels it leaves to the fix-up pass later
-        if (lane < 4u) flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
+        clear_flags(flags, gidx, lane);
         bool rare[4] = {false, false, false, false};
         if (gidx < n_full) {
             uint4 ca[4];
@@ -2315,11 +2281,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
                         col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((pos < 16u ? (win[q] << 4) : pb[q]) + pos));
                     }
                 }
-                uint3 wo;
-                wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-                wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-                wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-                out3[gidx] = wo;
+                out3[gidx] = pack4(col);
             };
             if (cls == 5u) body(std::integral_constant<int, 5>{});
             else if (cls == 10u) body(std::integral_constant<int, 10>{});
@@ -2358,6 +2320,8 @@ struct alignas(16) Cand3 {  // the coordinates of a candidate record: one ds_rea
     float x, y, z;
 };
 
+// Median of three as one v_med3_i32, for the float kernels' top-3 chain over eight keys: from med3i's min/max form the
+// compiler does not rebuild the instruction there (24-28 more instructions per kernel), so the two stay apart (see med3i).
 __device__ __forceinline__ int med3_i32(const int a, const int b, const int c)
 {
     int r;
@@ -2417,10 +2381,7 @@ __global__ __launch_bounds__(kCellBlock) void ordered_lean_float_kernel(const ui
         bool slow[4] = {false, false, false, false};
         if (gidx < n_full) {
             uint32_t xs[4];
-            xs[0] = wc.x & 0xffffffu;
-            xs[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xs[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xs[3] = wc.z >> 8;
+            unpack4(wc, xs);
             float tq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (MODE == 2) {
                 uint32_t row, col;
@@ -2528,26 +2489,16 @@ __global__ __launch_bounds__(kCellBlock) void ordered_lean_float_kernel(const ui
                 slow[q] = s;
                 col[q] = cpick;
             }
-            uint3 wo;
-            wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-            wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-            wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-            out3[gidx] = wo;
+            out3[gidx] = pack4(col);
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) slow[q] = gidx * 4u + (uint32_t)q < g.n_px;  // the partial last group
         }
         if (__ballot(slow[0] | slow[1] | slow[2] | slow[3]) != 0ull)
             store_flags(flags, g.dirty, gidx, slow);
-        else if (lane < 4u)
-            flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
-        fx += g.adv_x;
-        fy += g.adv_y;
-        if (fx >= g.w) {
-            fx -= g.w;
-            ++fy;
-        }
-        if (fy >= g.h) fy -= g.h;
+        else
+            clear_flags(flags, gidx, lane);
+        tile_advance(g, fy, fx);
     }
 }
 
@@ -2669,10 +2620,7 @@ __global__ __launch_bounds__(kCellBlock) void ordered_compact_float_kernel(const
         bool slow[4] = {false, false, false, false};
         if (gidx < n_full) {
             uint32_t xs[4];
-            xs[0] = wc.x & 0xffffffu;
-            xs[1] = __builtin_amdgcn_perm(wc.y, wc.x, 0x0c050403u);
-            xs[2] = __builtin_amdgcn_perm(wc.z, wc.y, 0x0c040302u);
-            xs[3] = wc.z >> 8;
+            unpack4(wc, xs);
             float tq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (MODE == 2) {
                 uint32_t row, col;
@@ -2786,26 +2734,16 @@ __global__ __launch_bounds__(kCellBlock) void ordered_compact_float_kernel(const
                     }
                 }
             }
-            uint3 wo;
-            wo.x = __builtin_amdgcn_perm(col[1], col[0], 0x04020100u);
-            wo.y = __builtin_amdgcn_perm(col[2], col[1], 0x05040201u);
-            wo.z = __builtin_amdgcn_perm(col[3], col[2], 0x06050402u);
-            out3[gidx] = wo;
+            out3[gidx] = pack4(col);
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) slow[q] = gidx * 4u + (uint32_t)q < g.n_px;  // the partial last group
         }
         if (__ballot(slow[0] | slow[1] | slow[2] | slow[3]) != 0ull)
             store_flags(flags, g.dirty, gidx, slow);
-        else if (lane < 4u)
-            flags[(size_t)(gidx >> 6) * 4 + lane] = 0ull;
-        fx += g.adv_x;
-        fy += g.adv_y;
-        if (fx >= g.w) {
-            fx -= g.w;
-            ++fy;
-        }
-        if (fy >= g.h) fy -= g.h;
+        else
+            clear_flags(flags, gidx, lane);
+        tile_advance(g, fy, fx);
     }
 }
 
