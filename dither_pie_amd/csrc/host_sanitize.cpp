@@ -39,6 +39,8 @@
 //                                     (uint32) for tests/test_ordered_fine_cpu.py to check against numpy
 //   host_xxx fineplan <cases.bin> <n>   whether the fine kernel replaces a plan (ordered_fine.h: fine_replaces): n records of one
 //                                     OrderedFacts, one OrderedSwitches and one FineFacts; prints 0 / 1 per line
+//   host_xxx finekeys <cases.bin> <n>   the key level of the fine kernel (ordered_fine.h: fine_keys_level): n records of one FineFacts;
+//                                     prints one level per line
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -761,6 +763,26 @@ static int run_fineplan(const char *path, const int n_cases)
     return 0;
 }
 
+static int run_finekeys(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        FineFacts ff;
+        if (fread(&ff, sizeof(ff), 1, f) != 1 || ff.n_win < 0 || ff.thr_bytes < 0) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            fclose(f);
+            return 2;
+        }
+        printf("keys %d %d\n", c, fine_keys_level(ff));
+    }
+    fclose(f);
+    return 0;
+}
+
 // ---- void-and-cluster rank matrices ------------------------------------------------------------------------------
 static int run_voidcluster(const char *path, const int n_cases)
 {
@@ -906,7 +928,7 @@ static int run_okfit(const char *path, const int n_cases)
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -920,6 +942,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "metric") return run_metric(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "finekeys") return run_finekeys(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     const int K = atoi(argv[3]);

@@ -2022,6 +2022,10 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 // the index-ordered table in global memory with the complete code (fast_pixel_global's path), which is where the tie codes
 // are defined.  MODE 1 only (integer thresholds in LDS).
 // LDS (words): quads A | wide lists | pairs B | windows of the cells (u16) | wide cell numbers (u16) | thresholds | ... | queues
+// KEYS (ordered_fine.h: fine_keys_level): 0 is the above.  1 and 2 stage the pixel-independent part of every key of A (2: and of B)
+// beside the colours and form a key with two instructions instead of four (cand4k / cand6k, same values); their LDS holds
+//   quads A | norms of A | pairs B (1) or records B' {c4, c5, N4, N5} (2) | windows of the cells | wide cell numbers | thresholds
+// and the flat lists of the wide cells are read from the table image in global memory.
 // ---------------------------------------------------------------------------------------------
 
 // Keys of the six candidates of a window and the three smallest (see cand8)
@@ -2074,19 +2078,124 @@ __device__ __forceinline__ void cand6(const uint32_t x, const uint4 ca, const ui
           [ng] "s"(neg2));
 }
 
+// Key levels 1 and 2 (ordered_fine.h: fine_keys_level): the part of a key that does not depend on the pixel, N_j = (|c_j|^2 << 8)
+// + 4 j, is staged in LDS next to the colour, and a key is two instructions -- the same value as cand4n / cand6 compute with four.
+// cand4k: keys of the quad A from its norms na, and the two smallest
+__device__ __forceinline__ void cand4k(const uint32_t x, const uint4 ca, const uint4 na, const int neg2, int &m0, int &m1)
+{
+    int n0, n1, n2, n3, p0, p1, p2, p3;
+    asm volatile(
+        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
+        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
+        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
+        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
+        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
+        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
+        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
+        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
+        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
+        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
+        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
+        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
+        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2),
+          [p3] "=&v"(p3), [m0] "=&v"(m0), [m1] "=&v"(m1)
+        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [k0] "v"(na.x), [k1] "v"(na.y), [k2] "v"(na.z),
+          [k3] "v"(na.w), [ng] "s"(neg2));
+}
+
+// cand6k: keys of the six candidates of a window and the three smallest.  KEYS 1: the pair B comes as colours only (c4, c5; its two
+// keys take four instructions as in cand6); KEYS 2: with its norms k4, k5.
+template <int KEYS>
+__device__ __forceinline__ void cand6k(const uint32_t x, const uint4 ca, const uint4 na, const uint32_t c4, const uint32_t c5,
+                                       const uint32_t k4, const uint32_t k5, const int neg2, int &m0, int &m1, int &m2)
+{
+    int n0, n1, n2, n3, n4, n5, p0, p1, p2, p3, p4, p5;
+    if constexpr (KEYS == 1) {
+        (void)k4, (void)k5;
+        asm volatile(
+            "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
+            "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
+            "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
+            "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
+            "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
+            "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
+            "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
+            "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
+            "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
+            "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
+            "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
+            "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
+            "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
+            "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
+            "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
+            "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
+            // top-3 insertion network (m0 <= m1 <= m2)
+            "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
+            "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
+            "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n3]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n4]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n5]\n\t"
+            : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
+              [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
+              [m2] "=&v"(m2)
+            : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5), [k0] "v"(na.x),
+              [k1] "v"(na.y), [k2] "v"(na.z), [k3] "v"(na.w), [ng] "s"(neg2));
+    } else {
+        asm volatile(
+            "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
+            "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
+            "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
+            "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
+            "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
+            "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
+            "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
+            "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
+            "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
+            "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
+            "v_mad_i32_i24 %[n4], %[p4], %[ng], %[k4]\n\t"
+            "v_mad_i32_i24 %[n5], %[p5], %[ng], %[k5]\n\t"
+            // top-3 insertion network (m0 <= m1 <= m2)
+            "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
+            "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
+            "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n3]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n4]\n\t"
+            "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
+            "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
+            "v_min_i32 %[m0], %[m0], %[n5]\n\t"
+            : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
+              [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
+              [m2] "=&v"(m2)
+            : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5), [k0] "v"(na.x),
+              [k1] "v"(na.y), [k2] "v"(na.z), [k3] "v"(na.w), [k4] "v"(k4), [k5] "v"(k5), [ng] "s"(neg2));
+    }
+}
+
 // byte offset of the window number of x's cell: cell = r>>3 | (g>>3)<<5 | (b>>3)<<10 (host_logic.h: fine_cell), times 2
 __device__ __forceinline__ uint32_t fine_cell_offset(const uint32_t x)
 {
     return ((x >> 2) & 0x3eu) | ((x >> 5) & 0x7c0u) | ((x >> 8) & 0xf800u);
 }
 
-struct FineLds {  // where the parts of the table are, in bytes from the start of LDS
-    uint32_t wide_at, pair_at, off_at, ids_at, thr_at;
+struct FineLds {  // where the parts of the table are, in bytes from the start of LDS (wide_at: level 0 only; norm_at: levels 1, 2)
+    uint32_t wide_at, norm_at, pair_at, off_at, ids_at, thr_at;
 };
 
 // The deferred path (see lean_pixel_full): the lowest deferred pixel of a queue entry, from its bytes in memory to its bytes
-// in memory; returns the entry without that pixel.
-template <int MODE>
+// in memory; returns the entry without that pixel.  KEYS > 0: the flat lists of the wide cells are read where the table image has
+// them in global memory (pal.fine_tab, behind the quads), not from LDS.
+template <int MODE, int KEYS>
 __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                     unsigned long long *__restrict__ flags, const Geo &g, const PalDev &pal,
                                                     const ThrDev &thr, const uint32_t *s_words, const FineLds &at)
@@ -2109,7 +2218,8 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
 #pragma unroll
         for (uint32_t step = kFineIds / 2; step != 0u; step >>= 1)
             if ((uint32_t)ids[lo + step] <= cell) lo += step;
-        done = resolve_wide<MODE>(x, th, thr.sh, s_words + at.wide_at / 4 + lo * kWideList, kWideList, c);
+        if constexpr (KEYS == 0) done = resolve_wide<MODE>(x, th, thr.sh, s_words + at.wide_at / 4 + lo * kWideList, kWideList, c);
+        else done = resolve_wide<MODE>(x, th, thr.sh, pal.fine_tab + (uint32_t)pal.fine_win * kFineQuad + lo * kWideList, kWideList, c);
     }
     if (!done) {
         bool hard;
@@ -2126,7 +2236,7 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
     return rest ? ((entry & ~15u) | rest) : 0u;
 }
 
-template <int MODE>
+template <int MODE, int KEYS>
 __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                                     unsigned long long *__restrict__ flags, const Geo g,
                                                                     const PalDev pal, const ThrDev thr, const float sx, const float sy,
@@ -2134,22 +2244,58 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
 {
     static_assert(MODE == 1, "integer thresholds in LDS only");
     (void)sx, (void)sy, (void)sc;
+    static_assert(KEYS >= 0 && KEYS <= 2, "key levels: ordered_fine.h");
     __shared__ __align__(16) uint32_t smem[kLeanLdsWords];
-    // (two words at a time: every part is a whole number of word pairs, the pairs B of an odd number of windows no more than that,
-    // and the thresholds right behind the table are written by other lanes)
-    for (int i = threadIdx.x * 2; i < pal.fine_words; i += kCellBlock * 2)
-        *reinterpret_cast<uint2 *>(&smem[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[i]);
-    {
-        const int n = thr.th_h * thr.tw_pad;
-        for (int i = threadIdx.x; i < n; i += kCellBlock) smem[pal.fine_words + i] = thr.mpad[i];
-    }
-    __syncthreads();
     FineLds at;
-    at.wide_at = (uint32_t)pal.fine_win * (kFineQuad * 4);
-    at.pair_at = at.wide_at + (uint32_t)pal.fine_wide * (kWideList * 4);
-    at.off_at = at.pair_at + (uint32_t)pal.fine_win * ((kFineWindow - kFineQuad) * 4);
+    if constexpr (KEYS == 0) {
+        // (two words at a time: every part is a whole number of word pairs, the pairs B of an odd number of windows no more than that,
+        // and the thresholds right behind the table are written by other lanes)
+        for (int i = threadIdx.x * 2; i < pal.fine_words; i += kCellBlock * 2)
+            *reinterpret_cast<uint2 *>(&smem[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[i]);
+        at.wide_at = (uint32_t)pal.fine_win * (kFineQuad * 4);
+        at.norm_at = 0;
+        at.pair_at = at.wide_at + (uint32_t)pal.fine_wide * (kWideList * 4);
+        at.off_at = at.pair_at + (uint32_t)pal.fine_win * ((kFineWindow - kFineQuad) * 4);
+    } else {
+        // quads A {c0..c3} | their norms {N0..N3} | pairs B (level 1) or records B' {c4, c5, N4, N5} (level 2) | off, ids: built from
+        // the same image quads A | wide lists | pairs B | off, ids; the wide lists stay where they are.  Colours and norms of the quads
+        // are two arrays of 16-byte records, not one of 32-byte records: a ds_read_b128 of 32-byte records at random windows uses
+        // every other 16-byte slot of the bank row only, and half the slots means 1.45 x the conflict cycles.
+        constexpr int kPairRec = KEYS == 2 ? 4 : 2;  // words
+        const int n_win = pal.fine_win;
+        const int pair_src = n_win * kFineQuad + pal.fine_wide * kWideList;  // words into pal.fine_tab
+        const int tail_src = pair_src + n_win * (kFineWindow - kFineQuad);
+        at.wide_at = 0;
+        at.norm_at = (uint32_t)n_win * (kFineQuad * 4);
+        at.pair_at = 2 * at.norm_at;
+        at.off_at = at.pair_at + (uint32_t)n_win * (kPairRec * 4);
+        for (int wi = threadIdx.x; wi < n_win; wi += kCellBlock) {
+            const uint4 c = *reinterpret_cast<const uint4 *>(&pal.fine_tab[wi * kFineQuad]);
+            *reinterpret_cast<uint4 *>(&smem[wi * 4]) = c;
+            *reinterpret_cast<uint4 *>(&smem[n_win * 4 + wi * 4]) =
+                make_uint4((__builtin_amdgcn_udot4(c.x, c.x, 0u, false) << kLocalBits), (__builtin_amdgcn_udot4(c.y, c.y, 0u, false) << kLocalBits) + 4u,
+                           (__builtin_amdgcn_udot4(c.z, c.z, 0u, false) << kLocalBits) + 8u, (__builtin_amdgcn_udot4(c.w, c.w, 0u, false) << kLocalBits) + 12u);
+            const uint2 b = *reinterpret_cast<const uint2 *>(&pal.fine_tab[pair_src + wi * 2]);
+            if constexpr (KEYS == 2)
+                *reinterpret_cast<uint4 *>(&smem[n_win * 8 + wi * 4]) =
+                    make_uint4(b.x, b.y, (__builtin_amdgcn_udot4(b.x, b.x, 0u, false) << kLocalBits) + 16u,
+                               (__builtin_amdgcn_udot4(b.y, b.y, 0u, false) << kLocalBits) + 20u);
+            else
+                *reinterpret_cast<uint2 *>(&smem[n_win * 8 + wi * 2]) = b;
+        }
+        // (two words at a time: source and destination start at an even word)
+        uint32_t *s_tail = smem + at.off_at / 4;
+        for (int i = threadIdx.x * 2; i < (kFineCells + kFineIds) / 2; i += kCellBlock * 2)
+            *reinterpret_cast<uint2 *>(&s_tail[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[tail_src + i]);
+    }
     at.ids_at = at.off_at + kFineCells * 2;
     at.thr_at = at.ids_at + kFineIds * 2;
+    {
+        const int n = thr.th_h * thr.tw_pad;
+        const int thr_word = KEYS == 0 ? pal.fine_words : (int)(at.thr_at / 4);  // (the same place at level 0)
+        for (int i = threadIdx.x; i < n; i += kCellBlock) smem[thr_word + i] = thr.mpad[i];
+    }
+    __syncthreads();
     const uint8_t *s_bytes = reinterpret_cast<const uint8_t *>(smem);
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t *s_queue = smem + (kLeanLdsWords - kLeanQueueWords) + (threadIdx.x >> 6) * kLeanQueue;
@@ -2167,7 +2313,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         qcount -= n;
         __threadfence_block();  // the group stores that are about to be overwritten
         uint32_t rest = 0u;
-        if (lane < n) rest = fine_pixel_full<MODE>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
+        if (lane < n) rest = fine_pixel_full<MODE, KEYS>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
         queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
     };
 
@@ -2225,19 +2371,30 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         clear_flags(flags, gidx, lane);
         bool rare[4] = {false, false, false, false};
         if (gidx < n_full) {
-            uint4 ca[4];
+            constexpr int kPairShift = KEYS == 2 ? 4 : 3;  // pairs B of 8 B / records B' of 16 B
+            uint4 ca[4], na[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) ca[q] = *reinterpret_cast<const uint4 *>(s_bytes + (win[q] << 4));
+            for (int q = 0; q < 4; ++q) {
+                ca[q] = *reinterpret_cast<const uint4 *>(s_bytes + (win[q] << 4));
+                if constexpr (KEYS != 0) na[q] = *reinterpret_cast<const uint4 *>(s_bytes + ((win[q] << 4) + at.norm_at));
+            }
             // one straight-line body per class pattern (bit q: slot q takes its nearest entry whatever the second one is)
             auto body = [&](auto cls_c) {
                 constexpr uint32_t CLS = (uint32_t)decltype(cls_c)::value;
                 uint32_t pb[4];  // byte offset of the pair B, less the quad's sixteen: position 4 of the window is at + 16
-                uint2 cb[4];
+                uint2 cb[4], nb[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if ((CLS >> q) & 1u) continue;
-                    pb[q] = (win[q] << 3) + (at.pair_at - 16u);
-                    cb[q] = *reinterpret_cast<const uint2 *>(s_bytes + pb[q] + 16u);
+                    pb[q] = (win[q] << kPairShift) + (at.pair_at - 16u);
+                    if constexpr (KEYS == 2) {
+                        const uint4 v = *reinterpret_cast<const uint4 *>(s_bytes + pb[q] + 16u);
+                        cb[q] = make_uint2(v.x, v.y);
+                        nb[q] = make_uint2(v.z, v.w);
+                    } else {
+                        cb[q] = *reinterpret_cast<const uint2 *>(s_bytes + pb[q] + 16u);
+                        nb[q] = make_uint2(0u, 0u);
+                    }
                 }
                 LeanThr th[4];
 #pragma unroll
@@ -2263,12 +2420,14 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
                     const uint32_t x = xq[q];
                     if ((CLS >> q) & 1u) {
                         int m0, m1;
-                        cand4n(x, ca[q], g.neg2, m0, m1);
+                        if constexpr (KEYS == 0) cand4n(x, ca[q], g.neg2, m0, m1);
+                        else cand4k(x, ca[q], na[q], g.neg2, m0, m1);
                         rare[q] = ((uint32_t)(m0 ^ m1) < (1u << kLocalBits)) | straddle;  // a tie for the nearest entry; also: any wide cell
                         col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((win[q] << 4) | ((uint32_t)m0 & 0xfcu)));
                     } else {
                         int m0, m1, m2;
-                        cand6(x, ca[q], cb[q].x, cb[q].y, g.neg2, m0, m1, m2);
+                        if constexpr (KEYS == 0) cand6(x, ca[q], cb[q].x, cb[q].y, g.neg2, m0, m1, m2);
+                        else cand6k<KEYS>(x, ca[q], na[q], cb[q].x, cb[q].y, nb[q].x, nb[q].y, g.neg2, m0, m1, m2);
                         const int a0 = m0 >> kLocalBits, a1 = m1 >> kLocalBits;
                         const bool tie = (a0 == a1) | ((uint32_t)(m1 ^ m2) < (1u << kLocalBits));  // also: any wide cell
                         const int xx = (int)__builtin_amdgcn_udot4(x, x, 0u, false);
@@ -3023,20 +3182,23 @@ int num_cus()
 // experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel of every launch on stderr (tests that must know which
 // kernel a case reached): the family, then the template arguments and the table of the plan and the fix-up pass's queue; the
 // product library compiles to nothing here
-// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine"
-static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine)
+// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine keys=<level>"
+static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine, int keys)
 {
 #ifdef DP_EXPERIMENTS
     if (std::getenv("DP_ORDERED_TRACE")) {
         constexpr const char *tables[] = {"plain8", "plain4", "warped"};
-        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s\n",
+        char keys_s[16] = "";
+        if (fine) snprintf(keys_s, sizeof(keys_s), " keys=%d", keys);
+        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s%s\n",
                 family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
-                p.fix_big_queue ? 1 : 0, fine ? "fine" : family_name(p.family));
+                p.fix_big_queue ? 1 : 0, fine ? "fine" : family_name(p.family), keys_s);
     }
 #else
     (void)p;
     (void)aligned;
     (void)fine;
+    (void)keys;
 #endif
 }
 
@@ -3086,6 +3248,20 @@ TileKernel tile_kernel(const OrderedPlan &p)
     case 1: return tile_kernel_of<1>(p);
     case 2: return tile_kernel_of<2>(p);
     case 3: return tile_kernel_of<3>(p);
+    }
+    return nullptr;
+}
+
+// the fine kernel at a key level (ordered_fine.h: fine_keys_level, kFineKeysShipped: level 2 is an instance of the experiments
+// build only, the A/B partner that showed it slower than level 1)
+TileKernel fine_kernel(const int keys)
+{
+    switch (keys) {
+    case 0: return ordered_fine_kernel<1, 0>;
+    case 1: return ordered_fine_kernel<1, 1>;
+#ifdef DP_EXPERIMENTS
+    case 2: return ordered_fine_kernel<1, 2>;
+#endif
     }
     return nullptr;
 }
@@ -3177,10 +3353,15 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         g.adv_x = plan.adv_x;
         const bool brute = plan.family == kFamBrute;
         // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where its table exists and fits
-        const bool fine = fine_replaces(plan, FineFacts{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, thr.th_h * thr.tw_pad * 4}) &&
-                          !exp_env("DP_NO_FINE_KERNEL");
+        const FineFacts fine_facts{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, thr.th_h * thr.tw_pad * 4};
+        const bool fine = fine_replaces(plan, fine_facts) && !exp_env("DP_NO_FINE_KERNEL");
+        // ... at the highest key level whose LDS layout fits, up to the one that measured fastest (experiments:
+        // DP_FINE_KEYS_MAX=0|1|2 in place of that cap)
+        int keys_cap = kFineKeysShipped;
+        if (const char *cap = exp_env("DP_FINE_KEYS_MAX")) keys_cap = std::min(2, std::max(0, std::atoi(cap)));
+        const int fine_keys = fine ? std::min(fine_keys_level(fine_facts), keys_cap) : 0;
         const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
-        const TileKernel tile_k = brute ? nullptr : (fine ? ordered_fine_kernel<1> : tile_kernel(plan));
+        const TileKernel tile_k = brute ? nullptr : (fine ? fine_kernel(fine_keys) : tile_kernel(plan));
         const FixKernel fix_k = fix_kernel(plan);
         if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
             set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
@@ -3209,7 +3390,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_plan(plan, g.aligned, fine);
+        trace_plan(plan, g.aligned, fine, fine_keys);
         prof_mid(pm, s);
         hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);

@@ -38,4 +38,29 @@ inline bool fine_replaces(const OrderedPlan &p, const FineFacts &f)
            fine_table_bytes(f.n_win, f.n_wide) + (int64_t)f.thr_bytes <= kLeanTabBytes;
 }
 
+// Key levels of the kernel (ordered.hip: ordered_fine_kernel<MODE, KEYS>).  A candidate key is (|c|^2 << 8) + 4 * position
+// - 2 * (x . c) << 8; everything but the last term is a constant of the window position.  Level 0 computes it per pixel from the
+// staged image above (four instructions per key).  Levels 1 and 2 build another layout in LDS from the same global image, with that
+// constant N next to the colour (two instructions per key), and leave the flat lists of the wide cells in global memory:
+//   quads A {c0..c3} [n_win x 16 B] | their norms {N0..N3} [n_win x 16 B] | level 1: pairs B [n_win x 8 B], level 2: records B'
+//   {c4, c5, N4, N5} [n_win x 16 B] | window of every cell | cell numbers of the wide cells | integer thresholds
+constexpr int64_t fine_keys_bytes(const int level, const int n_win)
+{
+    return (int64_t)n_win * (level == 2 ? 48 : 40) + kFineCells * 2 + kFineIds * 2;
+}
+// the highest level whose layout fits next to the thresholds; consulted where fine_replaces says yes (tests/test_ordered_fine_keys_cpu.py)
+inline int fine_keys_level(const FineFacts &f)
+{
+    if (f.present == 0) return 0;
+    for (int level = 2; level >= 1; --level)
+        if (fine_keys_bytes(level, f.n_win) + (int64_t)f.thr_bytes <= kLeanTabBytes) return level;
+    return 0;
+}
+
+// The highest level the library launches by itself.  Level 2 fits the headline's table, but measured slower than level 1 on MI355X:
+// once the keys are two instructions the LDS pipe limits the kernel as much as the vector issue does, and the 16-byte reads of B'
+// cost it more than the four instructions they save (profiles/experiments/fine_keys_levels.md).  The level-2 instance
+// exists in the experiments build only (DP_FINE_KEYS_MAX=2).
+constexpr int kFineKeysShipped = 1;
+
 }  // namespace dp
