@@ -407,8 +407,18 @@ int dp_palette_accel_info(const dp_palette *p, int *pool_entries, int *max_cell)
 }
 
 // ---- thresholds --------------------------------------------------------------------------------
+// A constructor that was given a stream uploads on that stream and waits for it there: a synchronous hipMemcpy is ordered on
+// the null stream, so it would also wait for whatever the null stream is running.  Either way the bytes are on the device when
+// this returns, for every stream.
+static hipError_t thresholds_upload(void *dst, const void *src, size_t bytes, bool on_stream, hipStream_t s)
+{
+    if (!on_stream) return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
 static int thresholds_from_device_f32(float *dev_f32, int th_h, int th_w, const float *host_copy,
-                                      dp_thresholds **out)
+                                      dp_thresholds **out, bool on_stream = false, hipStream_t stream = nullptr)
 {
     // integer form t = m / 2^sh with sh <= 13 and 0 <= t <= 1 lets the kernel decide in uint32
     const int n = th_h * th_w;
@@ -436,7 +446,7 @@ static int thresholds_from_device_f32(float *dev_f32, int th_h, int th_w, const 
         for (int i = 0; i < n; ++i) m[i] = (uint32_t)((double)host_copy[i] * (double)(1u << sh));
         // the integer table lives behind the f32 table in the same allocation
         uint32_t *dm = (uint32_t *)(dev_f32 + n);
-        hipError_t e = hipMemcpy(dm, m.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+        hipError_t e = thresholds_upload(dm, m.data(), sizeof(uint32_t) * n, on_stream, stream);
         if (e != hipSuccess) {
             delete t;
             return hip_fail(e, "thresholds integer upload");
@@ -478,7 +488,7 @@ static int thresholds_from_device_f32(float *dev_f32, int th_h, int th_w, const 
         }
         void *dp = nullptr;
         hipError_t e = hipMalloc(&dp, sizeof(uint32_t) * pad.size());
-        if (e == hipSuccess) e = hipMemcpy(dp, pad.data(), sizeof(uint32_t) * pad.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = thresholds_upload(dp, pad.data(), sizeof(uint32_t) * pad.size(), on_stream, stream);
         if (e != hipSuccess) {
             if (dp) (void)hipFree(dp);
             delete t;
@@ -527,12 +537,13 @@ int dp_thresholds_blue_noise(int size, uint32_t seed, void *stream, dp_threshold
     float *d = nullptr;
     void *scratch = nullptr;
     DP_HIP(hipMalloc((void **)&d, sizeof(float) * 2 * (size_t)n));
-    hipError_t e = hipMalloc(&scratch, blue_noise_scratch_bytes(size));
+    hipStream_t s = (hipStream_t)stream;
+    // stream-ordered scratch: hipFree would wait for every stream of the device, the null stream included
+    hipError_t e = hipMallocAsync(&scratch, blue_noise_scratch_bytes(size), s);
     if (e != hipSuccess) {
         (void)hipFree(d);
         return hip_fail(e, "blue-noise scratch");
     }
-    hipStream_t s = (hipStream_t)stream;
     int rc = launch_blue_noise(size, seed, d, scratch, s);
     std::vector<float> host(n);
     if (rc == DP_OK) {
@@ -540,8 +551,8 @@ int dp_thresholds_blue_noise(int size, uint32_t seed, void *stream, dp_threshold
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = hip_fail(e, "blue-noise download");
     }
-    (void)hipFree(scratch);
-    if (rc == DP_OK) rc = thresholds_from_device_f32(d, size, size, host.data(), out);
+    (void)hipFreeAsync(scratch, s);
+    if (rc == DP_OK) rc = thresholds_from_device_f32(d, size, size, host.data(), out, true, s);
     if (rc != DP_OK) (void)hipFree(d);
     return rc;
 }
@@ -1138,11 +1149,11 @@ int dp_thresholds_void_cluster(int h, int w, uint32_t seed, int sigma256, void *
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess) {
             vac_thresholds(ranks.data(), n, host.data());
-            e = hipMemcpy(d, host.data(), sizeof(float) * n, hipMemcpyHostToDevice);
+            e = thresholds_upload(d, host.data(), sizeof(float) * n, true, s);
         }
         if (e != hipSuccess) rc = hip_fail(e, "void-and-cluster download");
     }
-    if (rc == DP_OK) rc = thresholds_from_device_f32(d, h, w, host.data(), out);
+    if (rc == DP_OK) rc = thresholds_from_device_f32(d, h, w, host.data(), out, true, s);
     if (rc != DP_OK) (void)hipFree(d);
     return rc;
 }

@@ -112,7 +112,11 @@ int dp_kdtree_build_host(const double *pts, int K, int32_t *indices, int32_t *sp
  * dp_thresholds_create: upload a th_h x th_w float32 matrix (Bayer tables
  * dithering_lib.py:1705-1768, polka-dot, any MatrixDitherStrategy matrix).
  * dp_thresholds_blue_noise: generate_blue_noise(size, seed) (dithering_lib.py:381-399) computed on
- * the device, including numpy's legacy RandomState(seed).shuffle.
+ * the device, including numpy's legacy RandomState(seed).shuffle.  Unlike the launches below it ALLOCATES device
+ * memory and WAITS for `stream` (the generation, the download for the integer form and the uploads of the finished
+ * tables all run on `stream` and are complete for every stream when it returns); it does not wait for any other
+ * stream, the null stream included.  Not for use inside a graph capture.
+ * dp_thresholds_create uploads with synchronous copies, which are ordered on the null stream.
  * dp_thresholds_download copies the float32 matrix to host memory (th_h*th_w floats). */
 int dp_thresholds_create(const float *thr_host, int th_h, int th_w, dp_thresholds **out);
 int dp_thresholds_blue_noise(int size, uint32_t seed, void *stream, dp_thresholds **out);

@@ -56,7 +56,8 @@ int dp_void_cluster_host(uint16_t *ranks_host, int h, int w, uint32_t seed, int 
 
 /* The dp_thresholds_blue_noise counterpart: generates the matrix on the device, downloads it, applies step 6 and builds the
  * dp_thresholds (integer form and padded table included).  Unlike dp_void_cluster_u16 it ALLOCATES device memory and
- * SYNCHRONISES the stream: not for use inside a graph capture.  Free the result with dp_thresholds_destroy.
+ * SYNCHRONISES the stream (and no other: its copies run on `stream`, not on the null stream): not for use inside a
+ * graph capture.  Free the result with dp_thresholds_destroy.
  * DP_EINVAL: out == NULL or a size or sigma256 out of range, before any HIP call. */
 int dp_thresholds_void_cluster(int h, int w, uint32_t seed, int sigma256, void *stream, dp_thresholds **out);
 
