@@ -35,6 +35,24 @@ inline const char *exp_env(const char *name)
 }
 int hip_fail(hipError_t e, const char *what);
 
+// experiments build only: DP_ED_TRACE=1 names the kernel of every launch_error_diffusion / launch_variable_diffusion call on
+// stderr, before the launch (tests that must know which instantiation and which schedule a case reached): the kernel with its
+// template arguments as the launcher spells them, then the launch as the launcher computed it.  schedule: one_wg (a workgroup
+// per frame), spread (G > 1 workgroups per frame, repair=1: the one-workgroup repair launch follows), persistent (fewer
+// workgroups than frames), rowserial (a wave per frame, rows in LDS), serial (lane = frame).  lds: dynamic bytes of the launch.
+// The product library compiles to nothing here.
+inline void trace_diffusion(const char *kernel, const char *schedule, int G, long long grid, int waves, size_t lds, int K, int n_inner,
+                            int model, int numba, int serpentine)
+{
+#ifdef DP_EXPERIMENTS
+    if (std::getenv("DP_ED_TRACE"))
+        fprintf(stderr, "dp_diffusion: kernel=%s schedule=%s G=%d grid=%lld waves=%d lds=%zu K=%d n_inner=%d model=%d numba=%d serpentine=%d repair=%d\n",
+                kernel, schedule, G, grid, waves, lds, K, n_inner, model, numba, serpentine ? 1 : 0, G > 1 ? 1 : 0);
+#else
+    (void)kernel; (void)schedule; (void)G; (void)grid; (void)waves; (void)lds; (void)K; (void)n_inner; (void)model; (void)numba; (void)serpentine;
+#endif
+}
+
 #define DP_HIP(call)                                   \
     do {                                               \
         hipError_t e__ = (call);                       \

@@ -1058,8 +1058,12 @@ int launch_error_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, in
             if (G == 1 && v >= 1 && v <= n_frames && (n_frames + v - 1) / v * n_bands < 60000) pgrid = v;
         }
         const uint32_t nfr = (uint32_t)n_frames;
+        const char *sched = G > 1 ? "spread" : (pgrid < n_frames ? "persistent" : "one_wg");   // (DP_ED_TRACE: dp_internal.h)
 #define DP_EDW(C, N, X, S4, S)                                                                                               \
     do {                                                                                                                 \
+        trace_diffusion(nw <= 4 ? "ed_wavefront CAP=" #C " NT=" #N " EXACT=" #X " MAXW=4 NB=false PALS=" #S4                \
+                                : "ed_wavefront CAP=" #C " NT=" #N " EXACT=" #X " MAXW=kMaxWaves NB=false PALS=" #S,         \
+                        sched, G, (long long)pgrid, nw, 0, pal.K, pal.n_inner, 0, 0, serpentine);                          \
         if (nw <= 4)                                                                                                     \
             hipLaunchKernelGGL((ed_wavefront_kernel<C, N, X, 4, false, S4>), dim3((unsigned)pgrid), dim3(64 * nw), 0, s, in, out, h, w, \
                                pal, t, ws, G, gprog, test_giveup, nfr);                            \
@@ -1086,6 +1090,9 @@ int launch_error_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, in
             constexpr int kNbWaves = 8;
             if (nw > kNbWaves) nw = kNbWaves;  // (bands are dealt round-robin over whatever waves there are)
             const int nwr = nw1 < kNbWaves ? nw1 : kNbWaves;
+            trace_diffusion(nw <= 4 ? "ed_wavefront CAP=kQueueSmall NT=kMaxTaps EXACT=false MAXW=4 NB=true PALS=0"
+                                    : "ed_wavefront CAP=kQueueSmall NT=kMaxTaps EXACT=false MAXW=kNbWaves NB=true PALS=0",
+                            sched, G, (long long)pgrid, nw, 0, pal.K, pal.n_inner, 0, 1, serpentine);
             if (nw <= 4)
                 hipLaunchKernelGGL((ed_wavefront_kernel<kQueueSmall, kMaxTaps, false, 4, true>), dim3((unsigned)pgrid), dim3(64 * nw),
                                    0, s, in, out, h, w, pal, t, ws, G, gprog, test_giveup, nfr);
@@ -1115,6 +1122,8 @@ int launch_error_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, in
 #define DP_EDR(C, MM)                                                                                                   \
     do {                                                                                                               \
         auto kern = ed_rowserial_kernel<C, MM>;                                                                        \
+        trace_diffusion("ed_rowserial CAP=" #C " M=" #MM, "rowserial", 1, (long long)n_frames, 1, lds, pal.K, pal.n_inner, 0, 0, \
+                        serpentine);                                                                                   \
         DP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
                                    (int)lds));                                                                         \
         hipLaunchKernelGGL(kern, dim3((unsigned)n_frames), dim3(64), lds, s, in, out, h, w, pal, t, serpentine);        \
@@ -1129,6 +1138,9 @@ int launch_error_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, in
 #undef DP_EDR
     } else {
         const int64_t blocks = (n_frames + 63) / 64;
+        trace_diffusion(numba ? "ed_serial CAP=kQueueSmall NB=true"
+                              : (pal.n_inner > kQueueSmall || pal.K > 256) ? "ed_serial CAP=kQueueLarge NB=false" : "ed_serial CAP=kQueueSmall NB=false",
+                        "serial", 1, (long long)blocks, 1, 0, pal.K, pal.n_inner, 0, numba ? 1 : 0, serpentine);
         if (numba)  // serpentine scan with the numba arithmetic: the frame-parallel kernel (lane = frame)
             hipLaunchKernelGGL((ed_serial_kernel<kQueueSmall, true>), dim3((unsigned)blocks), dim3(64), 0, s, in, out, n_frames, h,
                                w, pal, t, serpentine, ws);

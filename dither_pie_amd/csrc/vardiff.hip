@@ -633,6 +633,11 @@ __device__ __forceinline__ float gray_of(const uint8_t *p, const uint8_t *lut)
 // (float)(t / size) as scipy computes it -- the double quotient correctly rounded, then rounded to float32 -- without the
 // ~40 instructions of a float64 division: q = t * (1/size) is within 2 ulp of the rounded quotient, and both round to the
 // same float32 unless a float32 rounding boundary (low 29 mantissa bits = 0x10000000) lies that close; then divide.
+// For the sizes the fused kernel is compiled for (1, 3, 5, 7, 9) the division never changes the result: the window sums are short dyadic
+// numbers, so q comes that close to a boundary only on an exact tie (t = size * a float32 midpoint; 2-9 % of the windows of noise), and there
+// t * fl(1 / size) rounds to the midpoint itself (size * fl(1 / size) rounds to 1.0 for every odd size below 49) and then to even as the quotient
+// does.  The first size at which a tie comes out differently is 49 (radius 24).  So no input of tests/test_gpu_variance_gate.py can tell this
+// function from one without the fallback; it stays for a larger kGateMaxR.
 __device__ __forceinline__ float mean_f32(const double t, const double size, const double rcp)
 {
     double q = __dmul_rn(t, rcp);
@@ -777,6 +782,19 @@ size_t variance_gate_ws_bytes(int64_t n_frames, int h, int w)
     return (size_t)variance_gate_chunk(n_frames, h, w) * h * w * sizeof(float) * 2 + 256;
 }
 
+// experiments build only: DP_ED_TRACE=1 names the path of every launch_variance_gate call on stderr, before the launch (see
+// trace_diffusion, dp_internal.h); chunk: frames per launch.  The product library compiles to nothing here.
+static inline void trace_gate(const char *kernel, int radius, int64_t chunk)
+{
+#ifdef DP_EXPERIMENTS
+    if (std::getenv("DP_ED_TRACE")) fprintf(stderr, "dp_variance_gate: kernel=%s radius=%d chunk=%lld\n", kernel, radius, (long long)chunk);
+#else
+    (void)kernel;
+    (void)radius;
+    (void)chunk;
+#endif
+}
+
 int launch_variance_gate(const uint8_t *in, uint8_t *gate, int64_t n_frames, int h, int w, const PalDev &pal, float thr,
                          int radius, void *ws, hipStream_t s)
 {
@@ -786,6 +804,7 @@ int launch_variance_gate(const uint8_t *in, uint8_t *gate, int64_t n_frames, int
         return DP_EUNSUPPORTED;
     }
     if (radius <= kGateMaxR && !exp_env("DP_GATE_TWO_PASS")) {
+        trace_gate("fused", radius, std::min<int64_t>(65535, n_frames));
         for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
             const int64_t nf = std::min<int64_t>(65535, n_frames - f0);
             const dim3 grid((w + kGateTW - 1) / kGateTW, (h + kGateTH - 1) / kGateTH, (unsigned)nf);
@@ -807,6 +826,7 @@ int launch_variance_gate(const uint8_t *in, uint8_t *gate, int64_t n_frames, int
     const int64_t chunk = std::min<int64_t>(variance_gate_chunk(n_frames, h, w), 65535);
     float *t_sq = reinterpret_cast<float *>(ws);
     float *t_g = t_sq + (size_t)chunk * h * w;
+    trace_gate("two_pass", radius, chunk);
     for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {  // chunks run back to back on the stream and reuse the planes
         const int64_t nf = std::min<int64_t>(chunk, n_frames - f0);
         const uint8_t *in_c = in + (size_t)f0 * h * w * 3;
@@ -864,8 +884,11 @@ int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames,
             if (G == 1 && v >= 1 && v <= n_frames && (n_frames + v - 1) / v * n_bands < 60000) pgrid = v;
         }
         const uint32_t nfr = (uint32_t)n_frames;
+        const char *sched = G > 1 ? "spread" : (pgrid < n_frames ? "persistent" : "one_wg");   // (DP_ED_TRACE: dp_internal.h)
 #define DP_VARW(C, M)                                                                                                     \
     do {                                                                                                                 \
+        trace_diffusion("var_wavefront CAP=" #C " MODEL=" #M, sched, G, (long long)pgrid, nw, 0, pal.K, pal.n_inner, model, 0, \
+                        serpentine);                                                                                     \
         hipLaunchKernelGGL((var_wavefront_kernel<C, M>), dim3((unsigned)pgrid), dim3(64 * nw), 0, s, in, out, h, w, pal, vp, \
                            reinterpret_cast<float *>(ws), G, gprog, test_giveup, nfr);                                   \
         if (G > 1)                                                                                                       \
@@ -895,6 +918,8 @@ int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames,
 #define DP_OSR(C, MM)                                                                                                   \
     do {                                                                                                               \
         auto kern = os_rowserial_kernel<C, MM>;                                                                        \
+        trace_diffusion("os_rowserial CAP=" #C " M=" #MM, "rowserial", 1, (long long)n_frames, 1, lds, pal.K, pal.n_inner, model, 0, \
+                        serpentine);                                                                                   \
         DP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
                                    (int)lds));                                                                         \
         hipLaunchKernelGGL(kern, dim3((unsigned)n_frames), dim3(64), lds, s, in, out, h, w, pal, vp);                   \
@@ -912,6 +937,8 @@ int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames,
         return DP_OK;
     }
     const int64_t blocks = (n_frames + 63) / 64;
+    trace_diffusion(pal.n_inner > kQueueSmall ? "var_serial CAP=kQueueLarge" : "var_serial CAP=kQueueSmall", "serial", 1, (long long)blocks, 1, 0,
+                    pal.K, pal.n_inner, model, 0, serpentine);
     if (pal.n_inner > kQueueSmall)
         hipLaunchKernelGGL(var_serial_kernel<kQueueLarge>, dim3((unsigned)blocks), dim3(64), 0, s, in, out, n_frames, h, w,
                            pal, vp, reinterpret_cast<float *>(ws));
