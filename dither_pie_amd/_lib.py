@@ -230,6 +230,27 @@ _SIGS_OKFIT = {
     "dp_okfit_host": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(C.c_uint64)]),
 }
 EXPORTS_OKFIT = tuple(_SIGS_OKFIT)
+# include/ditherpie_hip_resample.h: filtered resize (Pillow's BOX / BILINEAR / HAMMING / BICUBIC / LANCZOS, bit for bit) and its
+# host statement; a table of its own for the same reason.  dp_resample_u8 takes its arguments, the stream among them, in a
+# descriptor whose first field is its own size.
+RESAMPLE_FILTERS = ("box", "bilinear", "hamming", "bicubic", "lanczos")   # DP_RESAMPLE_* order
+RESAMPLE_MAX_SIZE = 16384
+
+
+class ResampleArgs(C.Structure):
+    """dp_resample_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("in_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_frames", C.c_int64),
+                ("plan", C.c_void_p), ("workspace_dev", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+_SIGS_RESAMPLE = {
+    "dp_resample_plan_create": (_i, [_i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "dp_resample_plan_destroy": (None, [_vp]),
+    "dp_resample_workspace_bytes": (_sz, [_vp, _i64]),
+    "dp_resample_u8": (_i, [C.POINTER(ResampleArgs)]),
+    "dp_resample_host": (_i, [_i, _vp, _vp, _i64, _i, _i, _i, _i]),
+}
+EXPORTS_RESAMPLE = tuple(_SIGS_RESAMPLE)
 
 
 def build(force=False):
@@ -276,7 +297,7 @@ def load():
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
                                           + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
                                           + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())
-                                          + list(_SIGS_OKFIT.items())):
+                                          + list(_SIGS_OKFIT.items()) + list(_SIGS_RESAMPLE.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

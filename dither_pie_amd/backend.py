@@ -1365,6 +1365,128 @@ def resize_nearest(frames, oh, ow):
     return out if frames.dim() == 4 else out[0]
 
 
+# ------------------------------------------------------------------------------------- filtered resize
+# include/ditherpie_hip_resample.h: Pillow's Image.resize, bit for bit, for the filters that average.
+RESAMPLE_FILTERS = ("nearest",) + _lib.RESAMPLE_FILTERS   # what resample() takes; "nearest" is resize_nearest()
+RESAMPLE_MAX_SIZE = _lib.RESAMPLE_MAX_SIZE                # DP_RESAMPLE_MAX_SIZE
+
+
+def _resample_filter(name, nearest=True):
+    ok = RESAMPLE_FILTERS if nearest else _lib.RESAMPLE_FILTERS
+    if not isinstance(name, str) or name not in ok:
+        raise ValueError(f"unknown resize filter {name!r}: it must be one of {', '.join(ok)}")
+    return name
+
+
+def _resample_sizes(h, w, oh, ow):
+    for v in (h, w, oh, ow):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= RESAMPLE_MAX_SIZE:
+            raise ValueError(f"resize: every size must be an integer in 1 .. {RESAMPLE_MAX_SIZE}, not {v!r}")
+    if int(h) * int(w) > 1 << 30:
+        raise ValueError("resize: h * w must not exceed 2^30")
+    return int(h), int(w), int(oh), int(ow)
+
+
+class ResamplePlan:
+    """dp_resample_plan: the coefficient tables of one geometry (h x w -> oh x ow) and one filter, resident on the current
+    device.  Making one allocates and copies with a blocking call: not inside a graph capture."""
+
+    def __init__(self, filter, h, w, oh, ow):
+        self._h = None
+        self.filter = _resample_filter(filter, nearest=False)
+        self.h, self.w, self.oh, self.ow = _resample_sizes(h, w, oh, ow)
+        require_gpu()
+        L = _lib.load()
+        self._destroy = L.dp_resample_plan_destroy
+        self._lib_path = _lib.LIB_PATH
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        handle = C.c_void_p()
+        check(L.dp_resample_plan_create(_lib.RESAMPLE_FILTERS.index(self.filter), self.h, self.w, self.oh, self.ow, C.byref(handle)))
+        self._h = handle
+
+    def workspace_bytes(self, n_frames):
+        return int(_lib.load().dp_resample_workspace_bytes(self._h, int(n_frames)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._destroy(h)
+            self._h = None
+
+
+_RESAMPLE_PLANS = OrderedDict()   # (library, device, filter, h, w, oh, ow) -> ResamplePlan
+_RESAMPLE_PLANS_CAP = 16
+_resample_guard = threading.Lock()
+
+
+def _resample_plan(device, filter, h, w, oh, ow):
+    key = (_lib.LIB_PATH, device.index, filter, h, w, oh, ow)   # (a plan stays with the library that made it)
+    with _resample_guard:
+        plan = _RESAMPLE_PLANS.get(key)
+        if plan is not None:
+            _RESAMPLE_PLANS.move_to_end(key)
+            return plan
+    with torch.cuda.device(device):
+        plan = ResamplePlan(filter, h, w, oh, ow)
+    with _resample_guard:
+        plan = _RESAMPLE_PLANS.setdefault(key, plan)
+        while len(_RESAMPLE_PLANS) > _RESAMPLE_PLANS_CAP:
+            _RESAMPLE_PLANS.popitem(last=False)
+    return plan
+
+
+def drop_resample_plans():
+    with _resample_guard:
+        _RESAMPLE_PLANS.clear()
+
+
+def resample(frames, oh, ow, filter="lanczos", out=None, plan=None):
+    """Image.resize((ow, oh), filter) of uint8 RGB frames already in HBM, [N,H,W,3] or [H,W,3], bit-identical to Pillow for
+    box, bilinear, hamming, bicubic and lanczos (include/ditherpie_hip_resample.h); "nearest" is resize_nearest(), unchanged.
+    The plan of a geometry is made at its first use (a blocking upload: not inside a graph capture; pass `plan` there) and kept
+    in a small cache; the intermediate of the two passes is the stream's workspace."""
+    _resample_filter(filter)
+    f = _frames(frames)
+    n, h, w, _ = f.shape
+    if filter == "nearest":
+        if out is not None or plan is not None:
+            raise ValueError("resample: the nearest filter takes neither out nor plan")
+        return resize_nearest(frames, oh, ow)
+    h, w, oh, ow = _resample_sizes(h, w, oh, ow)
+    if plan is None:
+        plan = _resample_plan(f.device, filter, h, w, oh, ow)
+    elif (plan.filter, plan.h, plan.w, plan.oh, plan.ow, plan.device) != (filter, h, w, oh, ow, f.device):
+        raise ValueError("resample: the plan was made for another filter, geometry or device")
+    if out is None:
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=f.device)
+    else:
+        out = _check_buffer(out, f.device, (n, oh, ow, 3), torch.uint8, "out")
+        if n and out.data_ptr() == f.data_ptr():
+            raise ValueError("resample does not work in place: out must not be the frames")
+    L = _lib.load()
+    ws_bytes = plan.workspace_bytes(n)
+    with torch.cuda.device(f.device), _Launch(f.device, ws_bytes if ws_bytes else None) as ws:
+        a = _lib.ResampleArgs(C.sizeof(_lib.ResampleArgs), f.data_ptr() or None, out.data_ptr() or None, n, plan._h.value,
+                              ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream().value)
+        check(L.dp_resample_u8(C.byref(a)))
+    return out if frames.dim() == 4 else out[0]
+
+
+def resample_host(frames, oh, ow, filter="lanczos"):
+    """The same resize on the CPU (dp_resample_host: the host statement of the kernels): numpy uint8 [N,H,W,3] or [H,W,3] ->
+    numpy.  Needs no device."""
+    _resample_filter(filter, nearest=False)
+    f = np.ascontiguousarray(frames)
+    if f.dtype != np.uint8 or f.ndim not in (3, 4) or f.shape[-1] != 3:
+        raise ValueError("frames must be [N,H,W,3] or [H,W,3] uint8")
+    x = f[None] if f.ndim == 3 else f
+    n, h, w, _ = x.shape
+    h, w, oh, ow = _resample_sizes(h, w, oh, ow)
+    out = np.empty((n, oh, ow, 3), np.uint8)
+    check(_lib.load().dp_resample_host(_lib.RESAMPLE_FILTERS.index(filter), _np_ptr(x), _np_ptr(out), n, h, w, oh, ow))
+    return out[0] if f.ndim == 3 else out
+
+
 # ------------------------------------------------------------------------------------- indexed output
 # include/ditherpie_hip_indexed.h.  A dithered frame holds only the K output colours of its palette; an index plane is
 # the same image at one (two) byte(s) per pixel.

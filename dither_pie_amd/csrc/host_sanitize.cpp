@@ -925,10 +925,75 @@ static int run_okfit(const char *path, const int n_cases)
     return 0;
 }
 
+// ---- filtered resize: the coefficient tables, the plan and the host statement ------------------------------------------------
+// resamplecoeffs record: in, out, filter (int32)
+static int run_resamplecoeffs(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[3];
+        if (fread(head, sizeof(int32_t), 3, f) != 3 || head[0] < 1 || head[1] < 1 || head[0] > kResampleMaxSize || head[1] > kResampleMaxSize ||
+            head[2] < 0 || head[2] >= kResampleFilters) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        std::vector<int32_t> bounds, kk;
+        const int ksize = resample_coeffs(head[0], head[1], head[2], bounds, kk);
+        printf("coeffs %d %d", c, ksize);
+        for (const int32_t v : bounds) printf(" %d", v);
+        for (const int32_t v : kk) printf(" %d", v);
+        printf("\n");
+    }
+    fclose(f);
+    return 0;
+}
+
+// resample record: filter, n, h, w, oh, ow (int32), then n * h * w * 3 bytes; the output bytes of the accepted cases go to out_path
+// back to back
+static int run_resample(const char *path, const int n_cases, const char *out_path)
+{
+    FILE *f = fopen(path, "rb");
+    FILE *g = fopen(out_path, "wb");
+    if (!f || !g) {
+        fprintf(stderr, "cannot open %s or %s\n", path, out_path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[6];
+        if (fread(head, sizeof(int32_t), 6, f) != 6 || head[1] < 0 || head[1] > 64) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        ResamplePlanHost p;
+        const int rule = resample_plan(head[0], head[2], head[3], head[4], head[5], p);
+        printf("resample %d %d", c, rule);
+        if (!rule) {
+            const size_t nin = (size_t)head[1] * 3u * (size_t)p.h * (size_t)p.w, nout = (size_t)head[1] * 3u * (size_t)p.oh * (size_t)p.ow;
+            std::vector<uint8_t> in(nin), out(nout);   // exactly what the statement reads and writes
+            if (fread(in.data(), 1, nin, f) != nin) {
+                fprintf(stderr, "bad record %d in %s\n", c, path);
+                return 2;
+            }
+            resample_host(p, in.data(), out.data(), head[1]);
+            if (fwrite(out.data(), 1, nout, g) != nout) return 2;
+            printf(" %d %d %d %d %d %d %lld %lld", p.y0, p.y1, p.need_h ? 1 : 0, p.need_v ? 1 : 0, p.mul32 ? 1 : 0, p.h_kernel,
+                   (long long)std::max(p.ver.max_abs, p.hor.max_abs), (long long)std::max(p.need_v ? p.ver.max_sum : 0, p.hor.max_sum));
+        }
+        printf("\n");
+    }
+    fclose(f);
+    fclose(g);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -945,6 +1010,8 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finekeys") return run_finekeys(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "resample") return argc > 4 ? run_resample(argv[2], atoi(argv[3]), argv[4]) : 2;
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

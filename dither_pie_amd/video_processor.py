@@ -55,13 +55,29 @@ class NeuralPixelizer:
         raise NotImplementedError("neural pixelization is outside the MI355X backend's scope")
 
 
-def pixelize_regular(image: Image.Image, max_size: int) -> Image.Image:
-    """NEAREST down-scale to even dimensions (video_processor.py:563-577), on the GPU."""
-    import torch
+def _downscale_filter(name) -> str:
+    """The `resample` / `downscale_filter` keyword: ValueError (listing the accepted names) for anything else."""
     from . import backend
+    return backend._resample_filter(name)
+
+
+def _downscale(x, th: int, tw: int, downscale_filter: str):
+    """The pixelization down-scale of frames in HBM: NEAREST as in the reference, or one of Pillow's averaging filters
+    (backend.resample: bit-identical to Image.resize)."""
+    from . import backend
+    if downscale_filter == "nearest":
+        return backend.resize_nearest(x, th, tw)
+    return backend.resample(x, th, tw, downscale_filter)
+
+
+def pixelize_regular(image: Image.Image, max_size: int, resample: str = "nearest") -> Image.Image:
+    """Down-scale to even dimensions (video_processor.py:563-577), on the GPU: NEAREST as in the reference, or with
+    resample = "box", "bilinear", "hamming", "bicubic" or "lanczos" what image.resize gives with that filter."""
+    import torch
+    resample = _downscale_filter(resample)
     tw, th = _even_dimensions(image.size[0], image.size[1], max_size)
     arr = np.array(image.convert("RGB"), dtype=np.uint8)
-    out = backend.resize_nearest(torch.from_numpy(arr).cuda(), th, tw)
+    out = _downscale(torch.from_numpy(arr).cuda(), th, tw, resample)
     return Image.fromarray(out.cpu().numpy(), "RGB")
 
 
@@ -92,16 +108,19 @@ def _apply_final_resize_to_frame(image: Image.Image, multiplier: int) -> Image.I
 
 
 def process_frames(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
-                   final_resize_multiplier: Optional[int] = None):
+                   final_resize_multiplier: Optional[int] = None, downscale_filter: str = "nearest"):
     """The per-frame pipeline of _process_single_frame (video_processor.py:423-475) for a batch of
-    equally sized frames resident in HBM: uint8 CUDA tensor [N,H,W,3] -> uint8 CUDA tensor [N,H',W',3]."""
+    equally sized frames resident in HBM: uint8 CUDA tensor [N,H,W,3] -> uint8 CUDA tensor [N,H',W',3].
+    downscale_filter: the filter of the pixelization down-scale ("nearest": the reference's; "box" ... "lanczos": Pillow's
+    averaging filters, backend.resample).  The final up-scale stays NEAREST: a pixel-art enlargement must not blur."""
     from . import backend
+    downscale_filter = _downscale_filter(downscale_filter)
     if pixelize_method in (PixelizeMethod.NEURAL.value, "neural"):
         raise NotImplementedError("neural pixelization is outside the MI355X backend's scope")
     x = frames
     if pixelize_method in (PixelizeMethod.REGULAR.value, "regular"):
         tw, th = _even_dimensions(x.shape[2], x.shape[1], max_size)
-        x = backend.resize_nearest(x, th, tw)
+        x = _downscale(x, th, tw, downscale_filter)
     x = ditherer.apply_dithering_frames(x)
     if final_resize_multiplier:
         nw, nh = _final_size(x.shape[2], x.shape[1], final_resize_multiplier)
@@ -110,17 +129,18 @@ def process_frames(frames, ditherer: ImageDitherer, pixelize_method: Optional[st
 
 
 def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
-                           final_resize_multiplier: Optional[int] = None):
+                           final_resize_multiplier: Optional[int] = None, downscale_filter: str = "nearest"):
     """process_frames() as palette-index planes: uint8 CUDA tensor [N,H,W,3] -> (planes [N,H',W'], palette_u8 [K,3]) with
     palette_u8[planes] == process_frames(...).  The final up-scale runs on the index plane (the same NEAREST coordinates),
-    so the index pass looks up the small frames only."""
+    so the index pass looks up the small frames only.  downscale_filter: as for process_frames."""
     from . import backend
+    downscale_filter = _downscale_filter(downscale_filter)
     if pixelize_method in (PixelizeMethod.NEURAL.value, "neural"):
         raise NotImplementedError("neural pixelization is outside the MI355X backend's scope")
     x = frames
     if pixelize_method in (PixelizeMethod.REGULAR.value, "regular"):
         tw, th = _even_dimensions(x.shape[2], x.shape[1], max_size)
-        x = backend.resize_nearest(x, th, tw)
+        x = _downscale(x, th, tw, downscale_filter)
     planes, colours = ditherer.apply_dithering_frames_indexed(x)
     if final_resize_multiplier:
         nw, nh = _final_size(planes.shape[2], planes.shape[1], final_resize_multiplier)
@@ -130,18 +150,18 @@ def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Opt
 
 def process_frames_png(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
                        final_resize_multiplier: Optional[int] = None, seg_bytes: Optional[int] = None, blocks: str = "fixed",
-                       assemble: str = "host"):
+                       assemble: str = "host", downscale_filter: str = "nearest"):
     """process_frames() as PNG-8 files: uint8 CUDA tensor [N,H,W,3] -> [bytes of one PNG file per frame]; decoding file i
     gives process_frames(...)[i], exactly.  process_frames_indexed, then png.encode_png: the planes are compressed on the
     device and only the compressed streams come back (assemble="device": the finished files, png.encode_png).  ValueError above
     256 colours."""
     from . import png
-    planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier)
+    planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
     return png.encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)
 
 
 def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_method: Optional[str] = None,
-                          max_size: int = 64, final_resize_multiplier: Optional[int] = None) -> bool:
+                          max_size: int = 64, final_resize_multiplier: Optional[int] = None, downscale_filter: str = "nearest") -> bool:
     """One PNG in place; True on success, False (with a message on stderr) on any error
     (video_processor.py:423-475)."""
     try:
@@ -149,7 +169,7 @@ def _process_single_frame(frame_path: Path, ditherer: ImageDitherer, pixelize_me
         frame_path = Path(frame_path)
         arr = np.array(Image.open(frame_path).convert("RGB"), dtype=np.uint8)
         out = process_frames(torch.from_numpy(arr).cuda().unsqueeze(0), ditherer, pixelize_method, max_size,
-                             final_resize_multiplier)
+                             final_resize_multiplier, downscale_filter)
         Image.fromarray(out[0].cpu().numpy(), "RGB").save(frame_path)
         if not frame_path.exists() or frame_path.stat().st_size == 0:
             raise ValueError(f"Frame {frame_path} not saved properly")
@@ -314,7 +334,7 @@ class VideoProcessor:
             self._probe_ok = False
             return {"fps": 30.0, "width": 1920, "height": 1080, "duration": None, "frame_count": None}
 
-    def _process_batch(self, files, ditherer, pixelize_method, max_size, final_resize_multiplier):
+    def _process_batch(self, files, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter="nearest"):
         """One batch of PNG files through the GPU; returns the list of files that failed."""
         import torch
         try:
@@ -322,7 +342,7 @@ class VideoProcessor:
             if len({a.shape for a in arrs}) != 1:
                 raise ValueError("frames of one batch differ in size")
             out = process_frames(torch.from_numpy(np.stack(arrs)).cuda(), ditherer, pixelize_method, max_size,
-                                 final_resize_multiplier).cpu().numpy()
+                                 final_resize_multiplier, downscale_filter).cpu().numpy()
             for f, o in zip(files, out):
                 Image.fromarray(o, "RGB").save(f)
                 if not f.exists() or f.stat().st_size == 0:
@@ -332,7 +352,7 @@ class VideoProcessor:
             print(f"Batch failed ({e}); retrying frame by frame", file=sys.stderr)
         failed = []
         for f in files:
-            if not any(_process_single_frame(f, ditherer, pixelize_method, max_size, final_resize_multiplier)
+            if not any(_process_single_frame(f, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
                        for _ in range(3)):
                 failed.append(f)
         return failed
@@ -686,7 +706,7 @@ class VideoProcessor:
         return scenes
 
     def process_video_gif(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                          scene_palettes=None, delta=True, max_frames=None, chunk_px=None) -> int:
+                          scene_palettes=None, delta=True, max_frames=None, chunk_px=None, downscale_filter="nearest") -> int:
         """The video as an animated GIF of palette indices (gif.GifWriter): decode -> GPU -> file, no encoder pipe and no RGB
         frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded: the same decoder
         line, reader thread and rotating pinned slots).  Per batch: process_frames_indexed -- piece by piece with each
@@ -703,6 +723,7 @@ class VideoProcessor:
         of more than 256 colours where that is known up front, max_frames or chunk_px < 1."""
         import copy
         from .gif import GIF_MAX_COLOURS, GifWriter
+        downscale_filter = _downscale_filter(downscale_filter)   # (the filter of the pixelization down-scale, as for process_frames)
         if self.devices is not None and len(list(self.devices)) > 1:
             raise ValueError(f"process_video_gif runs on one device, not on {len(list(self.devices))}: a GIF's frames are "
                              "written in order by one writer; pass devices=[one]")
@@ -743,7 +764,7 @@ class VideoProcessor:
                 try:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
-                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
                         writer.add(planes, colours, delta)
                 except Exception as e:  # noqa: BLE001
                     raise _BatchFailed(e) from e
@@ -763,7 +784,7 @@ class VideoProcessor:
         return made["writer"].n_frames
 
     def process_video_apng(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                           delta=True, max_frames=None, seg_bytes=None, blocks="fixed") -> int:
+                           delta=True, max_frames=None, seg_bytes=None, blocks="fixed", downscale_filter="nearest") -> int:
         """The video as an animated PNG of palette indices (apng.ApngWriter): decode -> GPU -> file, no encoder pipe and no
         RGB frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as
         process_video_gif is.  Per batch: process_frames_indexed, the inter-frame delta, the zlib streams, the chunk CRCs and
@@ -780,6 +801,7 @@ class VideoProcessor:
         colours where that is known up front, max_frames < 1, seg_bytes outside 256 ... 32768, a `blocks` that does not
         exist."""
         from .apng import APNG_MAX_COLOURS, ApngWriter
+        downscale_filter = _downscale_filter(downscale_filter)   # (the filter of the pixelization down-scale, as for process_frames)
         if self.devices is not None and len(list(self.devices)) > 1:
             raise ValueError(f"process_video_apng runs on one device, not on {len(list(self.devices))}: an APNG's frames are "
                              "written in order by one writer; pass devices=[one]")
@@ -806,7 +828,7 @@ class VideoProcessor:
 
             def feed(x, first):
                 try:
-                    planes, colours = process_frames_indexed(x, ditherer, pixelize_method, max_size, final_resize_multiplier)
+                    planes, colours = process_frames_indexed(x, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
                     writer.add(planes, colours)
                 except Exception as e:  # noqa: BLE001
                     raise _BatchFailed(e) from e
@@ -826,7 +848,8 @@ class VideoProcessor:
         return made["writer"].n_frames
 
     def process_video_pngs(self, input_path, out_pattern, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1, blocks="fixed", assemble="host") -> int:
+                           scene_palettes=None, max_frames=None, seg_bytes=None, start=1, blocks="fixed", assemble="host",
+                           downscale_filter="nearest") -> int:
         """The video as a sequence of PNG-8 files out_pattern % start, out_pattern % (start + 1), ... (the 'frame_%05d.png'
         of a frame directory): decode -> GPU -> files, no encoder pipe and no RGB frames on the way out.  Built on the
         decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as process_video_gif is.  Per batch:
@@ -842,6 +865,7 @@ class VideoProcessor:
         pattern that does not format an integer."""
         import copy
         from .png import PNG_MAX_COLOURS, encode_png
+        downscale_filter = _downscale_filter(downscale_filter)   # (the filter of the pixelization down-scale, as for process_frames)
         if self.devices is not None and len(list(self.devices)) > 1:
             raise ValueError(f"process_video_pngs runs on one device, not on {len(list(self.devices))}: the files are "
                              "numbered in order by one writer; pass devices=[one]")
@@ -888,7 +912,7 @@ class VideoProcessor:
                 try:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
-                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier)
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
                         for k, data in enumerate(encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)):
                             with open(str(out_pattern) % (int(start) + first + a + k), "wb") as f:
                                 f.write(data)
@@ -907,8 +931,10 @@ class VideoProcessor:
         return made["written"]
 
     def _stream_through_pipes(self, input_path, output_path, ditherer, method, max_size, batch_size,
-                              final_resize_multiplier, info, run=None, overlap=True, scene_palettes=None) -> int:
+                              final_resize_multiplier, info, run=None, overlap=True, scene_palettes=None,
+                              downscale_filter="nearest") -> int:
         """decode -> GPU -> encode through two ffmpeg rawvideo pipes; returns the number of frames written.
+        downscale_filter: the filter of the pixelization down-scale, as for process_frames.
         Failure policy as in the reference: a batch that fails is retried frame by frame, a frame that still fails is
         replaced by the nearest good output frame (the previous one first, video_processor.py:53-96) and the video goes
         on; the call fails only when ffmpeg does or when no frame at all could be processed.  `run` (tests): the batch
@@ -931,6 +957,7 @@ class VideoProcessor:
         ValueError before the decoder starts: scenes.check_scene_palettes, or a `run` of the caller's beside the list."""
         import time
         import torch
+        downscale_filter = _downscale_filter(downscale_filter)
         scene_run = scene_palettes is not None
         if scene_run:
             import copy
@@ -974,16 +1001,16 @@ class VideoProcessor:
                     from . import sharding
                     out = target["out"]
                     return sharding.process_on_devices(
-                        x, lambda y: process_frames(y, ditherer, method, max_size, final_resize_multiplier), devs,
+                        x, lambda y: process_frames(y, ditherer, method, max_size, final_resize_multiplier, downscale_filter), devs,
                         out=None if out is None else out[:x.shape[0]])
                 with torch.cuda.device(devs[0]):
                     if gpu_stream is not None:
                         with torch.cuda.stream(gpu_stream):
-                            return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier)
-                    return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier)
+                            return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier, downscale_filter)
+                    return process_frames(x.cuda(non_blocking=True), ditherer, method, max_size, final_resize_multiplier, downscale_filter)
 
             def one_palette(y, d):
-                return process_frames(y, d, method, max_size, final_resize_multiplier)
+                return process_frames(y, d, method, max_size, final_resize_multiplier, downscale_filter)
 
             def run_scenes(x, first=0):   # the same, piece by piece with the palette of the piece's scene
                 n = x.shape[0]
@@ -1309,12 +1336,15 @@ class VideoProcessor:
     def process_video_streaming(self, input_path: str, output_path: str, ditherer: ImageDitherer,
                                 pixelize_func=None, batch_size: int = 15,
                                 final_resize_multiplier: Optional[int] = None, use_pipes: bool = True,
-                                scene_palettes=None) -> bool:
+                                scene_palettes=None, downscale_filter: str = "nearest") -> bool:
         """video_processor.py:172-390; pixelize_func is the reference's tuple (method_str, max_size) or None.
+        downscale_filter (an addition): the filter of the pixelization down-scale, as for process_frames; ValueError for an
+        unknown name before anything is started.
         use_pipes (an addition): rawvideo pipes instead of the reference's PNG files on disk.
         scene_palettes (an addition; pipes path only): the list scan_scenes returns -- the palette switches at the scene
         boundaries (_stream_through_pipes).  None: one palette, the ditherer's, as ever.  ValueError, before anything is
         started: an empty list, overlapping scenes, a scene whose palette is None, use_pipes=False."""
+        downscale_filter = _downscale_filter(downscale_filter)
         if scene_palettes is not None:
             from .scenes import check_scene_palettes
             if not use_pipes:
@@ -1339,7 +1369,7 @@ class VideoProcessor:
                 self._report_progress(0.1, "Processing frames...")
                 self._stream_through_pipes(input_path, output_path, ditherer, method, max_size, max(1, batch_size),
                                            final_resize_multiplier, info,   # reports 0.9 before it waits for the encoder
-                                           scene_palettes=scene_palettes)
+                                           scene_palettes=scene_palettes, downscale_filter=downscale_filter)
                 self._report_progress(1.0, "Video processing complete!")
                 return True
             except Exception as e:  # noqa: BLE001
@@ -1365,7 +1395,7 @@ class VideoProcessor:
                 failed, done = [], 0
                 for lo in range(0, total, batch_size):
                     batch = frames[lo:lo + batch_size]
-                    failed += self._process_batch(batch, ditherer, method, max_size, final_resize_multiplier)
+                    failed += self._process_batch(batch, ditherer, method, max_size, final_resize_multiplier, downscale_filter)
                     done += len(batch)
                     self._report_progress(0.1 + 0.8 * (done / total), f"Processed {done}/{total} frames")
                 if failed:
