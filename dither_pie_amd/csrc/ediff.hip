@@ -8,18 +8,10 @@
 // order inside a row), which reproduces the same float32 sums bit for bit.  The taps arrive
 // pre-sorted in that order (dy descending, dx descending) from the launcher.
 //
-// ed_wavefront_kernel (serpentine off): one workgroup per frame, up to 16 waves.  A wave owns a band of
-//   64 image rows (lane = row) and walks it on the anti-diagonal schedule: lane L works on
-//   x = t - skew*L at step t, so every source pixel of a row above was finished `skew` steps
-//   earlier.  Bands of one frame are pipelined across the waves of the workgroup: band b+1 behaves
-//   like "lanes 64.." of band b, trailing it by 63*skew+3 steps; it spins on a progress word in LDS
-//   that the producing wave publishes after its stores are acknowledged.  Nothing on the dependency
-//   chain touches global memory: all global traffic happens at 16-step period boundaries -- each lane
-//   fetches the 48 bytes of its next 16 pixels one full period ahead (unaligned dword loads), flushes
-//   the 48 output bytes of the finished period, rows 62/63 flush their staged errors to a global row
-//   buffer (L2) and lanes prefetch the previous band's two boundary rows into a 64-column LDS ring --
-//   so every wait is for operations issued a period earlier.  Errors of the band's own rows live in an
-//   8-deep per-row LDS ring.
+// ed_wavefront_kernel (serpentine off): one workgroup per frame, up to 16 waves, on the banded wavefront
+//   schedule of ed_band.hip.h: a wave owns a band of 64 image rows (lane = row) and walks it on the
+//   anti-diagonal, the bands of a frame are pipelined across the waves through progress words, and all
+//   global traffic happens at period boundaries, a period ahead of its use.
 // ed_rowserial_kernel (any scan, used for serpentine): rows are strictly sequential under a serpentine
 //   scan (the first pixel of row y+1 needs the last pixel of row y), so only the latency of one pixel
 //   step counts: one wave per frame, error rows in LDS, lane-parallel palette scan (see the kernel).
@@ -42,6 +34,7 @@
 #include "tree_query.hip.h"
 #include "wave_util.hip.h"
 #include "ed_nearest.hip.h"
+#include "ed_band.hip.h"
 
 namespace dp {
 namespace {
@@ -180,16 +173,12 @@ __global__ __launch_bounds__(256) void ed_cells_kernel(const PalDev pal, uint4 *
     cells[cell] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// I/O period of the wavefront kernel: all global traffic happens at period boundaries.  A band follows the one above it at the
-// dependency distance (63 * skew + 2 steps) PLUS three periods of hand-off (its boundary errors are stored at the end of their period,
-// acknowledged one period later when the stores have landed, and fetched one period before use): with 16 steps that is 48 of ~175
-// steps per band, 33 times per 4K frame -- 18 % of a lone frame.  The instances of the few-frames schedule (<= 4 waves, every wave
-// with a SIMD to itself: their time IS that chain) therefore run 8-step periods; the sixteen-wave instances, bound by the
-// instructions they issue, keep 16 (half as many period boundaries per step).
+// I/O period of the wavefront kernel (ed_band.hip.h).  The three periods of hand-off between a band and the one above it are, with
+// 16 steps, 48 of ~175 steps per band, 33 times per 4K frame -- 18 % of a lone frame.  The instances of the few-frames schedule
+// (<= 4 waves, every wave with a SIMD to itself: their time IS that chain) therefore run 8-step periods; the sixteen-wave instances,
+// bound by the instructions they issue, keep 16 (half as many period boundaries per step).
 constexpr int kPeriod = 16;
 constexpr int kPeriodFew = 8;
-// progress words per frame when a frame's bands are spread over several workgroups (the last one: give-up flag)
-constexpr int kEdProgWords = 64;
 
 // NT: tap slots compiled in (taps.n <= NT); EXACT: taps.n == NT, the slots carry no test (the reference's eight tap sets
 // have 3, 4, 6, 7, 10 or 12 taps), so all LDS reads of a step's taps are in flight together
@@ -212,21 +201,19 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
     typedef typename ErrT<NB>::type E;  // an error: float, or double with the numba arithmetic
     constexpr int PERIOD = MAXW <= 4 ? kPeriodFew : kPeriod;   // steps per I/O period (a multiple of 4)
     constexpr int PW = PERIOD * 3 / 4;                          // dwords of a period's pixels
-    static_assert(PERIOD % 4 == 0 && PERIOD >= 4 && PERIOD <= 16, "the boundary fetch covers 32 columns per period");
     E *__restrict__ bnd_all = reinterpret_cast<E *>(bnd_all_v);
     // G == 1 with progress words given: the REPAIR launch that follows a G > 1 launch on the stream -- only the frames
     // whose give-up flag is set are done again, one workgroup per frame (the others return at once).
     if (G == 1 && gprog_all != nullptr &&
-        __hip_atomic_load(&gprog_all[(size_t)blockIdx.x * kEdProgWords + kEdProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+        __hip_atomic_load(&gprog_all[(size_t)blockIdx.x * kBandProgWords + kBandProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
         return;
     if (G != 1 && test_giveup) {  // tests: every workgroup gives up before it has written a pixel
         if (threadIdx.x == 0)
-            __hip_atomic_store(&gprog_all[(size_t)(blockIdx.x / (unsigned)G) * kEdProgWords + kEdProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&gprog_all[(size_t)(blockIdx.x / (unsigned)G) * kBandProgWords + kBandProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    // G > 1: a frame's bands are spread over G workgroups (few frames in flight: more CUs per frame, fewer waves per
-    // CU).  Waves of different workgroups then meet through progress words in global memory instead of s_prog, and the
-    // boundary rows are written with agent-scope stores (the workgroups may sit on different XCDs, i.e. L2s).
+    // G > 1: a frame's bands are spread over G workgroups (few frames in flight: more CUs per frame, fewer waves per CU).  Waves of
+    // different workgroups meet through progress words in global memory (ed_band.hip.h) and write the boundary rows with agent-scope stores.
     // errors of the band's own rows (last 8 columns).  A row's ring is padded to 27 words: at step t lane L reads (and
     // writes) slot (t - skew*L - dx) & 7 of a row, so with the natural stride of 24 words the lanes L, L+8, L+16, ... --
     // eight of them -- meet in one LDS bank on every ring access (SQ_LDS_BANK_CONFLICT: 72 % of the LDS cycles, the LDS
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
     __shared__ float4 s_pal[DP_MAX_COLORS + 16];
     uint32_t *s_coarse = reinterpret_cast<uint32_t *>(s_pal + 16);
     __shared__ E s_zero[4];                              // the "error" of pixels that do not exist
-    typedef const __attribute__((address_space(3))) E lds_float_t;
+    typedef band_lds_t<E> lds_float_t;
     const int L = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const int NW = blockDim.x >> 6;
@@ -255,7 +242,9 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
     const int gw = (int)(blockIdx.x % (unsigned)G) * NW + wv;  // this wave's number among them
     for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lut[i] = pal.lut_in ? pal.lut_in[i] : (uint8_t)i;
     for (int i = threadIdx.x; i < pal.K; i += blockDim.x) s_pal[i] = pal.fcand[i];
-    constexpr bool kSmall = PALS != 2, kLarge = PALS != 1;   // code for palettes of <= 16 / > 16 colours
+    // code for palettes of <= 16 / > 16 colours.  NB instances take j from nearest_numba_f64(s_pal, pal.K, ...) in the step below and
+    // never read lists16 / h4, so they have no tables of larger palettes (and s_lists16 has one element there)
+    constexpr bool kSmall = PALS != 2, kLarge = PALS != 1 && !NB;
     if (kSmall && pal.ed_coarse)
         for (int i = threadIdx.x; i < 4096; i += blockDim.x) s_coarse[i] = pal.ed_coarse[i];
     const uint32_t *coarse = (kSmall && pal.ed_coarse) ? s_coarse : nullptr;
@@ -267,6 +256,8 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
         s_expanded[threadIdx.x] = make_float4(-2.0f * c.x, -2.0f * c.y, -2.0f * c.z, (float)n2);
     }
     __shared__ uint4 s_lists16[(MAXW <= 4 && kLarge) ? kEdH4LdsWords / 4 : 1];   // the 16^3 lists (64 KB) or the hierarchical table (<= 108 KB)
+    static_assert(sizeof(s_ring) + sizeof(s_vring) + sizeof(s_bout) + sizeof(s_lut) + sizeof(s_prog) + sizeof(s_pal) + sizeof(s_zero) +
+                      sizeof(s_expanded) + sizeof(s_lists16) <= 160 * 1024, "the static LDS of this instance exceeds a CU's 160 KiB");
     const uint4 *lists16 = nullptr;
     const uint32_t *h4 = nullptr;
     if (!kLarge) {
@@ -303,7 +294,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
         const uint8_t *fin = in + f * (size_t)h * w * 3;
         uint8_t *fout = out + f * (size_t)h * w * 3;
         E *bnd = bnd_all + f * (size_t)4 * w * 3;  // [2 buffers][2 rows][w][3]
-        uint32_t *gprog = gprog_all + f * (size_t)kEdProgWords;   // [NWT] progress words + [kEdProgWords-1] give-up flag
+        uint32_t *gprog = gprog_all + f * (size_t)kBandProgWords;   // [NWT] progress words + [kBandProgWords-1] give-up flag
         const int r = band * 64 + L;
         const E *bprev = bnd + (size_t)((band + 1) & 1) * 2 * w * 3;  // written by band-1
         E *bnext = bnd + (size_t)(band & 1) * 2 * w * 3;
@@ -313,18 +304,14 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
         const bool row_ok = r < h;
         const long row_byte = (long)r * w * 3;
 
-        // Where each tap of this lane's row finds its source row: the ring of a row of the band (8 columns), the ring of
-        // the two rows above the band (64 columns), or -- the row does not exist (top of the image) -- the zero slot.
-        // Adding a zero error is exact, so the step needs no row test and one column test per tap.
+        // where each tap of this lane's row finds its source row (band_tap_source)
         lds_float_t *tbase[NT];
         uint32_t tmask[NT];
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
             const int rel = L - taps.dy[k];
-            const bool exists = (EXACT || k < taps.n) && r - taps.dy[k] >= 0;
             const E *row = rel >= 0 ? &s_ring[wv][rel & 63][0] : &s_vring[wv][(rel + 2) & 1][0][0];
-            tbase[k] = exists ? (lds_float_t *)row : (lds_float_t *)s_zero;
-            tmask[k] = exists ? (rel >= 0 ? (uint32_t)(kRing - 1) : 63u) : 0u;
+            band_tap_source<E>((EXACT || k < taps.n) && r - taps.dy[k] >= 0, rel, row, s_zero, kRing, tbase[k], tmask[k]);
         }
         uint32_t pix[PW], cur[PW + 1], outb[PW + 1];  // a period's pixels in flight / being consumed / being produced (raw bytes)
         E pb0 = 0, pb1 = 0, pb2 = 0;  // boundary errors in flight (one column per lane)
@@ -338,14 +325,8 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
         for (int t0 = -PERIOD; t0 < steps + PERIOD; t0 += PERIOD) {
             // ================= period boundary: everything issued one period ago has landed =================
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (L == 0) {
-                // boundary columns produced in steps < t0 - PERIOD are acknowledged
-                int ack = t0 - PERIOD - 63 * skew + 1024;
-                ack = ack < 0 ? 0 : ack;
-                const uint32_t word = ((uint32_t)gb << 16) | (uint32_t)ack;
-                if (G == 1) s_prog[wv] = word;
-                else __hip_atomic_store(&gprog[gw], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            // boundary columns produced in steps < t0 - PERIOD are acknowledged
+            if (L == 0) band_publish(G, &s_prog[wv], &gprog[gw], gb, t0 - PERIOD, skew);
             // park the boundary errors fetched during the previous period
             if (pb_valid) {
                 E *dst = &s_vring[wv][L >> 5][pb_col & 63][0];
@@ -355,33 +336,11 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
             }
             // ---- flush the outputs of the period that just ended: columns [xs, xs+PERIOD) of row r
             {
-                const int xs = (t0 - PERIOD) - skew * L;
-                const int lo = xs < 0 ? 0 : xs, hi = xs + PERIOD > w ? w : xs + PERIOD;
-                if (row_ok && hi > lo) {
-                    const long B = row_byte + (long)xs * 3;
-                    if (lo == xs && hi == xs + PERIOD) {
-#pragma unroll
-                        for (int k = 0; k < PW; ++k) *reinterpret_cast<uint32_t *>(fout + B + 4 * k) = outb[k];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < PERIOD; ++i) {
-                            if (xs + i >= 0 && xs + i < w) {
-                                const int bo = 3 * i;
-                                const uint32_t c = __funnelshift_r(outb[bo >> 2], outb[(bo >> 2) + 1], (bo & 3) * 8);
-                                uint8_t *o = fout + B + bo;
-                                o[0] = (uint8_t)c;
-                                o[1] = (uint8_t)(c >> 8);
-                                o[2] = (uint8_t)(c >> 16);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < PW + 1; ++k) outb[k] = 0;
+                const BandCols c = band_flush<PERIOD>(fout, r, w, (t0 - PERIOD) - skew * L, row_ok, outb);
                 // rows 62/63: this band's boundary errors of the same period go to the global row buffer
-                if (L >= 62 && row_ok && hi > lo) {
-                    for (int i = lo - xs; i < hi - xs; ++i) {
-                        E *b = bnext + ((size_t)(L - 62) * w + (xs + i)) * 3;
+                if (L >= 62 && row_ok && c.hi > c.lo) {
+                    for (int i = c.lo - c.xs; i < c.hi - c.xs; ++i) {
+                        E *b = bnext + ((size_t)(L - 62) * w + (c.xs + i)) * 3;
                         if (G == 1) {
                             b[0] = s_bout[wv][L - 62][i][0];
                             b[1] = s_bout[wv][L - 62][i][1];
@@ -418,15 +377,12 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
                     }
                 }
             }
-            // ---- boundary rows of the band above: the 32 columns that end two past lane 0's next period, [x0n+PERIOD+2-32, x0n+PERIOD+2)
+            // ---- boundary rows of the band above (BandWindow)
             pb_valid = false;
             if (band > 0) {
-                const int x0n = t0 + PERIOD;       // lane 0's first column of the next period (wave-uniform)
-                constexpr int kFirst = PERIOD + 2 - 32;   // (-14 with 16 steps: lane 1's taps reach back skew + 2 columns)
-                int need = x0n + PERIOD + 2;       // one past the last column fetched
-                need = need > w ? w : need;
-                if (x0n + kFirst < w && need > 0) {
-                    const uint32_t want = (uint32_t)(need + 1024);
+                const BandWindow<PERIOD> win(t0, w);
+                if (win.first() < w && win.need > 0) {
+                    const uint32_t want = (uint32_t)(win.need + 1024);
                     for (uint32_t spins = 0;; ++spins) {
                         const uint32_t v = G == 1 ? s_prog[pw] : __hip_atomic_load(&gprog[pw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((int)(v >> 16) > gb - 1 || ((int)(v >> 16) == gb - 1 && (v & 0xffffu) >= want)) break;
@@ -434,15 +390,14 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
                         // across workgroups the producer is another workgroup of the grid: never wait for it forever
                         // (a give-up flag stays in the workspace; the launch ends instead of hanging)
                         if (G != 1 && (spins > (1u << 24) || (spins % 1024u == 1023u &&
-                                                               __hip_atomic_load(&gprog[kEdProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))) {
-                            if (L == 0) __hip_atomic_store(&gprog[kEdProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                                               __hip_atomic_load(&gprog[kBandProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))) {
+                            if (L == 0) __hip_atomic_store(&gprog[kBandProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             return;
                         }
                     }
-                    const int col = x0n + kFirst + (L & 31);
+                    const int col = win.col(L);
                     if (col >= 0 && col < w) {
-                        // lanes 0..31 -> row -2 (lane 62 of band-1), lanes 32..63 -> row -1 (lane 63); the buffer was
-                        // written by another wave of this workgroup and is reused every 2 bands: bypass L1
+                        // the buffer was written by another wave (of this workgroup or another) and is reused every 2 bands: bypass L1
                         const E *b = bprev + ((size_t)(L >> 5) * w + col) * 3;
                         pb0 = __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         pb1 = __hip_atomic_load(b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -459,10 +414,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
 
-            // ================= PERIOD steps that touch LDS and registers only =================
-            // Four steps per round of the loop: the round's pixels are bytes 0..11 of cur[] and its colours become the LAST twelve
-            // bytes of outb[] at fixed positions, then both buffers move down by three whole registers -- a per-step rotation by
-            // three bytes costs 24 funnel shifts per step.
+            // ================= PERIOD steps that touch LDS and registers only, four per round (band_pixel, band_advance) =================
             for (int i4 = 0; i4 < PERIOD; i4 += 4) {
               uint32_t cb[4];
 #pragma unroll
@@ -474,9 +426,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
                 E e0 = 0, e1 = 0, e2 = 0;
                 uint32_t cbytes = 0;
                 if (act) {
-                    // this step's pixel: bytes 3q..3q+2 of the round's twelve
-                    const uint32_t pxv = q == 0 ? cur[0] : (q == 1 ? __funnelshift_r(cur[0], cur[1], 24)
-                                                               : (q == 2 ? __funnelshift_r(cur[1], cur[2], 16) : (cur[2] >> 8)));
+                    const uint32_t pxv = band_pixel(cur, q);
                     float a0, a1, a2;
                     if (pal.lut_in) {
                         a0 = (float)s_lut[pxv & 255u];
@@ -549,8 +499,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
                 // the row two below reads in this very step for a dx=+2 tap)
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                // columns -2, -1, w and w+1 are written too, with zero errors (e is 0 without a pixel): a tap that reaches
-                // past either end of a row reads them instead of testing its column
+                // columns -2, -1, w and w+1 are written too, with zero errors (e is 0 without a pixel): see band_tap_source
                 if (row_ok && x >= -2 && x < w + 2) {
                     E *slot = &s_ring[wv][L][(x & (kRing - 1)) * 3];
                     slot[0] = e0;
@@ -565,17 +514,7 @@ __global__ __launch_bounds__(64 * MAXW) void ed_wavefront_kernel(const uint8_t *
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
               }
-              // the round's twelve bytes are consumed / produced: both buffers move down by three registers; the colour of
-              // step i will have travelled to byte 3*i by the time the period is flushed
-#pragma unroll
-              for (int k = 0; k < PW - 3; ++k) {
-                  cur[k] = cur[k + 3];
-                  outb[k] = outb[k + 3];
-              }
-              cur[PW - 3] = cur[PW - 2] = cur[PW - 1] = 0u;
-              outb[PW - 3] = cb[0] | (cb[1] << 24);
-              outb[PW - 2] = (cb[1] >> 8) | (cb[2] << 16);
-              outb[PW - 1] = (cb[2] >> 16) | (cb[3] << 8);
+              band_advance<PERIOD>(cur, outb, cb);
             }
         }
         // band finished: once its boundary stores are acknowledged the next band may read any column
@@ -1026,7 +965,7 @@ int launch_error_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames, in
         uint32_t *gprog = nullptr;
         {
             const size_t prog_off = ((size_t)n_frames * (size_t)w * (numba ? 96 : 48) + 255) & ~(size_t)255;
-            const size_t prog_bytes = (size_t)n_frames * kEdProgWords * sizeof(uint32_t);
+            const size_t prog_bytes = (size_t)n_frames * kBandProgWords * sizeof(uint32_t);
             if (n_frames * 2 <= cus && n_bands >= 4 && w >= 64 && prog_off + prog_bytes <= ws_bytes && !exp_env("DP_ED_ONE_WG")) {
                 const int nwt = n_bands < 32 ? n_bands : 32;
                 while (G * 2 <= 16 && n_frames * (G * 2) <= cus && G * 2 <= nwt) G *= 2;

@@ -1,20 +1,15 @@
 // Integer error diffusion (include/ditherpie_hip_idiff.h): the classical raster scans in sixteenths, the nearest colour by one
 // gather from the palette's 2^24-entry table (pattern.hip; for a metric palette the table derived from its top-2 table).
 //
-// idiff_kernel<PERIOD, NT>  the schedule of ed_wavefront_kernel's one-workgroup-per-frame path (ediff.hip), minus what the float
-//   arithmetic forced on it.  One workgroup per frame, up to 16 waves.  A wave owns a band of 64 rows (lane = row) and walks
-//   it on the anti-diagonal: lane L works on x = t - skew * L at step t, so every source pixel of a row above was finished
-//   at least one step earlier (host_logic.h: idiff_plan has the skew).  The bands of the frame go round-robin over the
-//   waves.  A wave waits only for the wave that owns the band above, through a progress word in LDS; that wave never waits
-//   for it and all waves of a workgroup are resident together, so the wait ends.  Nothing waits across workgroups.
+// idiff_kernel<PERIOD, NT>  the banded wavefront schedule of ed_band.hip.h on its one-workgroup-per-frame path, minus what the float
+//   arithmetic forced on ed_wavefront_kernel (ediff.hip).  One workgroup per frame, up to 16 waves; the bands of the frame go
+//   round-robin over the waves; host_logic.h: idiff_plan has the skew.  A wave waits only for the wave that owns the band above,
+//   through a progress word in LDS; that wave never waits for it and all waves of a workgroup are resident together, so the wait
+//   ends.  Nothing waits across workgroups.
 //   Errors: a row's last 8 columns live in a per-row ring in LDS, two words per pixel (r | g << 16, b).  A destination PULLS
-//   trunc(e * q_k / 65536) from its finished sources: integer sums, any order, no atomics.  Rows 62 / 63 of a band also
-//   stage their errors per period and flush them to the workspace (L2); the band below prefetches them a period ahead into a
-//   64-column ring in LDS.  The workspace holds two such row pairs per frame: band b + 2 overwrites what band b wrote only
-//   where band b + 1 is long past (it trails band b + 1 by more than 63 * skew columns, the prefetch looks back 14).
-//   Global traffic is off the dependency chain: each lane fetches the 3 * PERIOD bytes of its next PERIOD pixels one period
-//   ahead (unaligned dword loads that stay inside the frame), and flushes the output bytes of the finished period; every
-//   wait is for operations issued a period earlier.  The one global access on the chain is the table gather.
+//   trunc(e * q_k / 65536) from its finished sources: integer sums, any order, no atomics.  The workspace holds two pairs of
+//   boundary rows per frame: band b + 2 overwrites what band b wrote only where band b + 1 is long past (it trails band b + 1 by
+//   more than 63 * skew columns, the prefetch looks back 14).  The one global access on the dependency chain is the table gather.
 //   The progress word of a wave is band * (w + 1) + (columns of rows 62 / 63 that have landed in the workspace), w columns
 //   once the band is finished: it only grows, and band * (w + 1) <= 2^24 + 2^24 as h * w <= 2^30.
 //   Taps travel by value.  Instances with 4, 7 and 12 tap slots (the reference's sets have 3, 4, 6, 7, 10 and 12 taps; a
@@ -26,6 +21,7 @@
 #include <algorithm>
 
 #include "../../include/ditherpie_hip_idiff.h"
+#include "ed_band.hip.h"
 #include "pattern_tab.hip.h"
 
 namespace dp {
@@ -66,7 +62,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
     __shared__ uint8_t s_lut[256];
     __shared__ volatile uint32_t s_prog[kIdMaxWaves];
     __shared__ uint32_t s_zero[2];                                // the "error" of pixels of rows that do not exist
-    typedef const __attribute__((address_space(3))) uint32_t lds_u32_t;
+    typedef band_lds_t<uint32_t> lds_u32_t;
     const int L = threadIdx.x & 63, wv = threadIdx.x >> 6, NW = blockDim.x >> 6;
     for (int i = threadIdx.x; i < 256; i += blockDim.x) {
         s_c[i] = i < pd.K ? pd.c_rank[i] : 0u;
@@ -94,8 +90,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
         const bool row_ok = r < h;
         const long row_byte = (long)r * w * 3;
 
-        // Where each tap of this lane's row finds its source row: the ring of a row of the band (8 columns), the ring of the
-        // two rows above the band (64 columns), or -- the row does not exist (top of the image) -- the zero slot.
+        // where each tap of this lane's row finds its source row (band_tap_source)
         lds_u32_t *tbase[NT];
         uint32_t tmask[NT];
 #pragma unroll
@@ -103,8 +98,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
             const int dy = taps.dy[k], rel = L - dy;   // (a spare slot: dx = 1, dy = 0, q = 0)
             const bool exists = r - dy >= 0;
             const uint32_t *row = rel >= 0 ? &s_ring[wv][rel][0] : &s_vring[wv][(rel + 2) & 1][0][0];
-            tbase[k] = exists ? (lds_u32_t *)row : (lds_u32_t *)s_zero;
-            tmask[k] = exists ? (rel >= 0 ? (uint32_t)(kIdRing - 1) : 63u) : 0u;
+            band_tap_source<uint32_t>(exists, rel, row, s_zero, kIdRing, tbase[k], tmask[k]);
         }
         uint32_t pix[PW], cur[PW + 1], outb[PW + 1];   // a period's pixels in flight / being consumed / being produced
         uint64_t pb = 0;                               // boundary errors in flight (one column per lane)
@@ -131,35 +125,15 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
             }
             // ---- flush the outputs of the period that just ended: columns [xs, xs + PERIOD) of row r
             {
-                const int xs = (t0 - PERIOD) - skew * L;
-                const int lo = xs < 0 ? 0 : xs, hi = xs + PERIOD > w ? w : xs + PERIOD;
-                if (row_ok && hi > lo) {
-                    const long B = row_byte + (long)xs * 3;
-                    if (lo == xs && hi == xs + PERIOD) {
-#pragma unroll
-                        for (int k = 0; k < PW; ++k) *reinterpret_cast<uint32_t *>(fout + B + 4 * k) = outb[k];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < PERIOD; ++i) {
-                            if (xs + i >= 0 && xs + i < w) {
-                                const int bo = 3 * i;
-                                const uint32_t c = __funnelshift_r(outb[bo >> 2], outb[(bo >> 2) + 1], (bo & 3) * 8);
-                                uint8_t *o = fout + B + bo;
-                                o[0] = (uint8_t)c;
-                                o[1] = (uint8_t)(c >> 8);
-                                o[2] = (uint8_t)(c >> 16);
-                            }
-                        }
-                    }
+                const BandCols c = band_flush<PERIOD>(fout, r, w, (t0 - PERIOD) - skew * L, row_ok, outb);
+                if (row_ok && c.hi > c.lo) {
                     // rows 62 / 63: the band's boundary errors of the same period
                     if (L >= 62) {
-                        for (int i = lo - xs; i < hi - xs; ++i)
-                            bnext[(size_t)(L - 62) * (size_t)w + (size_t)(xs + i)] =
+                        for (int i = c.lo - c.xs; i < c.hi - c.xs; ++i)
+                            bnext[(size_t)(L - 62) * (size_t)w + (size_t)(c.xs + i)] =
                                 (uint64_t)s_bout[wv][L - 62][i][0] | ((uint64_t)s_bout[wv][L - 62][i][1] << 32);
                     }
                 }
-#pragma unroll
-                for (int k = 0; k < PW + 1; ++k) outb[k] = 0;
             }
             // ---- the pixels fetched during the previous period become current; fetch the next period's
 #pragma unroll
@@ -197,8 +171,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     const int col = x0n + kFirst + (L & 31);
                     if (col >= 0 && col < w) {
-                        // lanes 0..31 -> row -2 (lane 62 of band - 1), lanes 32..63 -> row -1 (lane 63); written by another wave
-                        // of this workgroup and reused every two bands: bypass L1
+                        // written by another wave of this workgroup and reused every two bands: bypass L1
                         pb = __hip_atomic_load(bprev + (size_t)(L >> 5) * (size_t)w + (size_t)col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         pb_col = col;
                         pb_valid = true;
@@ -213,8 +186,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
             __builtin_amdgcn_wave_barrier();
 
             // ================= PERIOD steps that touch LDS, registers and the table only =================
-            // Four steps per round: the round's pixels are bytes 0..11 of cur[] and its colours become the last twelve bytes of
-            // outb[], then both buffers move down by three registers (ediff.hip has the reason)
+            // four steps per round (band_pixel, band_advance)
             for (int i4 = 0; i4 < PERIOD; i4 += 4) {
                 uint32_t cb[4];
 #pragma unroll
@@ -225,8 +197,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     int e0 = 0, e1 = 0, e2 = 0;
                     uint32_t cbytes = 0;
                     if (act) {
-                        const uint32_t pxv = q == 0 ? cur[0] : (q == 1 ? __funnelshift_r(cur[0], cur[1], 24)
-                                                                   : (q == 2 ? __funnelshift_r(cur[1], cur[2], 16) : (cur[2] >> 8)));
+                        const uint32_t pxv = band_pixel(cur, q);
                         uint32_t c0 = pxv & 255u, c1 = (pxv >> 8) & 255u, c2 = (pxv >> 16) & 255u;
                         if (lut) {
                             c0 = s_lut[c0];
@@ -264,8 +235,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     // below reads in this very step when skew * dy + dx == 8)
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    // columns -2, -1, w and w + 1 are written too, with zero errors: a tap that reaches past either end of a row
-                    // reads them instead of testing its column
+                    // columns -2, -1, w and w + 1 are written too, with zero errors: see band_tap_source
                     if (row_ok && x >= -2 && x < w + 2) {
                         uint32_t *slot = &s_ring[wv][L][(x & (kIdRing - 1)) * 2];
                         const uint32_t p0 = ((uint32_t)e0 & 0xffffu) | ((uint32_t)e1 << 16), p1 = (uint32_t)e2;
@@ -279,15 +249,7 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                 }
-#pragma unroll
-                for (int k = 0; k < PW - 3; ++k) {
-                    cur[k] = cur[k + 3];
-                    outb[k] = outb[k + 3];
-                }
-                cur[PW - 3] = cur[PW - 2] = cur[PW - 1] = 0u;
-                outb[PW - 3] = cb[0] | (cb[1] << 24);
-                outb[PW - 2] = (cb[1] >> 8) | (cb[2] << 16);
-                outb[PW - 1] = (cb[2] >> 16) | (cb[3] << 8);
+                band_advance<PERIOD>(cur, outb, cb);
             }
         }
         // band finished: once its boundary stores have landed the band below may read any column

@@ -6,7 +6,7 @@
 //                                                                          the source's luminance; clamps; optional serpentine
 // Same pull formulation as ediff.hip (pixel + sum of fl32(err_src * coefficient) in the reference's visiting
 // order), with a fourth float per stored error that carries what the coefficient depends on (sensitivity, gate or
-// table row).  var_wavefront_kernel runs them on the anti-diagonal schedule of ediff.hip (serpentine off);
+// table row).  var_wavefront_kernel runs them on the banded wavefront schedule of ed_band.hip.h (serpentine off);
 // var_serial_kernel (lane = frame) covers Ostromoukhov's serpentine scan, whose rows are strictly sequential.
 //
 // variance_gate: scipy.ndimage.uniform_filter(size, mode='nearest') restated (float32 passes along axis 0 then
@@ -17,6 +17,7 @@
 
 #include "dp_internal.h"
 #include "ed_nearest.hip.h"
+#include "ed_band.hip.h"
 #include "tree_query.hip.h"
 #include "wave_util.hip.h"
 
@@ -236,15 +237,14 @@ __global__ __launch_bounds__(64) void os_rowserial_kernel(const uint8_t *__restr
     }
 }
 
-// ---- anti-diagonal wavefront version (serpentine off): same schedule as ed_wavefront_kernel in ediff.hip ------------
-// (one workgroup per frame, lane = row of a 64-row band, bands pipelined across the waves through a progress word,
-// global traffic in 16-step bursts), with four floats per stored error (the fourth is `aux`) and at most 12 waves so
-// that the wider rings fit LDS.  All four models have skew 2 (their only upward-left tap is dx=-1, dy=1).
+// ---- anti-diagonal wavefront version (serpentine off): the banded schedule of ed_band.hip.h, launched as ed_wavefront_kernel is ----
+// with four floats per stored error (the fourth is `aux`) and at most 12 waves so that the wider rings fit LDS.  All four models
+// have skew 2 (their only upward-left tap is dx=-1, dy=1).
 constexpr int kVWaves = 12;
 constexpr int kVRing = 8;
 constexpr int kVRingStride = kVRing * 4 + 4;
 constexpr int kVPeriod = 16;
-constexpr int kVProgWords = 64;  // progress words per frame when a frame's bands are spread over workgroups (ediff.hip)
+constexpr int kVPW = kVPeriod * 3 / 4;   // dwords of a period's pixels
 
 template <int CAP, int MODEL>  // MODEL: 1 perceptual, 2 hybrid, 3 adaptive variance, 4 Ostromoukhov (vp.model)
 __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8_t *__restrict__ in,
@@ -257,11 +257,11 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
     // G == 1 with progress words given: the repair launch behind a G > 1 launch (see ed_wavefront_kernel) -- only frames
     // whose give-up flag is set are done again
     if (G == 1 && gprog_all != nullptr &&
-        __hip_atomic_load(&gprog_all[(size_t)blockIdx.x * kVProgWords + kVProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+        __hip_atomic_load(&gprog_all[(size_t)blockIdx.x * kBandProgWords + kBandProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
         return;
     if (G != 1 && test_giveup) {
         if (threadIdx.x == 0)
-            __hip_atomic_store(&gprog_all[(size_t)(blockIdx.x / (unsigned)G) * kVProgWords + kVProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&gprog_all[(size_t)(blockIdx.x / (unsigned)G) * kBandProgWords + kBandProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
     // G > 1: the bands of a frame are spread over G workgroups (few frames in flight), see ed_wavefront_kernel
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
         uint8_t *fout = out + f * (size_t)h * w * 3;
         const uint8_t *fgate = vp.gate ? vp.gate + f * (size_t)h * w : nullptr;
         float *bnd = bnd_all + f * (size_t)4 * w * 4;  // [2 buffers][2 rows][w][4]
-        uint32_t *gprog = gprog_all + f * (size_t)kVProgWords;
+        uint32_t *gprog = gprog_all + f * (size_t)kBandProgWords;
         const int r = band * 64 + L;
         const float *bprev = bnd + (size_t)((band + 1) & 1) * 2 * w * 4;
         float *bnext = bnd + (size_t)(band & 1) * 2 * w * 4;
@@ -327,41 +327,33 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
         constexpr int kDy[4] = {1, 1, MODEL == 4 ? 0 : 1, 0};
         constexpr float kW[4] = {1.0f / 16, 5.0f / 16, 3.0f / 16, 7.0f / 16};
         constexpr int kCol[3] = {2, 1, 0};
-        // where each tap of this lane's row finds its source row: the ring of a row of the band, the ring of the two rows
-        // above the band, or -- the row does not exist -- the zero slot; the rings hold zero errors for the two columns
-        // either side of the image (below), so a tap needs neither a row nor a column test
-        typedef const __attribute__((address_space(3))) float lds_float_t;
+        // where each tap of this lane's row finds its source row (band_tap_source)
+        typedef band_lds_t<float> lds_float_t;
         lds_float_t *tb[4];
         uint32_t tm[4];
 #pragma unroll
         for (int k = 0; k < ntaps; ++k) {
-            const int rel = L - kDy[k];
-            const bool exists = r - kDy[k] >= 0;
+            const int rel = L - kDy[k];   // (-1 .. 63: dy <= 1)
             const float *row = rel >= 0 ? &s_ring[wv][rel][0] : &s_vring[wv][rel + 2][0][0];
-            tb[k] = exists ? (lds_float_t *)row : (lds_float_t *)s_zero4;
-            tm[k] = exists ? (rel >= 0 ? (uint32_t)(kVRing - 1) : 63u) : 0u;
+            band_tap_source<float>(r - kDy[k] >= 0, rel, row, s_zero4, kVRing, tb[k], tm[k]);
         }
-        uint32_t pix[12], cur[13], outb[13], gpx[4], gcur[5];
+        // a period's pixels in flight / being consumed / being produced, and (model 3) its gate bytes in flight / being consumed
+        uint32_t pix[kVPW], cur[kVPW + 1], outb[kVPW + 1], gpx[kVPeriod / 4], gcur[kVPeriod / 4 + 1];
         float pb0 = 0.f, pb1 = 0.f, pb2 = 0.f, pb3 = 1.0f;
         int pb_col = 0;
         bool pb_valid = false;
 #pragma unroll
-        for (int k = 0; k < 12; ++k) pix[k] = 0;
+        for (int k = 0; k < kVPW; ++k) pix[k] = 0;
 #pragma unroll
-        for (int k = 0; k < 13; ++k) cur[k] = outb[k] = 0;
+        for (int k = 0; k < kVPW + 1; ++k) cur[k] = outb[k] = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) gpx[k] = gcur[k] = 0;
-        gcur[4] = 0;
+        for (int k = 0; k < kVPeriod / 4; ++k) gpx[k] = gcur[k] = 0;
+        gcur[kVPeriod / 4] = 0;
 
         for (int t0 = -kVPeriod; t0 < steps + kVPeriod; t0 += kVPeriod) {
+            // period boundary: everything issued one period ago has landed
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (L == 0) {
-                int ack = t0 - kVPeriod - 63 * skew + 1024;
-                ack = ack < 0 ? 0 : ack;
-                const uint32_t word = ((uint32_t)gb << 16) | (uint32_t)ack;
-                if (G == 1) s_prog[wv] = word;
-                else __hip_atomic_store(&gprog[gw], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (L == 0) band_publish(G, &s_prog[wv], &gprog[gw], gb, t0 - kVPeriod, skew);
             if (pb_valid) {
                 float *dst = &s_vring[wv][L >> 5][pb_col & 63][0];
                 dst[0] = pb0;
@@ -370,32 +362,10 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
                 dst[3] = pb3;
             }
             {
-                const int xs = (t0 - kVPeriod) - skew * L;
-                const int lo = xs < 0 ? 0 : xs, hi = xs + kVPeriod > w ? w : xs + kVPeriod;
-                if (row_ok && hi > lo) {
-                    const long B = row_byte + (long)xs * 3;
-                    if (lo == xs && hi == xs + kVPeriod) {
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) *reinterpret_cast<uint32_t *>(fout + B + 4 * k) = outb[k];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < kVPeriod; ++i) {
-                            if (xs + i >= 0 && xs + i < w) {
-                                const int bo = 3 * i;
-                                const uint32_t c = __funnelshift_r(outb[bo >> 2], outb[(bo >> 2) + 1], (bo & 3) * 8);
-                                uint8_t *o = fout + B + bo;
-                                o[0] = (uint8_t)c;
-                                o[1] = (uint8_t)(c >> 8);
-                                o[2] = (uint8_t)(c >> 16);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 13; ++k) outb[k] = 0;
-                if (L >= 62 && row_ok && hi > lo) {
-                    for (int i = lo - xs; i < hi - xs; ++i) {
-                        float *b = bnext + ((size_t)(L - 62) * w + (xs + i)) * 4;
+                const BandCols c = band_flush<kVPeriod>(fout, r, w, (t0 - kVPeriod) - skew * L, row_ok, outb);
+                if (L >= 62 && row_ok && c.hi > c.lo) {
+                    for (int i = c.lo - c.xs; i < c.hi - c.xs; ++i) {
+                        float *b = bnext + ((size_t)(L - 62) * w + (c.xs + i)) * 4;
                         if (G == 1) {
                             b[0] = s_bout[wv][L - 62][i][0];
                             b[1] = s_bout[wv][L - 62][i][1];
@@ -410,66 +380,34 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 12; ++k) cur[k] = pix[k];
+            for (int k = 0; k < kVPW; ++k) cur[k] = pix[k];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gcur[k] = gpx[k];
+            for (int k = 0; k < kVPeriod / 4; ++k) gcur[k] = gpx[k];
             {
                 const int xn = (t0 + kVPeriod) - skew * L;
-                const long B = row_byte + (long)xn * 3;
                 if (row_ok && xn + kVPeriod > 0 && xn < w) {
-                    if (B >= 0 && B + 48 <= frame_bytes) {
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) pix[k] = *reinterpret_cast<const uint32_t *>(fin + B + 4 * k);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) {
-                            uint32_t v = 0;
-#pragma unroll
-                            for (int bb = 0; bb < 4; ++bb) {
-                                const long a = B + 4 * k + bb;
-                                if (a >= 0 && a < frame_bytes) v |= (uint32_t)fin[a] << (8 * bb);
-                            }
-                            pix[k] = v;
-                        }
-                    }
-                    if (model == 3) {  // the next 16 gate bytes of this row
-                        const long G = row_gate + xn;
-                        if (G >= 0 && G + 16 <= gate_bytes) {  // four (unaligned) dword loads instead of sixteen byte loads
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) gpx[k] = *reinterpret_cast<const uint32_t *>(fgate + G + 4 * k);
-                        } else
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            uint32_t v = 0;
-#pragma unroll
-                            for (int bb = 0; bb < 4; ++bb) {
-                                const long a = G + 4 * k + bb;
-                                if (a >= 0 && a < gate_bytes) v |= (uint32_t)fgate[a] << (8 * bb);
-                            }
-                            gpx[k] = v;
-                        }
-                    }
+                    band_fetch<kVPW>(fin, row_byte + (long)xn * 3, frame_bytes, pix);
+                    if (model == 3) band_fetch<kVPeriod / 4>(fgate, row_gate + xn, gate_bytes, gpx);  // the next 16 gate bytes of this row
                 }
             }
             pb_valid = false;
             if (band > 0) {
-                const int x0n = t0 + kVPeriod;
-                int need = x0n + 18;
-                need = need > w ? w : need;
-                if (x0n - 14 < w && need > 0) {
-                    const uint32_t want = (uint32_t)(need + 1024);
+                const BandWindow<kVPeriod> win(t0, w);
+                if (win.first() < w && win.need > 0) {
+                    const uint32_t want = (uint32_t)(win.need + 1024);
                     for (uint32_t spins = 0;; ++spins) {
                         const uint32_t v = G == 1 ? s_prog[pw] : __hip_atomic_load(&gprog[pw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((int)(v >> 16) > gb - 1 || ((int)(v >> 16) == gb - 1 && (v & 0xffffu) >= want)) break;
                         __builtin_amdgcn_s_sleep(4);
-                        // another workgroup produces this: never wait forever (a give-up flag stays in the workspace)
+                        // across workgroups the producer is another workgroup of the grid: never wait for it forever
+                        // (a give-up flag stays in the workspace; the launch ends instead of hanging)
                         if (G != 1 && (spins > (1u << 24) || (spins % 1024u == 1023u &&
-                                                               __hip_atomic_load(&gprog[kVProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))) {
-                            if (L == 0) __hip_atomic_store(&gprog[kVProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                                               __hip_atomic_load(&gprog[kBandProgWords - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))) {
+                            if (L == 0) __hip_atomic_store(&gprog[kBandProgWords - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             return;
                         }
                     }
-                    const int col = x0n - 14 + (L & 31);
+                    const int col = win.col(L);
                     if (col >= 0 && col < w) {
                         const float *b = bprev + ((size_t)(L >> 5) * w + col) * 4;
                         pb0 = __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -489,7 +427,7 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
 
-            // four steps per round (see ed_wavefront_kernel): the period buffers move by whole registers
+            // four steps per round (band_pixel, band_advance)
             for (int i4 = 0; i4 < kVPeriod; i4 += 4) {
               uint32_t cb[4];
 #pragma unroll
@@ -501,8 +439,7 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
                 float e0 = 0.f, e1 = 0.f, e2 = 0.f, aux = 1.0f;
                 uint32_t cbytes = 0;
                 if (act) {
-                    const uint32_t pxv = q == 0 ? cur[0] : (q == 1 ? __funnelshift_r(cur[0], cur[1], 24)
-                                                               : (q == 2 ? __funnelshift_r(cur[1], cur[2], 16) : (cur[2] >> 8)));
+                    const uint32_t pxv = band_pixel(cur, q);
                     const float g0 = (float)s_lut[pxv & 255u], g1 = (float)s_lut[(pxv >> 8) & 255u],
                                 g2 = (float)s_lut[(pxv >> 16) & 255u];
                     float a0 = g0, a1 = g1, a2 = g2;
@@ -593,17 +530,9 @@ __global__ __launch_bounds__(64 * kVWaves) void var_wavefront_kernel(const uint8
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
               }
+              band_advance<kVPeriod>(cur, outb, cb);
 #pragma unroll
-              for (int k = 0; k < 9; ++k) {
-                  cur[k] = cur[k + 3];
-                  outb[k] = outb[k + 3];
-              }
-              cur[9] = cur[10] = cur[11] = 0u;
-              outb[9] = cb[0] | (cb[1] << 24);
-              outb[10] = (cb[1] >> 8) | (cb[2] << 16);
-              outb[11] = (cb[2] >> 16) | (cb[3] << 8);
-#pragma unroll
-              for (int k = 0; k < 4; ++k) gcur[k] = gcur[k + 1];  // four gate bytes consumed
+              for (int k = 0; k < kVPeriod / 4; ++k) gcur[k] = gcur[k + 1];  // four gate bytes consumed
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -866,7 +795,7 @@ int launch_variable_diffusion(const uint8_t *in, uint8_t *out, int64_t n_frames,
                 nw = (nwt + G - 1) / G;
                 const size_t prog_off = ((size_t)n_frames * (size_t)w * 64 + 255) & ~(size_t)255;
                 gprog = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ws) + prog_off);
-                DP_HIP(hipMemsetAsync(gprog, 0, (size_t)n_frames * kVProgWords * sizeof(uint32_t), s));
+                DP_HIP(hipMemsetAsync(gprog, 0, (size_t)n_frames * kBandProgWords * sizeof(uint32_t), s));
             }
         }
         const int test_giveup = exp_env("DP_ED_TEST_GIVEUP") ? 1 : 0;

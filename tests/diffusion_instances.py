@@ -280,5 +280,27 @@ for _pal in ("palr16", "palr300", "degenerate200"):
 for _r in range(GATE_MAX_R + 2):
     _add(f"gate-r{_r}", "variance_gate", "palr16", (2, 17, 65), dict(var_threshold=300.0, window_radius=_r),
          ((("fused", _r) if _r <= GATE_MAX_R else ("two_pass",)), None), "radius <= kGateMaxR: the fused kernel of that radius")
+# -- the shared pieces of the band kernels (csrc/ed_band.hip.h) at the widths where they can go wrong; appended last, so that the rows
+# above keep their content seeds.  PERIOD is 8 for the four-wave instance of error_diffusion, 16 for its sixteen-wave instance and for
+# variable_diffusion; `why` names the helper path of each row.  (Three bands under one workgroup at w = 23 < 64 columns: the edw- and
+# varw- rows above; more than 64 columns under one workgroup: the rows below.)
+BAND_SHAPES = [((1, 3, _w), f"w = PERIOD {_w - _p:+d} = {_w}, one band: band_flush writes a row that ends {_p - _w:+d} columns from a period "
+                            f"boundary byte by byte, and the pixel prefetch (band_fetch in var_wavefront) assembles the ends of the {9 * _w}-byte frame bytewise")
+               for _p in (8, 16) for _w in (_p - 1, _p, _p + 1)]
+BAND_TALL = [((1, 321, _w), f"w = 16 {_w - 16:+d}, six bands: BandWindow's 32 columns hang over both ends of the row in every period (band_col_margin on "
+                            f"both sides); band_flush / band_advance at PERIOD = 16") for _w in (15, 16, 17)]
+BAND_ODD = [((1, 1, 1), "no row above (band_tap_source: the zero slot for every tap) and a frame shorter than one dword: band_fetch and band_flush bytewise at both ends at once"),
+            ((1, 65, 9), "the second band has a single row: BandWindow / band_poll with one lane at work, band_finished after w + 0 * skew steps"),
+            ((2, 130, 70), "three bands under one workgroup, wider than the 64-column ring of the rows above: BandWindow columns wrap in s_vring; whole-dword band_flush")]
+for _shape, _why in [s for s in BAND_SHAPES if s[0][2] in (7, 8, 9)] + BAND_TALL + BAND_ODD:
+    _waves = 4 if _shape[1] <= 256 else MAX_WAVES
+    _add(f"band-ed-{_shape[0]}x{_shape[1]}x{_shape[2]}", "error_diffusion", "palr40", _shape, dict(taps="floyd_steinberg", serpentine=False),
+         (ed_wavefront("lists", 4, _waves), "one_wg"), _why)
+for _shape, _why in [s for s in BAND_SHAPES if s[0][2] in (15, 16, 17)] + BAND_TALL + BAND_ODD:
+    _add(f"band-var-{_shape[0]}x{_shape[1]}x{_shape[2]}", "variable_diffusion", "palr40", _shape, dict(model=1, serpentine=False),
+         (("var_wavefront", QS, 1), "one_wg"), _why)
+# model 3's gate bytes go through band_fetch as well (one byte per pixel): a map of tests/test_gpu_diffusion_instances.py: _gate_patterns
+_add("band-var-gate-2x130x70", "variable_diffusion", "palr40", (2, 130, 70), dict(model=3, serpentine=False, gate_pattern="checkerboard"),
+     (("var_wavefront", QS, 3), "one_wg"), "band_fetch<4> of the gate bytes, a period ahead, at both ends of the map and across three bands")
 
 assert len({c.id for c in CASES}) == len(CASES)

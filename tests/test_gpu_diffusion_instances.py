@@ -67,7 +67,9 @@ def _inputs(orc, case):
     assert kind == "rnd"
     frames = [orc.rnd(h, w, 1000 * seed + i) for i in range(distinct)]
     gates = None
-    if case.params.get("model") == 3:
+    if case.params.get("model") == 3 and "gate_pattern" in case.params:      # a map of _gate_patterns, its open bytes shifted per frame
+        gates = [_gate_bytes(_gate_patterns(h, w)[case.params["gate_pattern"]], i) for i in range(distinct)]
+    elif case.params.get("model") == 3:
         rs = np.random.RandomState(seed)
         gates = [np.array(GATE_BYTES, np.uint8)[rs.randint(0, len(GATE_BYTES), (h, w))] for _ in range(distinct)]
     return frames, gates

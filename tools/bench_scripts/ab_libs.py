@@ -6,6 +6,7 @@ usage: ab_libs.py [case ...]   cases: variant:K:frames  (e.g. floyd_steinberg:16
        ImageDitherer(DitherMode.RIEMERSMA).apply_dithering_frames (one backend.riemersma launch underneath): the three
        one-wave-per-frame kernels, on 1080p frames (a step of theirs is a pixel, ~0.5 s a launch: one warm-up and three timed
        launches per repetition; profiles/HISTORY.md has the A/A noise of these cases)
+       or integer error diffusion (idiff.hip) with a variant's taps on 4K frames: idiff_floyd_steinberg:16:1, idiff_jjn:256:24
        or ordered modes on 1080p frames: bayer4:K:frames, bayer8:K:frames, none:K:frames, ign:K:frames (bayer4:16:100 = C5's launch;
        K <= 64: the uniform palette, else palr(K, 7); the cell table is built before the timing)
        or the PNG-8 encoder's fixed-mode entry point on photo-like 1080p planes: png:K:frames (dp_png_deflate_encode_u8 at the default
@@ -63,6 +64,8 @@ for case in cases:
                 d = ImageDitherer(K, ORDERED[variant][0], pal, False, ORDERED[variant][1]).prepare()
             elif variant == "riemersma":
                 d = ImageDitherer(K, DitherMode.RIEMERSMA, pal, False, {})
+            elif variant.startswith("idiff_"):
+                d = ImageDitherer(K, dithering_lib.IntegerErrorDiffusionDitherStrategy(variant[6:]), pal, False, {})
             elif variant in ("perceptual", "hybrid", "adaptive_variance", "ostromoukhov"):
                 d = ImageDitherer(K, DitherMode(variant), pal, False, {"serpentine": serp} if variant == "ostromoukhov" else {})
             else:
