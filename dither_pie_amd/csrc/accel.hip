@@ -427,9 +427,9 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
     //         4-entry table [2 x 4096 words]
     //         | the flat lists of their split cells [2 x kWideCap x kWideList words]
     //         | the compact (one byte per entry) copy of the crowded table [kCompactMaxWords]
-    //         | the fine table as ordered_fine_kernel stages it [kLeanTabBytes at most]
+    //         | the fine table as ordered_fine_kernel stages it [kLeanTabBytes at most] | the two-level fine table [the same]
     const size_t bytes = sizeof(uint32_t) * (3 * kCodeWords + 2 * kTabMaxWords + kTabCapWords) + sizeof(uint4) * kExcCap + 16 + 768 +
-                         sizeof(uint32_t) * (2 * kCells + 2 * kWideCap * kWideList + kCompactMaxWords) + kLeanTabBytes;
+                         sizeof(uint32_t) * (2 * kCells + 2 * kWideCap * kWideList + kCompactMaxWords) + 2 * kLeanTabBytes;
     DP_HIP(hipMalloc((void **)&blob, bytes));
     struct DevFree {  // frees the scan masks on every way out
         void *p = nullptr;
@@ -714,6 +714,8 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
     // ordered_fine_kernel read the index-ordered table in global memory, so that one must be whole.
     dev.fine_tab = nullptr;
     dev.fine_words = dev.fine_win = dev.fine_wide = 0;
+    dev.fsub_tab = nullptr;
+    dev.fsub_win = dev.fsub_wide = 0;
     if (have8 && !st.too_big && !use4 && wbw == 0 && !dev.adapt && mw == 8 && K >= kWideList && !exp_env("DP_NO_FINE")) {
         fine_masks->resize((size_t)2 * kFineCells * mw);
         uint32_t *ftm = fine_masks->data(), *fnm = ftm + (size_t)kFineCells * mw;
@@ -783,10 +785,27 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
 // The fine table of ordered_fine_kernel (host_logic.h: fine_pack): windows of 4 + 2 candidates shared by the 8-wide cells, packed
 // from the sets build_accel kept (eight mask words per cell) and uploaded to its place in the accelerator's blob.  Fills the fine
 // fields of `dev`; a palette whose sets or table exceed the budget (ordered_fine.h) simply gets none.
-int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev)
+// sub: the two-level table instead (host_logic.h: fine_pack_sub; ordered_fine.h: fine_sub_fits), behind the place of the other one;
+// fills the fsub fields.
+int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev, const bool sub)
 {
     constexpr int mw = 8;
     FineTable ft;
+    if (sub) {
+        fine_pack_sub(fine_masks.data(), fine_masks.data() + (size_t)kFineCells * mw, mw, dev.K, p4_host, fine_sub_fits, ft);
+        if (exp_env("DP_DEBUG_ACCEL"))
+            fprintf(stderr, "accel K=%d: two-level fine table: %s, %d windows, %d wide cells, %zu sub-cells still wide, %lld bytes\n", dev.K,
+                    ft.ok ? "yes" : "no", ft.n_win, ft.n_wide, ft.sub_wide.size(), (long long)fine_sub_bytes(ft.n_win, ft.n_wide));
+        if (!ft.ok) return DP_OK;
+        const std::vector<uint32_t> im = ft.sub_image();
+        uint32_t *at = fine_dev + kLeanTabBytes / 4;
+        const hipError_t e = hipMemcpy(at, im.data(), sizeof(uint32_t) * im.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "accelerator upload (two-level fine table)");
+        dev.fsub_tab = at;
+        dev.fsub_win = ft.n_win;
+        dev.fsub_wide = ft.n_wide;
+        return DP_OK;
+    }
     fine_pack(fine_masks.data(), fine_masks.data() + (size_t)kFineCells * mw, mw, dev.K, p4_host, fine_table_fits, ft);
     if (exp_env("DP_DEBUG_ACCEL"))
         fprintf(stderr, "accel K=%d: fine table: %s, %d windows, %d wide cells, %lld bytes\n", dev.K, ft.ok ? "yes" : "no", ft.n_win, ft.n_wide,

@@ -33,6 +33,11 @@ inline const char *exp_env(const char *name)
     return nullptr;
 #endif
 }
+#ifdef DP_EXPERIMENTS
+constexpr bool kExperiments = true;
+#else
+constexpr bool kExperiments = false;
+#endif
 int hip_fail(hipError_t e, const char *what);
 
 // experiments build only: DP_ED_TRACE=1 names the kernel of every launch_error_diffusion / launch_variable_diffusion call on
@@ -115,6 +120,10 @@ struct PalDev {
     const uint32_t *fine_tab;
     int fine_words;             // words of the image
     int fine_win, fine_wide;    // its windows (4 + 2 entries each) and the flat lists of its wide cells
+    // the two-level table (host_logic.h: FineTable::sub_image; ordered_fine.h: fine_sub_level), with windows for the 4-wide
+    // sub-cells of the wide cells; nullptr when absent
+    const uint32_t *fsub_tab;
+    int fsub_win, fsub_wide;
     int n_split;
     int n_slow_blocks;
     int n_split_cells;          // 16^3 cells of cell_tab that are split (a palette crowded into few cells has many)
@@ -232,6 +241,10 @@ struct dp_palette {
     std::vector<uint32_t> fine_masks;
     uint32_t *fine_dev;              // its place in accel_blob
     std::atomic<bool> fine_pending;  // fine_masks is waiting (read without build_mu by every matrix-mode call)
+    // The two-level table is tried first.  Where it fits, the product library packs today's table only for a call whose thresholds
+    // do not fit beside the two-level layout (more than fine_sub_room bytes), and keeps fine_masks until then.
+    std::atomic<bool> fine_plain_pending;
+    std::atomic<int> fine_sub_room;
     // the colour metric (include/ditherpie_hip_metric.h), fixed at birth.  A palette of DP_METRIC_OKLAB is searched only through
     // its top-2 table (metric.hip), built at the first call that needs it under build_mu and published under dev_mu like `pat`
     int metric;
@@ -263,7 +276,7 @@ void prof_end(ProfMark *m, hipStream_t s);
 namespace dp {
 int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_out, size_t *blob_bytes, std::vector<uint32_t> *fine_masks,
                 uint32_t **fine_dev);
-int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev);
+int build_fine(PalDev &dev, const std::vector<uint32_t> &p4_host, const std::vector<uint32_t> &fine_masks, uint32_t *fine_dev, bool sub);
 int build_accel_float(PalDev &dev, const float *pal_f32, const uint8_t *lut_host, void **blob_out, size_t *blob_bytes);
 int build_ed_cells(PalDev &dev, const double *pts_host, void **blob_out);
 int build_ed_ext(PalDev &dev, const double *pts_host, void **blob_out);   // the unclamped diffusers' extended lists (ediff.hip)

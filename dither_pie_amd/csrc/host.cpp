@@ -7,6 +7,7 @@
 #include <numeric>
 
 #include "dp_internal.h"
+#include "ordered_fine.h"
 #include "../../include/ditherpie_hip_dotdiff.h"
 #include "../../include/ditherpie_hip_cells.h"
 #include "../../include/ditherpie_hip_voidcluster.h"
@@ -272,6 +273,8 @@ int dp::palette_create_impl(const char *fn, const float *pal_f32, const uint8_t 
     p->pat_blob = nullptr;
     p->fine_dev = nullptr;
     p->fine_pending = false;
+    p->fine_plain_pending = false;
+    p->fine_sub_room = 0;
     p->metric = metric;
     p->met = dp::MetDev{nullptr, nullptr, nullptr, nullptr, 0};   // the top-2 table of a metric palette: built when first needed (metric.hip)
     p->met_blob = nullptr;
@@ -330,18 +333,38 @@ static int ensure_ed_ext(const dp_palette *pal_c)
 // The fine table of ordered_fine_kernel: packed (4 ms at 256 colours) at the first matrix-mode call with integer thresholds after
 // the accelerator was built, so that nearest-only, IGN and diffusion users never pay for it and the accelerator's build stays
 // what it was.  Not inside a stream capture: the upload is a copy.
-static int ensure_fine_table(const dp_palette *pal_c, hipStream_t s)
+// The two-level table (ordered_fine.h: fine_sub_level) is packed first.  Where the palette gets one, today's table is packed only
+// for a call whose thresholds (thr_bytes) do not fit beside it -- one pack in the common case -- except in the experiments build,
+// which keeps both so that every level can run on one palette.
+static int ensure_fine_table(const dp_palette *pal_c, hipStream_t s, const int thr_bytes)
 {
     dp_palette *p = const_cast<dp_palette *>(pal_c);
     std::lock_guard<std::mutex> lock(p->build_mu);
-    if (!p->fine_pending.load()) return DP_OK;
+    const bool first = p->fine_pending.load();
+    if (!first && !(p->fine_plain_pending.load() && thr_bytes > p->fine_sub_room.load())) return DP_OK;
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return DP_OK;
-    p->fine_pending = false;
     dp::PalDev d = snapshot(p);
-    const int rc = build_fine(d, p->p4_host, p->fine_masks, p->fine_dev);
-    std::vector<uint32_t>().swap(p->fine_masks);
-    if (rc != DP_OK) return rc;
+    bool plain = !first;
+    if (first) {
+        p->fine_pending = false;
+        if (dp::kFineSubShipped > 0 || dp::kExperiments) {
+            const int rc = build_fine(d, p->p4_host, p->fine_masks, p->fine_dev, true);
+            if (rc != DP_OK) return rc;
+        }
+        const int room = d.fsub_tab ? dp::kLeanTabBytes - (int)dp::fine_sub_bytes(d.fsub_win, d.fsub_wide) : -1;
+        plain = dp::kExperiments || thr_bytes > room;
+        if (!plain) {
+            p->fine_sub_room = room;
+            p->fine_plain_pending = true;
+        }
+    }
+    if (plain) {
+        p->fine_plain_pending = false;
+        const int rc = build_fine(d, p->p4_host, p->fine_masks, p->fine_dev, false);
+        std::vector<uint32_t>().swap(p->fine_masks);
+        if (rc != DP_OK) return rc;
+    }
     publish(p, d);
     return DP_OK;
 }
@@ -636,8 +659,11 @@ int dp_ordered_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
                   dp_ordered_workspace_bytes(n_frames, h, w));
         return DP_EWORKSPACE;
     }
-    if (mode == DP_MODE_MATRIX && thr->dev.mpad && pal->fine_pending.load(std::memory_order_relaxed)) {
-        const int rc = ensure_fine_table(pal, (hipStream_t)stream);
+    const int fine_thr_bytes = mode == DP_MODE_MATRIX && thr->dev.mpad ? thr->dev.th_h * thr->dev.tw_pad * 4 : 0;
+    if (mode == DP_MODE_MATRIX && thr->dev.mpad &&
+        (pal->fine_pending.load(std::memory_order_relaxed) ||
+         (pal->fine_plain_pending.load(std::memory_order_relaxed) && fine_thr_bytes > pal->fine_sub_room.load(std::memory_order_relaxed)))) {
+        const int rc = ensure_fine_table(pal, (hipStream_t)stream, fine_thr_bytes);
         if (rc != DP_OK) return rc;
     }
     return launch_ordered(in_dev, out_dev, n_frames, h, w, y0, x0, snapshot(pal), mode, thr ? &thr->dev : nullptr,

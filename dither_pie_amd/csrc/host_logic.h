@@ -507,6 +507,11 @@ constexpr int kFineQuad = 4, kFineWindow = 6;  // entries of A, of A + B
 constexpr int kFineIds = kWideCap;             // the ascending cell numbers of the wide cells, padded to this many with 0xffff
 
 inline int fine_cell(const int r, const int g, const int b) { return (r >> 3) | ((g >> 3) << 5) | ((b >> 3) << 10); }
+// The two-level table: a wide cell's eight sub-cells of 4 colours a side, numbered by bit 2 of r, g and b, have sets of their own,
+// and all but a few of them fit a window.  The cell's entry of `off` is then this tag plus the cell's rank among the wide cells (read
+// as int16 it is negative: one compare), and row `rank` holds the windows of the eight sub-cells.
+constexpr uint16_t kFineSubTag = 0x8000u;
+inline int fine_sub_cell(const int r, const int g, const int b) { return ((r >> 2) & 1) | (((g >> 2) & 1) << 1) | (((b >> 2) & 1) << 2); }
 
 struct FineTable {
     bool ok = false;             // false: no fine table for this palette (a set above kWideList, too many wide cells or windows)
@@ -518,6 +523,10 @@ struct FineTable {
     std::vector<uint16_t> wide_cell; // [n_wide] ascending
     std::vector<uint32_t> wide;      // [n_wide][kWideList] T(cell) in index order, padded with further entries
     std::vector<uint16_t> wide_idx;  // ... as palette indices
+    // the two-level table (fine_pack_sub): off[wide cell] = kFineSubTag | its rank among the wide cells, and a row per wide cell
+    bool sub = false;
+    std::vector<uint16_t> rows;      // [n_wide][8] the window of each 4-wide sub-cell; 0 (the reserved window): still wide
+    std::vector<uint16_t> sub_wide;  // rank * 8 + sub-cell of the still-wide sub-cells, ascending
     // the image the kernel copies to LDS: A | wide lists | B | off (two per word) | wide cell numbers (kFineIds, two per word)
     std::vector<uint32_t> lds_image() const
     {
@@ -533,6 +542,18 @@ struct FineTable {
         }
         return im;
     }
+    // the image of the two-level table: A | wide lists | B | off with tags (two per word) | rows (two entries per word)
+    std::vector<uint32_t> sub_image() const
+    {
+        std::vector<uint32_t> im;
+        im.reserve(quad.size() + wide.size() + pair.size() + kFineCells / 2 + rows.size() / 2);
+        im.insert(im.end(), quad.begin(), quad.end());
+        im.insert(im.end(), wide.begin(), wide.end());
+        im.insert(im.end(), pair.begin(), pair.end());
+        for (int c = 0; c < kFineCells; c += 2) im.push_back((uint32_t)off[c] | ((uint32_t)off[c + 1] << 16));
+        for (size_t i = 0; i < rows.size(); i += 2) im.push_back((uint32_t)rows[i] | ((uint32_t)rows[i + 1] << 16));
+        return im;
+    }
 };
 
 // tmask / nmask: [kFineCells][mw] membership of T(cell) / N(cell), cells numbered by fine_cell.  fits(n_win, n_wide): whether
@@ -540,9 +561,14 @@ struct FineTable {
 // longest T first, then longest N, then by number; a cell whose pair (N, T) was met before takes that cell's window; any other
 // goes into the window -- among those that hold its rarest member of N in their quad -- that needs the fewest new entries (the
 // lowest numbered among equals), or into a new window when none takes it.  Sets are 256-bit masks throughout (K <= 256).
+// fine_pack_units is both packers: `sub` false is fine_pack; true is fine_pack_sub, which computes the sets of the sub-cells of the
+// wide cells from the cells' flat lists (N(x) and T(x) of a colour lie inside T(cell)) and packs the cells that are not wide and the
+// sub-cells that are not wide as ONE population under the same rule: a unit is a cell (its number) or a sub-cell (kFineCells + 8 *
+// rank + sub-cell), ordered longest T first, then longest N, then by unit number.  fits(n_win, n_wide) is then the budget of the
+// two-level layout (ordered_fine.h: fine_sub_fits).
 template <class Fits>
-void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const int K, const std::vector<uint32_t> &coord4, Fits fits,
-               FineTable &ft)
+void fine_pack_units(const uint32_t *tmask, const uint32_t *nmask, const int mw, const int K, const std::vector<uint32_t> &coord4, Fits fits,
+                     FineTable &ft, const bool sub)
 {
     ft = FineTable{};
     if (K < kWideList || K > 256 || K > 32 * mw) return;
@@ -601,10 +627,51 @@ void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const
         cls[cell] = (uint8_t)((kFineWindow - nt) * (kFineQuad + 1) + (kFineQuad - nn));  // longest T first, then longest N
         ++class_count[cls[cell] + 1];
     }
+    const int n_units = kFineCells + (sub ? 8 * ft.n_wide : 0);
+    if (sub) {
+        tms.resize(n_units), nms.resize(n_units), cls.resize(n_units, 0xff);
+        for (int k = 0; k < ft.n_wide; ++k) {
+            const int cell = ft.wide_cell[k];
+            const int r0 = (cell & 31) * 8, g0 = ((cell >> 5) & 31) * 8, b0 = (cell >> 10) * 8;
+            const uint16_t *list = &ft.wide_idx[(size_t)k * kWideList];
+            int pr[kWideList], pg[kWideList], pb[kWideList];
+            for (int i = 0; i < kWideList; ++i) {
+                const uint32_t c = coord4[list[i]];
+                pr[i] = (int)(c & 255u), pg[i] = (int)((c >> 8) & 255u), pb[i] = (int)((c >> 16) & 255u);
+            }
+            for (int s = 0; s < 8; ++s) {
+                Mask tm{{0, 0, 0, 0}}, nm{{0, 0, 0, 0}};
+                for (int i = 0; i < 64; ++i) {
+                    const int r = r0 + (s & 1) * 4 + (i & 3), g = g0 + ((s >> 1) & 1) * 4 + ((i >> 2) & 3), b = b0 + (s >> 2) * 4 + (i >> 4);
+                    int d[kWideList], d0 = 1 << 30, d1 = 1 << 30;  // the two smallest, with multiplicity
+                    for (int q = 0; q < kWideList; ++q) {
+                        d[q] = (r - pr[q]) * (r - pr[q]) + (g - pg[q]) * (g - pg[q]) + (b - pb[q]) * (b - pb[q]);
+                        if (d[q] < d0) d1 = d0, d0 = d[q];
+                        else if (d[q] < d1) d1 = d[q];
+                    }
+                    for (int q = 0; q < kWideList; ++q) {
+                        if (d[q] <= d1) tm.set(list[q]);
+                        if (d[q] == d0) nm.set(list[q]);
+                    }
+                }
+                const int u = kFineCells + 8 * k + s;
+                tms[u] = tm, nms[u] = nm;
+                const int nt = tm.count(), nn = nm.count();
+                if (nn > kFineQuad || nt > kFineWindow) {
+                    ft.sub_wide.push_back((uint16_t)(8 * k + s));
+                    continue;
+                }
+                cls[u] = (uint8_t)((kFineWindow - nt) * (kFineQuad + 1) + (kFineQuad - nn));
+                ++class_count[cls[u] + 1];
+            }
+        }
+    }
     for (int c = 0; c < kClasses; ++c) class_count[c + 1] += class_count[c];
     std::vector<int> order(class_count[kClasses]);
-    for (int cell = 0; cell < kFineCells; ++cell)
+    for (int cell = 0; cell < n_units; ++cell)
         if (cls[cell] != 0xff) order[class_count[cls[cell]]++] = cell;
+    std::vector<uint16_t> unit_win(sub ? n_units : 0, 0);  // (the cells' are ft.off)
+    auto win_of = [&](const int u) -> uint16_t & { return u < kFineCells ? ft.off[u] : unit_win[u]; };
     struct Win {
         Mask a, ab;  // the quad, the whole window
         int na, nb;
@@ -621,7 +688,7 @@ void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const
         bool met = false;
         for (; seen[slot] != 0; slot = (slot + 1) & (kSlots - 1))
             if (nms[seen[slot] - 1] == nm && tms[seen[slot] - 1] == tm) {
-                ft.off[cell] = ft.off[seen[slot] - 1];
+                win_of(cell) = win_of(seen[slot] - 1);
                 met = true;
                 break;
             }
@@ -678,7 +745,12 @@ void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const
                 holds[j].push_back(best);
             }
         });
-        ft.off[cell] = (uint16_t)best;
+        win_of(cell) = (uint16_t)best;
+    }
+    if (sub) {
+        ft.sub = true;
+        ft.rows.assign(unit_win.begin() + kFineCells, unit_win.end());
+        for (int k = 0; k < ft.n_wide; ++k) ft.off[ft.wide_cell[k]] = (uint16_t)(kFineSubTag | k);
     }
     // free places: the lowest indices the window does not hold yet; the reserved window: entry 0 six times
     ft.n_win = (int)wins.size();
@@ -705,6 +777,21 @@ void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const
             else ft.pair[(size_t)wi * (kFineWindow - kFineQuad) + p - kFineQuad] = c;
         }
     ft.ok = true;
+}
+
+// Today's table: the cells alone.  Its output is what tests/test_ordered_fine_cpu.py checks and does not depend on the other packer.
+template <class Fits>
+void fine_pack(const uint32_t *tmask, const uint32_t *nmask, const int mw, const int K, const std::vector<uint32_t> &coord4, Fits fits,
+               FineTable &ft)
+{
+    fine_pack_units(tmask, nmask, mw, K, coord4, fits, ft, false);
+}
+// The two-level table: cells and the sub-cells of the wide cells packed together (see fine_pack_units).
+template <class Fits>
+void fine_pack_sub(const uint32_t *tmask, const uint32_t *nmask, const int mw, const int K, const std::vector<uint32_t> &coord4, Fits fits,
+                   FineTable &ft)
+{
+    fine_pack_units(tmask, nmask, mw, K, coord4, fits, ft, true);
 }
 
 

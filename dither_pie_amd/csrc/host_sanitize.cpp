@@ -41,6 +41,14 @@
 //                                     OrderedFacts, one OrderedSwitches and one FineFacts; prints 0 / 1 per line
 //   host_xxx finekeys <cases.bin> <n>   the key level of the fine kernel (ordered_fine.h: fine_keys_level): n records of one FineFacts;
 //                                     prints one level per line
+//   host_xxx finesub <pal.u8> <K> <out.bin>   the two-level fine table (host_logic.h: fine_pack_sub) from the same brute-force sets,
+//                                     packed twice (the same answer) within fine_sub_fits, every sub-cell's window checked against
+//                                     sets brute-forced over the whole palette; writes int32 ok, n_win, n_wide, still-wide sub-cells,
+//                                     image words, then (uint16) off with its tags, the rows, the windows as palette indices, the wide
+//                                     cells, the still-wide sub-cells (8 * rank + sub-cell), the flat lists as palette indices, then
+//                                     (uint32) quads, pairs, lists as colours and the image, for tests/test_ordered_fine_sub_cpu.py
+//   host_xxx finesublevel <cases.bin> <n>   the SUB level of a call (ordered_fine.h: fine_sub_level): n records of one FineSubFacts;
+//                                     prints one level per line
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -740,6 +748,119 @@ static int run_finepack(const char *path, const int K, const char *out_path)
     return bad ? 1 : 0;
 }
 
+static int run_finesub(const char *path, const int K, const char *out_path)
+{
+    if (K < 2 || K > 256) {
+        fprintf(stderr, "finesub: 2 <= K <= 256\n");
+        return 2;
+    }
+    std::vector<uint8_t> pal((size_t)K * 3);
+    FILE *f = fopen(path, "rb");
+    if (!f || fread(pal.data(), 1, pal.size(), f) != pal.size()) {
+        fprintf(stderr, "cannot read %d colours from %s\n", K, path);
+        return 2;
+    }
+    fclose(f);
+    const int mw = 8;
+    std::vector<uint32_t> coord4(K), tm, nm;
+    for (int j = 0; j < K; ++j) coord4[j] = (uint32_t)pal[3 * j] | ((uint32_t)pal[3 * j + 1] << 8) | ((uint32_t)pal[3 * j + 2] << 16);
+    fine_masks(pal, K, mw, tm, nm);
+    FineTable ft, again;
+    fine_pack_sub(tm.data(), nm.data(), mw, K, coord4, fine_sub_fits, ft);
+    fine_pack_sub(tm.data(), nm.data(), mw, K, coord4, fine_sub_fits, again);  // the same answer every time
+    const std::vector<uint32_t> im = ft.ok ? ft.sub_image() : std::vector<uint32_t>();
+    int bad = ft.ok != again.ok || ft.off != again.off || ft.rows != again.rows || ft.win_idx != again.win_idx || ft.wide_idx != again.wide_idx ||
+              ft.sub_wide != again.sub_wide;
+    if (ft.ok) {
+        bad += (int64_t)im.size() * 4 != fine_sub_image_bytes(ft.n_win, ft.n_wide) || !fine_sub_fits(ft.n_win, ft.n_wide) || !ft.sub;
+        // the sets of every sub-cell of a wide cell over the WHOLE palette: in its window (N in the quad), or the sub-cell is still wide
+        size_t still = 0;
+        for (int k = 0; k < ft.n_wide; ++k) {
+            const int cell = ft.wide_cell[(size_t)k];
+            bad += ft.off[(size_t)cell] != (uint16_t)(kFineSubTag | k);
+            for (int sc = 0; sc < 8; ++sc) {
+                std::vector<uint8_t> in_t((size_t)K, 0), in_n((size_t)K, 0);
+                std::vector<int> d((size_t)K);
+                for (int i = 0; i < 64; ++i) {
+                    const int r = (cell & 31) * 8 + (sc & 1) * 4 + (i & 3), g = ((cell >> 5) & 31) * 8 + ((sc >> 1) & 1) * 4 + ((i >> 2) & 3),
+                              b = (cell >> 10) * 8 + (sc >> 2) * 4 + (i >> 4);
+                    bad += fine_cell(r, g, b) != cell || fine_sub_cell(r, g, b) != sc;
+                    int d0 = 1 << 30, d1 = 1 << 30;
+                    for (int j = 0; j < K; ++j) {
+                        const uint8_t *q = &pal[3 * (size_t)j];
+                        d[(size_t)j] = (r - q[0]) * (r - q[0]) + (g - q[1]) * (g - q[1]) + (b - q[2]) * (b - q[2]);
+                        if (d[(size_t)j] < d0) d1 = d0, d0 = d[(size_t)j];
+                        else if (d[(size_t)j] < d1) d1 = d[(size_t)j];
+                    }
+                    for (int j = 0; j < K; ++j) {
+                        if (d[(size_t)j] <= d1) in_t[(size_t)j] = 1;
+                        if (d[(size_t)j] == d0) in_n[(size_t)j] = 1;
+                    }
+                }
+                int nt = 0, nn = 0;
+                for (int j = 0; j < K; ++j) nt += in_t[(size_t)j], nn += in_n[(size_t)j];
+                const uint16_t wi = ft.rows[(size_t)k * 8 + sc];
+                const bool wide = nn > kFineQuad || nt > kFineWindow;
+                if (wide) {
+                    bad += wi != 0 || still >= ft.sub_wide.size() || ft.sub_wide[still] != (uint16_t)(8 * k + sc);
+                    ++still;
+                    continue;
+                }
+                bad += wi == 0 || wi >= ft.n_win;
+                if (wi == 0 || wi >= ft.n_win) continue;
+                const uint16_t *e = &ft.win_idx[(size_t)wi * kFineWindow];
+                for (int j = 0; j < K; ++j) {
+                    bool in_quad = false, in_win = false;
+                    for (int q = 0; q < kFineWindow; ++q)
+                        if (e[q] == j) in_win = true, in_quad = in_quad || q < kFineQuad;
+                    bad += (in_n[(size_t)j] && !in_quad) || (in_t[(size_t)j] && !in_win);
+                }
+            }
+        }
+        bad += still != ft.sub_wide.size();
+    }
+    f = fopen(out_path, "wb");
+    if (!f) return 2;
+    const int32_t head[5] = {ft.ok ? 1 : 0, ft.n_win, ft.n_wide, (int32_t)ft.sub_wide.size(), (int32_t)im.size()};
+    fwrite(head, sizeof(int32_t), 5, f);
+    if (ft.ok) {
+        fwrite(ft.off.data(), 2, ft.off.size(), f);
+        fwrite(ft.rows.data(), 2, ft.rows.size(), f);
+        fwrite(ft.win_idx.data(), 2, ft.win_idx.size(), f);
+        fwrite(ft.wide_cell.data(), 2, ft.wide_cell.size(), f);
+        fwrite(ft.sub_wide.data(), 2, ft.sub_wide.size(), f);
+        fwrite(ft.wide_idx.data(), 2, ft.wide_idx.size(), f);
+        fwrite(ft.quad.data(), 4, ft.quad.size(), f);
+        fwrite(ft.pair.data(), 4, ft.pair.size(), f);
+        fwrite(ft.wide.data(), 4, ft.wide.size(), f);
+        fwrite(im.data(), 4, im.size(), f);
+    }
+    fclose(f);
+    printf("finesub K=%d ok=%d windows=%d wide=%d still_wide=%zu bytes=%lld bad=%d\n", K, (int)ft.ok, ft.n_win, ft.n_wide, ft.sub_wide.size(),
+           (long long)(ft.ok ? fine_sub_bytes(ft.n_win, ft.n_wide) : 0), bad);
+    return bad ? 1 : 0;
+}
+
+static int run_finesublevel(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        FineSubFacts ff;
+        if (fread(&ff, sizeof(ff), 1, f) != 1 || ff.n_win < 0 || ff.n_wide < 0 || ff.thr_bytes < 0) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            fclose(f);
+            return 2;
+        }
+        printf("sub %d %d\n", c, fine_sub_level(ff));
+    }
+    fclose(f);
+    return 0;
+}
+
 static int run_fineplan(const char *path, const int n_cases)
 {
     FILE *f = fopen(path, "rb");
@@ -993,7 +1114,7 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1008,6 +1129,8 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finepack") return argc > 4 ? run_finepack(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "fineplan") return run_fineplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finekeys") return run_finekeys(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "finesub") return argc > 4 ? run_finesub(argv[2], atoi(argv[3]), argv[4]) : 2;
+    if (std::string(argv[1]) == "finesublevel") return run_finesublevel(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));

@@ -2026,6 +2026,14 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 // beside the colours and form a key with two instructions instead of four (cand4k / cand6k, same values); their LDS holds
 //   quads A | norms of A | pairs B (1) or records B' {c4, c5, N4, N5} (2) | windows of the cells | wide cell numbers | thresholds
 // and the flat lists of the wide cells are read from the table image in global memory.
+// SUB (ordered_fine.h: fine_sub_level; KEYS 1 only): 0 is the above.  1 and 2 run on the two-level table (host_logic.h: fine_pack_sub): a
+// wide cell's window number is a tag (bit 15) plus the cell's rank among the wide cells, and the main loop replaces it, one tile
+// ahead and under the lane mask, by the entry of row `rank` for the pixel's 4-wide sub-cell -- an ordinary window holding N and T
+// of the sub-cell, or the reserved window where the sub-cell is still wide.  Only the pixels of those leave the main path for
+// their set's sake; on the deferred path the tag gives the flat list's number.  1 is the cheaper partner of the A/B (experiments
+// build only): the main loop is SUB 0's -- the tags are staged as window 0 -- and the deferred path ranks a wide cell's pixel on its
+// sub-cell's window in LDS (resolve_window) instead of the sixteen entries of the global list.  LDS:
+//   quads A | norms of A | pairs B | window or tag of every cell | rows [n_wide x 8 u16] | thresholds
 // ---------------------------------------------------------------------------------------------
 
 // Keys of the six candidates of a window and the three smallest (see cand8)
@@ -2189,13 +2197,46 @@ __device__ __forceinline__ uint32_t fine_cell_offset(const uint32_t x)
 }
 
 struct FineLds {  // where the parts of the table are, in bytes from the start of LDS (wide_at: level 0 only; norm_at: levels 1, 2)
-    uint32_t wide_at, norm_at, pair_at, off_at, ids_at, thr_at;
+    uint32_t wide_at, norm_at, pair_at, off_at, ids_at, thr_at;  // (SUB 2: ids_at is where the rows are)
 };
+
+// SUB 2: LDS address of the row entry of a tagged window number `tag` for the colour x: rows + 16 * rank + 2 * sub-cell, the sub-cell
+// from bit 2 of r, g and b (host_logic.h: fine_sub_cell) as a dot product with the byte weights 2, 4, 8
+__device__ __forceinline__ uint32_t fine_row_address(const uint32_t tag, const uint32_t x, const uint32_t rows_at)
+{
+    const uint32_t sub2 = __builtin_amdgcn_udot4((x >> 2) & 0x010101u, 0x00080402u, rows_at, false);
+    return ((tag & (uint32_t)(kFineIds - 1)) << 4) + sub2;
+}
+
+// SUB 1: a pixel of a wide cell on the window `win` of its sub-cell in LDS, as resolve_wide does it on a flat list: false -- nothing
+// written -- at a tie among the three nearest or exact equality in the decision.
+template <int MODE>
+__device__ __forceinline__ bool resolve_window(const uint32_t x, const LeanThr &th, const int sh, const uint8_t *s_bytes, const uint32_t win,
+                                               const uint32_t pair_at, const int neg2, uint32_t &c)
+{
+    const uint4 ca = *reinterpret_cast<const uint4 *>(s_bytes + (win << 4));
+    const uint32_t pb = pair_at + (win << 3);
+    const uint2 cb = *reinterpret_cast<const uint2 *>(s_bytes + pb);
+    int m0, m1, m2;
+    cand6(x, ca, cb.x, cb.y, neg2, m0, m1, m2);
+    const int a0 = m0 >> kLocalBits, a1 = m1 >> kLocalBits, a2 = m2 >> kLocalBits;
+    if (a0 == a1 || a1 == a2) return false;
+    const int xx = (int)__builtin_amdgcn_udot4(x, x, 0u, false);
+    const uint32_t d0 = (uint32_t)(a0 + xx);
+    const uint32_t S = d0 + (uint32_t)a1 + (uint32_t)xx;
+    bool eq;
+    const bool nearest = lean_decide<MODE>(d0, S, th, sh, eq);
+    if (eq) return false;
+    const uint32_t pos = (uint32_t)(nearest ? m0 : m1) & 0xfcu;
+    c = *reinterpret_cast<const uint32_t *>(s_bytes + (pos < 16u ? (win << 4) + pos : pb + pos - 16u));
+    return true;
+}
 
 // The deferred path (see lean_pixel_full): the lowest deferred pixel of a queue entry, from its bytes in memory to its bytes
 // in memory; returns the entry without that pixel.  KEYS > 0: the flat lists of the wide cells are read where the table image has
-// them in global memory (pal.fine_tab, behind the quads), not from LDS.
-template <int MODE, int KEYS>
+// them in global memory (pal.fine_tab, behind the quads), not from LDS.  SUB 2: a tagged cell's pixel takes the flat list the tag
+// names where its sub-cell is still wide (row entry 0), and the index-ordered table like every other deferred pixel where it is not.
+template <int MODE, int KEYS, int SUB>
 __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                     unsigned long long *__restrict__ flags, const Geo &g, const PalDev &pal,
                                                     const ThrDev &thr, const uint32_t *s_words, const FineLds &at)
@@ -2210,7 +2251,21 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
     const uint32_t cell2 = fine_cell_offset(x);
     uint32_t c = 0;
     bool done = false, slow = false;
-    if (*reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2) == 0) {
+    if constexpr (SUB != 0) {
+        uint32_t tag = *reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2);
+        if constexpr (SUB == 1) {  // (staged as window 0: the tag is in the image)
+            const uint32_t off_src = (uint32_t)pal.fsub_win * kFineWindow + (uint32_t)pal.fsub_wide * kWideList;
+            tag = tag == 0u ? (uint32_t) reinterpret_cast<const uint16_t *>(pal.fsub_tab + off_src)[cell2 >> 1] : 0u;
+        }
+        if ((tag & kFineSubTag) != 0u) {
+            const uint32_t win = *reinterpret_cast<const uint16_t *>(s_bytes + fine_row_address(tag, x, at.ids_at));
+            if (win == 0u)
+                done = resolve_wide<MODE>(x, th, thr.sh, pal.fsub_tab + (uint32_t)pal.fsub_win * kFineQuad + (tag & (uint32_t)(kFineIds - 1)) * kWideList,
+                                          kWideList, c);
+            else if constexpr (SUB == 1)
+                done = resolve_window<MODE>(x, th, thr.sh, s_bytes, win, at.pair_at, g.neg2, c);
+        }
+    } else if (*reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2) == 0) {
         // a wide cell: its place in the ascending list of their numbers (padded to kFineIds with 0xffff) is its flat list's
         const uint16_t *ids = reinterpret_cast<const uint16_t *>(s_bytes + at.ids_at);
         const uint32_t cell = cell2 >> 1;
@@ -2236,7 +2291,7 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
     return rest ? ((entry & ~15u) | rest) : 0u;
 }
 
-template <int MODE, int KEYS>
+template <int MODE, int KEYS, int SUB = 0>
 __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                                     unsigned long long *__restrict__ flags, const Geo g,
                                                                     const PalDev pal, const ThrDev thr, const float sx, const float sy,
@@ -2245,6 +2300,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
     static_assert(MODE == 1, "integer thresholds in LDS only");
     (void)sx, (void)sy, (void)sc;
     static_assert(KEYS >= 0 && KEYS <= 2, "key levels: ordered_fine.h");
+    static_assert(SUB == 0 || ((SUB == 1 || SUB == 2) && KEYS == 1), "SUB levels: ordered_fine.h");
     __shared__ __align__(16) uint32_t smem[kLeanLdsWords];
     FineLds at;
     if constexpr (KEYS == 0) {
@@ -2262,20 +2318,21 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         // are two arrays of 16-byte records, not one of 32-byte records: a ds_read_b128 of 32-byte records at random windows uses
         // every other 16-byte slot of the bank row only, and half the slots means 1.45 x the conflict cycles.
         constexpr int kPairRec = KEYS == 2 ? 4 : 2;  // words
-        const int n_win = pal.fine_win;
-        const int pair_src = n_win * kFineQuad + pal.fine_wide * kWideList;  // words into pal.fine_tab
+        const uint32_t *tab = SUB == 0 ? pal.fine_tab : pal.fsub_tab;
+        const int n_win = SUB == 0 ? pal.fine_win : pal.fsub_win, n_wide = SUB == 0 ? pal.fine_wide : pal.fsub_wide;
+        const int pair_src = n_win * kFineQuad + n_wide * kWideList;  // words into the image
         const int tail_src = pair_src + n_win * (kFineWindow - kFineQuad);
         at.wide_at = 0;
         at.norm_at = (uint32_t)n_win * (kFineQuad * 4);
         at.pair_at = 2 * at.norm_at;
         at.off_at = at.pair_at + (uint32_t)n_win * (kPairRec * 4);
         for (int wi = threadIdx.x; wi < n_win; wi += kCellBlock) {
-            const uint4 c = *reinterpret_cast<const uint4 *>(&pal.fine_tab[wi * kFineQuad]);
+            const uint4 c = *reinterpret_cast<const uint4 *>(&tab[wi * kFineQuad]);
             *reinterpret_cast<uint4 *>(&smem[wi * 4]) = c;
             *reinterpret_cast<uint4 *>(&smem[n_win * 4 + wi * 4]) =
                 make_uint4((__builtin_amdgcn_udot4(c.x, c.x, 0u, false) << kLocalBits), (__builtin_amdgcn_udot4(c.y, c.y, 0u, false) << kLocalBits) + 4u,
                            (__builtin_amdgcn_udot4(c.z, c.z, 0u, false) << kLocalBits) + 8u, (__builtin_amdgcn_udot4(c.w, c.w, 0u, false) << kLocalBits) + 12u);
-            const uint2 b = *reinterpret_cast<const uint2 *>(&pal.fine_tab[pair_src + wi * 2]);
+            const uint2 b = *reinterpret_cast<const uint2 *>(&tab[pair_src + wi * 2]);
             if constexpr (KEYS == 2)
                 *reinterpret_cast<uint4 *>(&smem[n_win * 8 + wi * 4]) =
                     make_uint4(b.x, b.y, (__builtin_amdgcn_udot4(b.x, b.x, 0u, false) << kLocalBits) + 16u,
@@ -2285,11 +2342,18 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         }
         // (two words at a time: source and destination start at an even word)
         uint32_t *s_tail = smem + at.off_at / 4;
-        for (int i = threadIdx.x * 2; i < (kFineCells + kFineIds) / 2; i += kCellBlock * 2)
-            *reinterpret_cast<uint2 *>(&s_tail[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[tail_src + i]);
+        const int tail_words = SUB == 0 ? (kFineCells + kFineIds) / 2 : kFineCells / 2 + n_wide * 4;  // off, then ids or rows
+        for (int i = threadIdx.x * 2; i < tail_words; i += kCellBlock * 2) {
+            uint2 v = *reinterpret_cast<const uint2 *>(&tab[tail_src + i]);
+            if (SUB == 1 && i < kFineCells / 2) {  // a tag becomes window 0, the reserved one
+                v.x &= ~(((v.x & 0x80008000u) >> 15) * 0xffffu);
+                v.y &= ~(((v.y & 0x80008000u) >> 15) * 0xffffu);
+            }
+            *reinterpret_cast<uint2 *>(&s_tail[i]) = v;
+        }
     }
     at.ids_at = at.off_at + kFineCells * 2;
-    at.thr_at = at.ids_at + kFineIds * 2;
+    at.thr_at = at.ids_at + (SUB == 0 ? (uint32_t)kFineIds * 2 : (uint32_t)pal.fsub_wide * 16);
     {
         const int n = thr.th_h * thr.tw_pad;
         const int thr_word = KEYS == 0 ? pal.fine_words : (int)(at.thr_at / 4);  // (the same place at level 0)
@@ -2313,7 +2377,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         qcount -= n;
         __threadfence_block();  // the group stores that are about to be overwritten
         uint32_t rest = 0u;
-        if (lane < n) rest = fine_pixel_full<MODE, KEYS>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
+        if (lane < n) rest = fine_pixel_full<MODE, KEYS, SUB>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
         queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
     };
 
@@ -2328,8 +2392,18 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         const uint32_t gidx1 = gidx0 + gridDim.x * kCellBlock;
         if (tile + gridDim.x < n_tiles && gidx1 < n_full) wnn = in3[gidx1];
     }
+    // SUB 2: the windows of the sub-cells in place of the tags, one branch per pixel slot (a wave has a tagged lane in a given
+    // slot about every other time; a test over all four slots is taken by nearly every wave)
+    auto sub_windows = [&](const uint32_t xq[4], uint32_t win[4]) {
+        if constexpr (SUB == 2) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if ((win[q] & kFineSubTag) != 0u) win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + fine_row_address(win[q], xq[q], at.ids_at));
+        }
+    };
     unpack4(wn, xn);
     windows(xn, winn);
+    sub_windows(xn, winn);
     // (classes of the wave tiles: see ordered_lean_kernel)
     const bool use_cls = thr.has_cls != 0;
     uint32_t cls_word = 0, cls_shift = 0;  // wave-uniform
@@ -2450,6 +2524,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
 #pragma unroll
             for (int q = 0; q < 4; ++q) rare[q] = gidx * 4u + (uint32_t)q < g.n_px;  // the partial last group
         }
+        sub_windows(xn, winn);  // the next tile's: their tags arrived during the body
         // one queue entry per group with deferred pixels: group << 4 | which of its four
         const uint32_t rmask = (rare[0] ? 1u : 0u) | (rare[1] ? 2u : 0u) | (rare[2] ? 4u : 0u) | (rare[3] ? 8u : 0u);
         const unsigned long long rb = __ballot(rmask != 0u);
@@ -3182,14 +3257,15 @@ int num_cus()
 // experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel of every launch on stderr (tests that must know which
 // kernel a case reached): the family, then the template arguments and the table of the plan and the fix-up pass's queue; the
 // product library compiles to nothing here
-// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine keys=<level>"
-static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine, int keys)
+// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine keys=<level>
+// sub=<level>"
+static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine, int keys, int sub)
 {
 #ifdef DP_EXPERIMENTS
     if (std::getenv("DP_ORDERED_TRACE")) {
         constexpr const char *tables[] = {"plain8", "plain4", "warped"};
-        char keys_s[16] = "";
-        if (fine) snprintf(keys_s, sizeof(keys_s), " keys=%d", keys);
+        char keys_s[32] = "";
+        if (fine) snprintf(keys_s, sizeof(keys_s), " keys=%d sub=%d", keys, sub);
         fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s%s\n",
                 family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
                 p.fix_big_queue ? 1 : 0, fine ? "fine" : family_name(p.family), keys_s);
@@ -3199,6 +3275,7 @@ static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine, int
     (void)aligned;
     (void)fine;
     (void)keys;
+    (void)sub;
 #endif
 }
 
@@ -3253,9 +3330,15 @@ TileKernel tile_kernel(const OrderedPlan &p)
 }
 
 // the fine kernel at a key level (ordered_fine.h: fine_keys_level, kFineKeysShipped: level 2 is an instance of the experiments
-// build only, the A/B partner that showed it slower than level 1)
-TileKernel fine_kernel(const int keys)
+// build only, the A/B partner that showed it slower than level 1) and a SUB level (fine_sub_level, kFineSubShipped)
+TileKernel fine_kernel(const int keys, const int sub)
 {
+    if (sub == 2) return keys == 1 ? ordered_fine_kernel<1, 1, 2> : nullptr;
+#ifdef DP_EXPERIMENTS
+    if (sub == 1) return keys == 1 ? ordered_fine_kernel<1, 1, 1> : nullptr;
+#else
+    if (sub == 1) return nullptr;
+#endif
     switch (keys) {
     case 0: return ordered_fine_kernel<1, 0>;
     case 1: return ordered_fine_kernel<1, 1>;
@@ -3354,14 +3437,24 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         const bool brute = plan.family == kFamBrute;
         // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where its table exists and fits
         const FineFacts fine_facts{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, thr.th_h * thr.tw_pad * 4};
-        const bool fine = fine_replaces(plan, fine_facts) && !exp_env("DP_NO_FINE_KERNEL");
+        const bool fine_plain = fine_replaces(plan, fine_facts) && !exp_env("DP_NO_FINE_KERNEL");
         // ... at the highest key level whose LDS layout fits, up to the one that measured fastest (experiments:
         // DP_FINE_KEYS_MAX=0|1|2 in place of that cap)
         int keys_cap = kFineKeysShipped;
         if (const char *cap = exp_env("DP_FINE_KEYS_MAX")) keys_cap = std::min(2, std::max(0, std::atoi(cap)));
-        const int fine_keys = fine ? std::min(fine_keys_level(fine_facts), keys_cap) : 0;
+        // ... and on the two-level table where the palette has one and it fits at key level 1 (experiments: DP_FINE_SUB_MAX=0|1|2
+        // in place of kFineSubShipped).  A palette of the product library that has the two-level table has the other one only
+        // once a call needed it (host.cpp: ensure_fine_table).
+        int sub_cap = kFineSubShipped;
+        if (const char *cap = exp_env("DP_FINE_SUB_MAX")) sub_cap = std::min(2, std::max(0, std::atoi(cap)));
+        const bool sub_only = pal.fine_tab == nullptr && pal.fsub_tab != nullptr && fine_plan_ok(plan) && !exp_env("DP_NO_FINE_KERNEL");
+        const int keys_plain = fine_plain ? std::min(fine_keys_level(fine_facts), keys_cap) : (sub_only ? std::min(1, keys_cap) : 0);
+        const FineSubFacts sub_facts{pal.fsub_tab != nullptr && (fine_plain || sub_only), pal.fsub_win, pal.fsub_wide, fine_facts.thr_bytes, keys_plain, sub_cap};
+        const int fine_sub = fine_sub_level(sub_facts);
+        const bool fine = fine_plain || fine_sub != 0;
+        const int fine_keys = fine ? keys_plain : 0;
         const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
-        const TileKernel tile_k = brute ? nullptr : (fine ? fine_kernel(fine_keys) : tile_kernel(plan));
+        const TileKernel tile_k = brute ? nullptr : (fine ? fine_kernel(fine_keys, fine_sub) : tile_kernel(plan));
         const FixKernel fix_k = fix_kernel(plan);
         if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
             set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
@@ -3390,7 +3483,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_plan(plan, g.aligned, fine, fine_keys);
+        trace_plan(plan, g.aligned, fine, fine_keys, fine_sub);
         prof_mid(pm, s);
         hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);

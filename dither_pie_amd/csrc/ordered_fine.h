@@ -63,4 +63,54 @@ inline int fine_keys_level(const FineFacts &f)
 // exists in the experiments build only (DP_FINE_KEYS_MAX=2).
 constexpr int kFineKeysShipped = 1;
 
+// The two-level table (host_logic.h: fine_pack_sub; ordered.hip: ordered_fine_kernel<MODE, 1, SUB>).  A wide cell's entry of `off` is
+// a tag plus its rank among the wide cells, and a row of eight window numbers serves its 4-wide sub-cells, so that only the pixels
+// of the few sub-cells that are still wide leave the main path.  Key level 1 only.  LDS:
+//   quads A [n_win x 16 B] | their norms [n_win x 16 B] | pairs B [n_win x 8 B] | window or tag of every cell [32768 x 2 B] | rows
+//   [n_wide x 16 B] | integer thresholds
+// (the sorted cell numbers of the wide cells are not staged: the tag is the rank), and the image in global memory, which also holds
+// the flat lists, is  A | flat lists [n_wide x 64 B] | B | off | rows.
+constexpr int64_t fine_sub_bytes(const int n_win, const int n_wide)
+{
+    return (int64_t)n_win * 40 + kFineCells * 2 + (int64_t)n_wide * 16;
+}
+constexpr int64_t fine_sub_image_bytes(const int n_win, const int n_wide)
+{
+    return (int64_t)n_win * (kFineWindow * 4) + (int64_t)n_wide * (kWideList * 4 + 16) + kFineCells * 2;
+}
+// what the builder asks fine_pack_sub to stay within: the thresholds of a 16 x 16 matrix beside the table as in fine_table_fits, and
+// the image within the table's place in the accelerator's blob.  All or nothing: a palette whose joint pack does not fit gets no
+// two-level table and keeps what fine_pack gives it.
+constexpr bool fine_sub_fits(const int n_win, const int n_wide)
+{
+    return n_wide <= kFineIds && fine_sub_bytes(n_win, n_wide) + 16 * 19 * 4 <= kLeanTabBytes && fine_sub_image_bytes(n_win, n_wide) <= kLeanTabBytes;
+}
+
+struct FineSubFacts {  // 32-bit members: the record format of the test harness (`finesublevel`); FineFacts stays what it is
+    int32_t present;    // the palette has a two-level table
+    int32_t n_win, n_wide;
+    int32_t thr_bytes;
+    int32_t keys;       // the key level the call runs at (after any cap): the SUB instances exist at level 1 only
+    int32_t cap;        // the highest SUB level allowed (kFineSubShipped, or DP_FINE_SUB_MAX in the experiments build)
+};
+// The SUB level of a call that fine_replaces has accepted (or would, given today's table): 0 is today's kernel on today's table.
+//   1: the main loop is today's (a tag is staged as window 0); the deferred path ranks a wide cell's pixel on its sub-cell's window
+//      in LDS.  The cheaper partner of the A/B: an instance of the experiments build only.
+//   2: the main loop replaces a tagged window number by the row's entry for the pixel's sub-cell.
+inline int fine_sub_level(const FineSubFacts &f)
+{
+    if (f.present == 0 || f.keys != 1 || f.cap < 1 || f.n_wide > kFineIds) return 0;
+    return fine_sub_bytes(f.n_win, f.n_wide) + (int64_t)f.thr_bytes <= kLeanTabBytes ? (f.cap < 2 ? 1 : 2) : 0;
+}
+// whether the plan is one the fine kernels take over at all (the first half of fine_replaces)
+inline bool fine_plan_ok(const OrderedPlan &p)
+{
+    return p.family == kFamLean && p.mode == 1 && p.bw == 8 && p.table == kTabPlain8 && !p.adapt && !p.warp && !p.half;
+}
+
+// The highest SUB level the library launches by itself.  Level 2 measured 6-7 % above today's kernel on the headline, every run
+// above every run of the parent; level 1 measured exactly today's time -- it makes a wide pixel's drain cheaper, not rarer -- and
+// exists in the experiments build only (DP_FINE_SUB_MAX=1; DESIGN 4.1, profiles/experiments/fine_sub_levels.md).
+constexpr int kFineSubShipped = 2;
+
 }  // namespace dp
