@@ -330,6 +330,14 @@ static int ensure_ed_ext(const dp_palette *pal_c)
     return DP_OK;
 }
 
+// whether ensure_fine_table still has a pack to do for a call with these thresholds: the first one, or today's table beside a
+// two-level table that leaves the thresholds no room (asked before the lock in dp_ordered_u8 and again under it)
+static bool fine_pack_due(const dp_palette *p, const int thr_bytes)
+{
+    return p->fine_pending.load(std::memory_order_relaxed) ||
+           (p->fine_plain_pending.load(std::memory_order_relaxed) && thr_bytes > p->fine_sub_room.load(std::memory_order_relaxed));
+}
+
 // The fine table of ordered_fine_kernel: packed (4 ms at 256 colours) at the first matrix-mode call with integer thresholds after
 // the accelerator was built, so that nearest-only, IGN and diffusion users never pay for it and the accelerator's build stays
 // what it was.  Not inside a stream capture: the upload is a copy.
@@ -340,8 +348,8 @@ static int ensure_fine_table(const dp_palette *pal_c, hipStream_t s, const int t
 {
     dp_palette *p = const_cast<dp_palette *>(pal_c);
     std::lock_guard<std::mutex> lock(p->build_mu);
+    if (!fine_pack_due(p, thr_bytes)) return DP_OK;
     const bool first = p->fine_pending.load();
-    if (!first && !(p->fine_plain_pending.load() && thr_bytes > p->fine_sub_room.load())) return DP_OK;
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return DP_OK;
     dp::PalDev d = snapshot(p);
@@ -352,7 +360,7 @@ static int ensure_fine_table(const dp_palette *pal_c, hipStream_t s, const int t
             const int rc = build_fine(d, p->p4_host, p->fine_masks, p->fine_dev, true);
             if (rc != DP_OK) return rc;
         }
-        const int room = d.fsub_tab ? dp::kLeanTabBytes - (int)dp::fine_sub_bytes(d.fsub_win, d.fsub_wide) : -1;
+        const int room = d.fsub_tab ? (int)dp::fine_sub_room(d.fsub_win, d.fsub_wide) : -1;
         plain = dp::kExperiments || thr_bytes > room;
         if (!plain) {
             p->fine_sub_room = room;
@@ -660,9 +668,7 @@ int dp_ordered_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
         return DP_EWORKSPACE;
     }
     const int fine_thr_bytes = mode == DP_MODE_MATRIX && thr->dev.mpad ? thr->dev.th_h * thr->dev.tw_pad * 4 : 0;
-    if (mode == DP_MODE_MATRIX && thr->dev.mpad &&
-        (pal->fine_pending.load(std::memory_order_relaxed) ||
-         (pal->fine_plain_pending.load(std::memory_order_relaxed) && fine_thr_bytes > pal->fine_sub_room.load(std::memory_order_relaxed)))) {
+    if (mode == DP_MODE_MATRIX && thr->dev.mpad && fine_pack_due(pal, fine_thr_bytes)) {
         const int rc = ensure_fine_table(pal, (hipStream_t)stream, fine_thr_bytes);
         if (rc != DP_OK) return rc;
     }

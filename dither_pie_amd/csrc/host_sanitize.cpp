@@ -49,6 +49,9 @@
 //                                     (uint32) quads, pairs, lists as colours and the image, for tests/test_ordered_fine_sub_cpu.py
 //   host_xxx finesublevel <cases.bin> <n>   the SUB level of a call (ordered_fine.h: fine_sub_level): n records of one FineSubFacts;
 //                                     prints one level per line
+//   host_xxx finechoice <cases.bin> <n>   the fine kernel of a call (ordered_fine.h: choose_fine after plan_ordered): n records of one
+//                                     OrderedFacts, one OrderedSwitches, one FineTables and one FineSwitches; prints the plan's family,
+//                                     fine, keys, sub, and whether the product and the experiments build have that instance (fine_instance)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -884,6 +887,34 @@ static int run_fineplan(const char *path, const int n_cases)
     return 0;
 }
 
+static int run_finechoice(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        OrderedFacts facts;
+        OrderedSwitches sw;
+        FineTables ft;
+        FineSwitches fsw;
+        if (fread(&facts, sizeof(facts), 1, f) != 1 || fread(&sw, sizeof(sw), 1, f) != 1 || fread(&ft, sizeof(ft), 1, f) != 1 ||
+            fread(&fsw, sizeof(fsw), 1, f) != 1 || facts.hw < 1 || facts.w < 1 || facts.n_cus < 1 || ft.n_win < 0 || ft.n_wide < 0 ||
+            ft.sub_win < 0 || ft.sub_wide < 0 || ft.thr_bytes < 0) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            fclose(f);
+            return 2;
+        }
+        const OrderedPlan p = plan_ordered(facts, sw);
+        const FineChoice fc = choose_fine(p, ft, fsw);
+        printf("choice %d %s %d %d %d %d %d\n", c, family_name(p.family), fc.fine, fc.keys, fc.sub, (int)fine_instance(fc.keys, fc.sub, false),
+               (int)fine_instance(fc.keys, fc.sub, true));
+    }
+    fclose(f);
+    return 0;
+}
+
 static int run_finekeys(const char *path, const int n_cases)
 {
     FILE *f = fopen(path, "rb");
@@ -1114,7 +1145,7 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1131,6 +1162,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finekeys") return run_finekeys(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finesub") return argc > 4 ? run_finesub(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "finesublevel") return run_finesublevel(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "finechoice") return run_finechoice(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));

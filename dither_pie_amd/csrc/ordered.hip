@@ -12,7 +12,8 @@
 // tests/test_ordered_plan_cpu.py checks the decision without a GPU -- and tile_kernel / brute_kernel / fix_kernel at the
 // end of this file map a plan to one of the instantiations the library ships.  One refinement comes after the plan: where the
 // palette has a fine table and it fits, ordered_fine_kernel runs in place of the lean kernel on plain 8-entry blocks with integer
-// thresholds (ordered_fine.h: fine_replaces; tests/test_ordered_fine_cpu.py).
+// thresholds, at the key level and on the table that choose_fine picks (ordered_fine.h; tests/test_ordered_fine_choice_cpu.py).
+// The hand-scheduled candidate networks (cand8 ... cand6k) are in ordered_cand.hip.h.
 // Pixels whose result depends on scipy's visiting order in a way no table expresses, and near ties of the
 // float path, only set a flag bit; fixup_kernel compacts the flagged pixels per workgroup into LDS and
 // resolves them through the scipy-order KD-tree emulation (tree_query) and the literal float64 chain.
@@ -22,6 +23,7 @@
 #include "ordered_plan.h"
 #include "ordered_fine.h"
 #include "tree_query.hip.h"
+#include "ordered_cand.hip.h"
 
 namespace dp {
 
@@ -320,132 +322,6 @@ __global__ __launch_bounds__(kBlock) void ordered_int_kernel(const uint8_t *__re
 // inline; only tie code 3 and overflowing sub-cells are flagged for the fix-up pass.
 // ---------------------------------------------------------------------------------------------
 
-// Keys of the 8 candidates of one block and the three smallest of them.
-//   key = ((|p|^2 - 2 x.p) << 8) | (4*idx)      (4*idx = byte offset of the candidate inside its block)
-// Hand scheduled: hipcc neither fuses the shift/add/multiply into v_lshl_add + v_mad_i32_i24 nor keeps
-// med3 for the running top-3, and it has to pad DOT results with s_nop; here all eight v_dot4 pairs are
-// issued first (a DOT result must not be read for 3 issue slots), then 2 ops per key, then the three
-// smallest: sort the first three (min3/med3/max3), insert the other five (3 ops each).  `neg2` = -512 must sit in an SGPR (v_mad_i32_i24 takes no literal).
-__device__ __forceinline__ void cand8(const uint32_t x, const uint4 ca, const uint4 cb, const int neg2, int &m0,
-                                      int &m1, int &m2)
-{
-    int n0, n1, n2, n3, n4, n5, n6, n7, p0, p1, p2, p3, p4, p5, p6, p7;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[n6], %[c6], %[c6], 0\n\t"
-        "v_dot4_u32_u8 %[p6], %[x], %[c6], 0\n\t"
-        "v_dot4_u32_u8 %[n7], %[c7], %[c7], 0\n\t"
-        "v_dot4_u32_u8 %[p7], %[x], %[c7], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
-        "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
-        "v_lshl_add_u32 %[n6], %[n6], 8, 24\n\t"
-        "v_lshl_add_u32 %[n7], %[n7], 8, 28\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
-        "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
-        "v_mad_i32_i24 %[n6], %[p6], %[ng], %[n6]\n\t"
-        "v_mad_i32_i24 %[n7], %[p7], %[ng], %[n7]\n\t"
-        // top-3 insertion network (m0 <= m1 <= m2)
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n6]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n6]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n6]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n7]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n7]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n7]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5),
-          [n6] "=&v"(n6), [n7] "=&v"(n7), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3),
-          [p4] "=&v"(p4), [p5] "=&v"(p5), [p6] "=&v"(p6), [p7] "=&v"(p7), [m0] "=&v"(m0), [m1] "=&v"(m1),
-          [m2] "=&v"(m2)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(cb.x),
-          [c5] "v"(cb.y), [c6] "v"(cb.z), [c7] "v"(cb.w), [ng] "s"(neg2));
-}
-
-// The same keys, the TWO smallest only (pixels that take their nearest entry whatever the second one is): 44 operations
-__device__ __forceinline__ void cand8n(const uint32_t x, const uint4 ca, const uint4 cb, const int neg2, int &m0, int &m1)
-{
-    int n0, n1, n2, n3, n4, n5, n6, n7, p0, p1, p2, p3, p4, p5, p6, p7;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[n6], %[c6], %[c6], 0\n\t"
-        "v_dot4_u32_u8 %[p6], %[x], %[c6], 0\n\t"
-        "v_dot4_u32_u8 %[n7], %[c7], %[c7], 0\n\t"
-        "v_dot4_u32_u8 %[p7], %[x], %[c7], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
-        "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
-        "v_lshl_add_u32 %[n6], %[n6], 8, 24\n\t"
-        "v_lshl_add_u32 %[n7], %[n7], 8, 28\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
-        "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
-        "v_mad_i32_i24 %[n6], %[p6], %[ng], %[n6]\n\t"
-        "v_mad_i32_i24 %[n7], %[p7], %[ng], %[n7]\n\t"
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n6]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n6]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n7]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n7]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5),
-          [n6] "=&v"(n6), [n7] "=&v"(n7), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3),
-          [p4] "=&v"(p4), [p5] "=&v"(p5), [p6] "=&v"(p6), [p7] "=&v"(p7), [m0] "=&v"(m0), [m1] "=&v"(m1)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(cb.x),
-          [c5] "v"(cb.y), [c6] "v"(cb.z), [c7] "v"(cb.w), [ng] "s"(neg2));
-}
-
 // Colours whose tie outcome no code expresses: binary search of the palette's exception list.
 // Returns false when the colour is not listed (or the list overflowed at build time).
 __device__ __forceinline__ bool find_exception(const PalDev &pal, const uint32_t x, uint32_t &pair, uint32_t &single)
@@ -479,38 +355,6 @@ __device__ __forceinline__ uint32_t cell_offset4(const uint32_t x)
     const uint32_t t = x & 0xf0f0f0u;
     const uint32_t y = t | (t << 12);
     return (y >> 12) & 0xfff0u;
-}
-
-// Keys of the 4 candidates of a small block and the three smallest (see cand8)
-__device__ __forceinline__ void cand4(const uint32_t x, const uint4 ca, const int neg2, int &m0, int &m1, int &m2)
-{
-    int n0, n1, n2, n3, p0, p1, p2, p3;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2),
-          [p3] "=&v"(p3), [m0] "=&v"(m0), [m1] "=&v"(m1), [m2] "=&v"(m2)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [ng] "s"(neg2));
 }
 
 template <int MODE>
@@ -1264,66 +1108,6 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_lean_kernel(
 // candidates: fix-up pass).
 // ---------------------------------------------------------------------------------------------
 
-// keys of eight palette records and the three smallest (see cand8); r_k = {colour, |p|^2 << 8 | index}
-__device__ __forceinline__ void cand8r(const uint32_t x, const uint2 r0, const uint2 r1, const uint2 r2, const uint2 r3,
-                                       const uint2 r4, const uint2 r5, const uint2 r6, const uint2 r7, const int neg2, int &m0,
-                                       int &m1, int &m2)
-{
-    int n0, n1, n2, n3, n4, n5, n6, n7;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[x], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[n4], %[x], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[n5], %[x], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[n6], %[x], %[c6], 0\n\t"
-        "v_dot4_u32_u8 %[n7], %[x], %[c7], 0\n\t"
-        "v_mad_i32_i24 %[n0], %[n0], %[ng], %[k0]\n\t"
-        "v_mad_i32_i24 %[n1], %[n1], %[ng], %[k1]\n\t"
-        "v_mad_i32_i24 %[n2], %[n2], %[ng], %[k2]\n\t"
-        "v_mad_i32_i24 %[n3], %[n3], %[ng], %[k3]\n\t"
-        "v_mad_i32_i24 %[n4], %[n4], %[ng], %[k4]\n\t"
-        "v_mad_i32_i24 %[n5], %[n5], %[ng], %[k5]\n\t"
-        "v_mad_i32_i24 %[n6], %[n6], %[ng], %[k6]\n\t"
-        "v_mad_i32_i24 %[n7], %[n7], %[ng], %[k7]\n\t"
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n6]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n6]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n6]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n7]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n7]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n7]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5),
-          [n6] "=&v"(n6), [n7] "=&v"(n7), [m0] "=&v"(m0), [m1] "=&v"(m1), [m2] "=&v"(m2)
-        : [x] "v"(x), [c0] "v"(r0.x), [c1] "v"(r1.x), [c2] "v"(r2.x), [c3] "v"(r3.x), [c4] "v"(r4.x), [c5] "v"(r5.x),
-          [c6] "v"(r6.x), [c7] "v"(r7.x), [k0] "v"(r0.y), [k1] "v"(r1.y), [k2] "v"(r2.y), [k3] "v"(r3.y), [k4] "v"(r4.y),
-          [k5] "v"(r5.y), [k6] "v"(r6.y), [k7] "v"(r7.y), [ng] "s"(neg2));
-}
-
-// byte k of `word` times 8 (the LDS address of palette record number byte k): one SDWA shift; `three` holds 3
-template <int BYTE>
-__device__ __forceinline__ uint32_t rec_addr(const uint32_t word, const uint32_t three)
-{
-    uint32_t a;
-    if (BYTE == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(a) : "v"(three), "v"(word));
-    else if (BYTE == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(a) : "v"(three), "v"(word));
-    else if (BYTE == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(a) : "v"(three), "v"(word));
-    else asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(a) : "v"(three), "v"(word));
-    return a;
-}
-
 // Which of the three nearest candidates (0, 1, 2 by (distance, index)) is written: two bits per (tie code, decision).
 // k=2 codes (accel.hip): 0 (c0,c1)  1 (c1,c0)  2 (c0,c2)  3 (c2,c0)  4 (c1,c2)  5 (c2,c1); field 2*code + (nearest ? 0 : 1)
 constexpr uint32_t kPickTable = (0u << 0) | (1u << 2) | (1u << 4) | (0u << 6) | (0u << 8) | (2u << 10) | (2u << 12) | (0u << 14) |
@@ -1577,81 +1361,6 @@ __global__ __launch_bounds__(kCellBlock, HALF ? 8 : 4) void ordered_compact_kern
 // MODE as in ordered_lean_kernel.  BW = 8 or 4 (tables of small palettes: every slot is read either way).
 // ---------------------------------------------------------------------------------------------
 [[maybe_unused]] constexpr int kNearSlots8 = 6;
-
-// Keys of the first six entries of a block and the two smallest (see cand8)
-__device__ __forceinline__ void cand6n(const uint32_t x, const uint4 ca, const uint32_t c4, const uint32_t c5, const int neg2,
-                                       int &m0, int &m1)
-{
-    int n0, n1, n2, n3, n4, n5, p0, p1, p2, p3, p4, p5;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
-        "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
-        "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
-        // the two smallest (m0 <= m1)
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
-          [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5),
-          [ng] "s"(neg2));
-}
-
-// The same for the four entries of a small block
-__device__ __forceinline__ void cand4n(const uint32_t x, const uint4 ca, const int neg2, int &m0, int &m1)
-{
-    int n0, n1, n2, n3, p0, p1, p2, p3;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2),
-          [p3] "=&v"(p3), [m0] "=&v"(m0), [m1] "=&v"(m1)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [ng] "s"(neg2));
-}
 
 // the leaf of a colour, every block read from the (index-ordered) table in global memory
 template <int BW>
@@ -2035,160 +1744,6 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 // sub-cell's window in LDS (resolve_window) instead of the sixteen entries of the global list.  LDS:
 //   quads A | norms of A | pairs B | window or tag of every cell | rows [n_wide x 8 u16] | thresholds
 // ---------------------------------------------------------------------------------------------
-
-// Keys of the six candidates of a window and the three smallest (see cand8)
-__device__ __forceinline__ void cand6(const uint32_t x, const uint4 ca, const uint32_t c4, const uint32_t c5, const int neg2, int &m0,
-                                      int &m1, int &m2)
-{
-    int n0, n1, n2, n3, n4, n5, p0, p1, p2, p3, p4, p5;
-    asm volatile(
-        "v_dot4_u32_u8 %[n0], %[c0], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[n1], %[c1], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[n2], %[c2], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[n3], %[c3], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-        "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
-        "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-        "v_lshl_add_u32 %[n0], %[n0], 8, 0\n\t"
-        "v_lshl_add_u32 %[n1], %[n1], 8, 4\n\t"
-        "v_lshl_add_u32 %[n2], %[n2], 8, 8\n\t"
-        "v_lshl_add_u32 %[n3], %[n3], 8, 12\n\t"
-        "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
-        "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[n0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[n1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[n2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[n3]\n\t"
-        "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
-        "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
-        // top-3 insertion network (m0 <= m1 <= m2)
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-        "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
-          [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
-          [m2] "=&v"(m2)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5),
-          [ng] "s"(neg2));
-}
-
-// Key levels 1 and 2 (ordered_fine.h: fine_keys_level): the part of a key that does not depend on the pixel, N_j = (|c_j|^2 << 8)
-// + 4 j, is staged in LDS next to the colour, and a key is two instructions -- the same value as cand4n / cand6 compute with four.
-// cand4k: keys of the quad A from its norms na, and the two smallest
-__device__ __forceinline__ void cand4k(const uint32_t x, const uint4 ca, const uint4 na, const int neg2, int &m0, int &m1)
-{
-    int n0, n1, n2, n3, p0, p1, p2, p3;
-    asm volatile(
-        "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-        "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-        "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-        "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-        "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
-        "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
-        "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
-        "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
-        "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-        "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-        "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-        : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [p0] "=&v"(p0), [p1] "=&v"(p1), [p2] "=&v"(p2),
-          [p3] "=&v"(p3), [m0] "=&v"(m0), [m1] "=&v"(m1)
-        : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [k0] "v"(na.x), [k1] "v"(na.y), [k2] "v"(na.z),
-          [k3] "v"(na.w), [ng] "s"(neg2));
-}
-
-// cand6k: keys of the six candidates of a window and the three smallest.  KEYS 1: the pair B comes as colours only (c4, c5; its two
-// keys take four instructions as in cand6); KEYS 2: with its norms k4, k5.
-template <int KEYS>
-__device__ __forceinline__ void cand6k(const uint32_t x, const uint4 ca, const uint4 na, const uint32_t c4, const uint32_t c5,
-                                       const uint32_t k4, const uint32_t k5, const int neg2, int &m0, int &m1, int &m2)
-{
-    int n0, n1, n2, n3, n4, n5, p0, p1, p2, p3, p4, p5;
-    if constexpr (KEYS == 1) {
-        (void)k4, (void)k5;
-        asm volatile(
-            "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-            "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-            "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-            "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-            "v_dot4_u32_u8 %[n4], %[c4], %[c4], 0\n\t"
-            "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-            "v_dot4_u32_u8 %[n5], %[c5], %[c5], 0\n\t"
-            "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-            "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
-            "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
-            "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
-            "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
-            "v_lshl_add_u32 %[n4], %[n4], 8, 16\n\t"
-            "v_lshl_add_u32 %[n5], %[n5], 8, 20\n\t"
-            "v_mad_i32_i24 %[n4], %[p4], %[ng], %[n4]\n\t"
-            "v_mad_i32_i24 %[n5], %[p5], %[ng], %[n5]\n\t"
-            // top-3 insertion network (m0 <= m1 <= m2)
-            "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-            "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-            "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-            : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
-              [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
-              [m2] "=&v"(m2)
-            : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5), [k0] "v"(na.x),
-              [k1] "v"(na.y), [k2] "v"(na.z), [k3] "v"(na.w), [ng] "s"(neg2));
-    } else {
-        asm volatile(
-            "v_dot4_u32_u8 %[p0], %[x], %[c0], 0\n\t"
-            "v_dot4_u32_u8 %[p1], %[x], %[c1], 0\n\t"
-            "v_dot4_u32_u8 %[p2], %[x], %[c2], 0\n\t"
-            "v_dot4_u32_u8 %[p3], %[x], %[c3], 0\n\t"
-            "v_dot4_u32_u8 %[p4], %[x], %[c4], 0\n\t"
-            "v_dot4_u32_u8 %[p5], %[x], %[c5], 0\n\t"
-            "v_mad_i32_i24 %[n0], %[p0], %[ng], %[k0]\n\t"
-            "v_mad_i32_i24 %[n1], %[p1], %[ng], %[k1]\n\t"
-            "v_mad_i32_i24 %[n2], %[p2], %[ng], %[k2]\n\t"
-            "v_mad_i32_i24 %[n3], %[p3], %[ng], %[k3]\n\t"
-            "v_mad_i32_i24 %[n4], %[p4], %[ng], %[k4]\n\t"
-            "v_mad_i32_i24 %[n5], %[p5], %[ng], %[k5]\n\t"
-            // top-3 insertion network (m0 <= m1 <= m2)
-            "v_min3_i32 %[m0], %[n0], %[n1], %[n2]\n\t"
-            "v_med3_i32 %[m1], %[n0], %[n1], %[n2]\n\t"
-            "v_max3_i32 %[m2], %[n0], %[n1], %[n2]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n3]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n3]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n3]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n4]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n4]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n4]\n\t"
-            "v_med3_i32 %[m2], %[m1], %[m2], %[n5]\n\t"
-            "v_med3_i32 %[m1], %[m0], %[m1], %[n5]\n\t"
-            "v_min_i32 %[m0], %[m0], %[n5]\n\t"
-            : [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [n4] "=&v"(n4), [n5] "=&v"(n5), [p0] "=&v"(p0),
-              [p1] "=&v"(p1), [p2] "=&v"(p2), [p3] "=&v"(p3), [p4] "=&v"(p4), [p5] "=&v"(p5), [m0] "=&v"(m0), [m1] "=&v"(m1),
-              [m2] "=&v"(m2)
-            : [x] "v"(x), [c0] "v"(ca.x), [c1] "v"(ca.y), [c2] "v"(ca.z), [c3] "v"(ca.w), [c4] "v"(c4), [c5] "v"(c5), [k0] "v"(na.x),
-              [k1] "v"(na.y), [k2] "v"(na.z), [k3] "v"(na.w), [k4] "v"(k4), [k5] "v"(k5), [ng] "s"(neg2));
-    }
-}
 
 // byte offset of the window number of x's cell: cell = r>>3 | (g>>3)<<5 | (b>>3)<<10 (host_logic.h: fine_cell), times 2
 __device__ __forceinline__ uint32_t fine_cell_offset(const uint32_t x)
@@ -3257,25 +2812,23 @@ int num_cus()
 // experiments build only: DP_ORDERED_TRACE=1 names the pass-1 kernel of every launch on stderr (tests that must know which
 // kernel a case reached): the family, then the template arguments and the table of the plan and the fix-up pass's queue; the
 // product library compiles to nothing here
-// `fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h); the line then ends in "kernel=fine keys=<level>
-// sub=<level>"
-static inline void trace_plan(const OrderedPlan &p, bool aligned, bool fine, int keys, int sub)
+// `fc.fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h: choose_fine); the line then ends in
+// "kernel=fine keys=<level> sub=<level>"
+static inline void trace_plan(const OrderedPlan &p, bool aligned, const FineChoice &fc)
 {
 #ifdef DP_EXPERIMENTS
     if (std::getenv("DP_ORDERED_TRACE")) {
         constexpr const char *tables[] = {"plain8", "plain4", "warped"};
         char keys_s[32] = "";
-        if (fine) snprintf(keys_s, sizeof(keys_s), " keys=%d sub=%d", keys, sub);
+        if (fc.fine) snprintf(keys_s, sizeof(keys_s), " keys=%d sub=%d", fc.keys, fc.sub);
         fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s%s\n",
                 family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
-                p.fix_big_queue ? 1 : 0, fine ? "fine" : family_name(p.family), keys_s);
+                p.fix_big_queue ? 1 : 0, fc.fine ? "fine" : family_name(p.family), keys_s);
     }
 #else
     (void)p;
     (void)aligned;
-    (void)fine;
-    (void)keys;
-    (void)sub;
+    (void)fc;
 #endif
 }
 
@@ -3330,23 +2883,22 @@ TileKernel tile_kernel(const OrderedPlan &p)
 }
 
 // the fine kernel at a key level (ordered_fine.h: fine_keys_level, kFineKeysShipped: level 2 is an instance of the experiments
-// build only, the A/B partner that showed it slower than level 1) and a SUB level (fine_sub_level, kFineSubShipped)
+// build only, the A/B partner that showed it slower than level 1) and a SUB level (fine_sub_level, kFineSubShipped): the instances
+// fine_instance (ordered_fine.h) lists for this build, no more and no fewer.  (The order in which the instances are named here is
+// the order of the kernels in the device code: renaming them in another order gives a different code object.)
 TileKernel fine_kernel(const int keys, const int sub)
 {
-    if (sub == 2) return keys == 1 ? ordered_fine_kernel<1, 1, 2> : nullptr;
+    if (!fine_instance(keys, sub, kExperiments)) return nullptr;
+    if (sub == 2) return ordered_fine_kernel<1, 1, 2>;
 #ifdef DP_EXPERIMENTS
-    if (sub == 1) return keys == 1 ? ordered_fine_kernel<1, 1, 1> : nullptr;
-#else
-    if (sub == 1) return nullptr;
+    if (sub == 1) return ordered_fine_kernel<1, 1, 1>;
 #endif
-    switch (keys) {
-    case 0: return ordered_fine_kernel<1, 0>;
-    case 1: return ordered_fine_kernel<1, 1>;
+    if (keys == 0) return ordered_fine_kernel<1, 0>;
+    if (keys == 1) return ordered_fine_kernel<1, 1>;
 #ifdef DP_EXPERIMENTS
-    case 2: return ordered_fine_kernel<1, 2>;
+    if (keys == 2) return ordered_fine_kernel<1, 2>;
 #endif
-    }
-    return nullptr;
+    return nullptr;  // (not reached: the predicate lists nothing else)
 }
 
 // (ordered_f64_kernel<1> is named but never planned: MODE 1 needs an integer palette)
@@ -3403,6 +2955,11 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
     sw.force_compact = exp_env("DP_FORCE_COMPACT") != nullptr;
     sw.no_compact_kernel = exp_env("DP_NO_COMPACT_KERNEL") != nullptr;
     sw.compact_no_half = exp_env("DP_COMPACT_NO_HALF") != nullptr;
+    // ... and of the fine kernel's (ordered_fine.h: choose_fine): the caps are the levels that measured fastest, DP_FINE_KEYS_MAX=0|1|2
+    // and DP_FINE_SUB_MAX=0|1|2 stand in their place
+    FineSwitches fsw{exp_env("DP_NO_FINE_KERNEL") != nullptr, kFineKeysShipped, kFineSubShipped};
+    if (const char *cap = exp_env("DP_FINE_KEYS_MAX")) fsw.keys_cap = std::min(2, std::max(0, std::atoi(cap)));
+    if (const char *cap = exp_env("DP_FINE_SUB_MAX")) fsw.sub_cap = std::min(2, std::max(0, std::atoi(cap)));
 
     const float sx = (float)((double)ign_seed * 0.37), sy = (float)((double)ign_seed * 0.73);
     const int64_t hw = (int64_t)h * w;
@@ -3435,26 +2992,11 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         g.adv_y = plan.adv_y;
         g.adv_x = plan.adv_x;
         const bool brute = plan.family == kFamBrute;
-        // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where its table exists and fits
-        const FineFacts fine_facts{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, thr.th_h * thr.tw_pad * 4};
-        const bool fine_plain = fine_replaces(plan, fine_facts) && !exp_env("DP_NO_FINE_KERNEL");
-        // ... at the highest key level whose LDS layout fits, up to the one that measured fastest (experiments:
-        // DP_FINE_KEYS_MAX=0|1|2 in place of that cap)
-        int keys_cap = kFineKeysShipped;
-        if (const char *cap = exp_env("DP_FINE_KEYS_MAX")) keys_cap = std::min(2, std::max(0, std::atoi(cap)));
-        // ... and on the two-level table where the palette has one and it fits at key level 1 (experiments: DP_FINE_SUB_MAX=0|1|2
-        // in place of kFineSubShipped).  A palette of the product library that has the two-level table has the other one only
-        // once a call needed it (host.cpp: ensure_fine_table).
-        int sub_cap = kFineSubShipped;
-        if (const char *cap = exp_env("DP_FINE_SUB_MAX")) sub_cap = std::min(2, std::max(0, std::atoi(cap)));
-        const bool sub_only = pal.fine_tab == nullptr && pal.fsub_tab != nullptr && fine_plan_ok(plan) && !exp_env("DP_NO_FINE_KERNEL");
-        const int keys_plain = fine_plain ? std::min(fine_keys_level(fine_facts), keys_cap) : (sub_only ? std::min(1, keys_cap) : 0);
-        const FineSubFacts sub_facts{pal.fsub_tab != nullptr && (fine_plain || sub_only), pal.fsub_win, pal.fsub_wide, fine_facts.thr_bytes, keys_plain, sub_cap};
-        const int fine_sub = fine_sub_level(sub_facts);
-        const bool fine = fine_plain || fine_sub != 0;
-        const int fine_keys = fine ? keys_plain : 0;
+        // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where a table of its exists and fits
+        const FineChoice fc = choose_fine(plan, FineTables{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, pal.fsub_tab != nullptr,
+                                                           pal.fsub_win, pal.fsub_wide, thr.th_h * thr.tw_pad * 4}, fsw);
         const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
-        const TileKernel tile_k = brute ? nullptr : (fine ? fine_kernel(fine_keys, fine_sub) : tile_kernel(plan));
+        const TileKernel tile_k = brute ? nullptr : (fc.fine ? fine_kernel(fc.keys, fc.sub) : tile_kernel(plan));
         const FixKernel fix_k = fix_kernel(plan);
         if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
             set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
@@ -3483,7 +3025,7 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_plan(plan, g.aligned, fine, fine_keys, fine_sub);
+        trace_plan(plan, g.aligned, fc);
         prof_mid(pm, s);
         hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
         prof_end(pm, s);

@@ -3,8 +3,9 @@
 // harness (host_sanitize.cpp, `fineplan`), where tests/test_ordered_fine_cpu.py compares it case by case with a Python
 // restatement.  plan_ordered, OrderedFacts and their record format are what they were: the fine kernel is a refinement of one
 // row of the plan -- the lean kernel on the plain 8-entry table with integer thresholds in LDS -- and takes that row's grid,
-// tile stride and fix-up pass unchanged.
+// tile stride and fix-up pass unchanged.  choose_fine at the end is what launch_ordered calls: which instance of the kernel, if any.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 
 #include "ordered_plan.h"
@@ -78,6 +79,12 @@ constexpr int64_t fine_sub_image_bytes(const int n_win, const int n_wide)
 {
     return (int64_t)n_win * (kFineWindow * 4) + (int64_t)n_wide * (kWideList * 4 + 16) + kFineCells * 2;
 }
+// the room beside the two-level table: the most threshold bytes a call may bring and still run on it (fine_sub_level; host.cpp
+// packs the other table for a call that brings more)
+constexpr int64_t fine_sub_room(const int n_win, const int n_wide)
+{
+    return kLeanTabBytes - fine_sub_bytes(n_win, n_wide);
+}
 // what the builder asks fine_pack_sub to stay within: the thresholds of a 16 x 16 matrix beside the table as in fine_table_fits, and
 // the image within the table's place in the accelerator's blob.  All or nothing: a palette whose joint pack does not fit gets no
 // two-level table and keeps what fine_pack gives it.
@@ -100,7 +107,7 @@ struct FineSubFacts {  // 32-bit members: the record format of the test harness 
 inline int fine_sub_level(const FineSubFacts &f)
 {
     if (f.present == 0 || f.keys != 1 || f.cap < 1 || f.n_wide > kFineIds) return 0;
-    return fine_sub_bytes(f.n_win, f.n_wide) + (int64_t)f.thr_bytes <= kLeanTabBytes ? (f.cap < 2 ? 1 : 2) : 0;
+    return (int64_t)f.thr_bytes <= fine_sub_room(f.n_win, f.n_wide) ? (f.cap < 2 ? 1 : 2) : 0;
 }
 // whether the plan is one the fine kernels take over at all (the first half of fine_replaces)
 inline bool fine_plan_ok(const OrderedPlan &p)
@@ -112,5 +119,44 @@ inline bool fine_plan_ok(const OrderedPlan &p)
 // above every run of the parent; level 1 measured exactly today's time -- it makes a wide pixel's drain cheaper, not rarer -- and
 // exists in the experiments build only (DP_FINE_SUB_MAX=1; DESIGN 4.1, profiles/experiments/fine_sub_levels.md).
 constexpr int kFineSubShipped = 2;
+
+// ---- the choice of a call: everything above put together, as pure as plan_ordered (host_sanitize.cpp `finechoice`;
+// tests/test_ordered_fine_choice_cpu.py) ------------------------------------------------------------------------------------
+struct FineTables {  // what the palette has and the call brings (32-bit members: also the record format of the test harness)
+    int32_t plain, n_win, n_wide;      // the fine table (fine_pack)
+    int32_t sub, sub_win, sub_wide;    // the two-level table (fine_pack_sub)
+    int32_t thr_bytes;                 // the padded integer thresholds: th_h * tw_pad * 4
+};
+struct FineSwitches {  // the product library: {0, kFineKeysShipped, kFineSubShipped}
+    int32_t no_fine;   // experiments: DP_NO_FINE_KERNEL
+    int32_t keys_cap;  // the highest key level allowed, 0..2 (experiments: DP_FINE_KEYS_MAX)
+    int32_t sub_cap;   // the highest SUB level allowed, 0..2 (experiments: DP_FINE_SUB_MAX)
+};
+struct FineChoice {
+    int32_t fine;       // ordered_fine_kernel<1, keys, sub> runs in place of the plan's kernel, on the plan's grid, tile stride and fix-up pass
+    int32_t keys, sub;  // (keys is 0 where fine is)
+};
+// The fine kernel takes over where its table exists and fits (fine_replaces), at the highest key level whose LDS layout fits up
+// to the cap, and on the two-level table where the palette has one and it fits at key level 1.  A palette of the product
+// library that has the two-level table has the other one only once a call needed it (host.cpp: ensure_fine_table): `sub_only`.
+inline FineChoice choose_fine(const OrderedPlan &p, const FineTables &t, const FineSwitches &sw)
+{
+    const FineFacts f{t.plain, t.n_win, t.n_wide, t.thr_bytes};
+    const bool plain = fine_replaces(p, f) && !sw.no_fine;
+    const bool sub_only = !t.plain && t.sub && fine_plan_ok(p) && !sw.no_fine;
+    const int keys = plain ? std::min(fine_keys_level(f), (int)sw.keys_cap) : (sub_only ? std::min(1, (int)sw.keys_cap) : 0);
+    const int sub = fine_sub_level({t.sub && (plain || sub_only), t.sub_win, t.sub_wide, t.thr_bytes, keys, sw.sub_cap});
+    const bool fine = plain || sub != 0;
+    return {fine, fine ? keys : 0, sub};
+}
+
+// The instances of ordered_fine_kernel<1, keys, sub> a build has (ordered.hip: fine_kernel follows this): every (keys, sub) that
+// choose_fine can give within the shipped caps, and in the experiments build within any caps.
+constexpr bool fine_instance(const int keys, const int sub, const bool experiments)
+{
+    if (sub == 2) return keys == 1;
+    if (sub == 1) return experiments && keys == 1;
+    return sub == 0 && (keys == 0 || keys == 1 || (experiments && keys == 2));
+}
 
 }  // namespace dp

@@ -22,8 +22,8 @@
 //                 workgroups per CU (HALF).  Crowded palettes (many split cells, or a table larger than LDS) take the
 //                 instantiation that adapts per wave (ADAPT).
 //                 (Its plainest row -- 8-entry blocks on plain cells, not adaptive, integer thresholds in LDS -- is served by
-//                 ordered_fine_kernel where the palette has a fine table: ordered_fine.h decides that after this plan, which
-//                 stays what it was.)
+//                 ordered_fine_kernel where the palette has a fine table: choose_fine (ordered_fine.h) decides that after this
+//                 plan, which stays what it was.)
 //     4. cell     the previous generation (inline rare paths, the whole plain 8-entry table in dynamic LDS): what is left
 //                 for buffers that are not dword-aligned, negative origins and thresholds without a padded copy.
 //   float (use_gamma) palette with a cell table, dword-aligned frames:

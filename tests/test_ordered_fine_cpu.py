@@ -143,14 +143,18 @@ def test_packer_refuses_a_crowded_palette(harness, tmp_path):
     assert t["ok"] == 0, t["line"]
 
 
+# the pieces the cases of the kernel's choice are built from (here and in tests/test_ordered_fine_choice_cpu.py)
+PLAIN8 = dict(cell_tab=1, tab_words=4096 * 8, tab_total=4096 * 8)
+BAYER8 = dict(m=1, mpad=1, fpad=1, th_h=8, th_w=8, tw_pad=11)
+BASE = dict(mode=ref.MATRIX, K=256, is_integer=1, n_inner=51, n_px=3 * 120 * 203, hw=120 * 203, w=203, y0=0, x0=0, aligned=1, cell_tab=0,
+            tab_words=0, tab_total=0, cell_tab4=0, tab4_words=0, warp_tab=0, warp_words=0, warp_total=0, warp_bw=0, warp_adapt=0, adapt=0,
+            cell_perm=0, cell_perm4=0, n_wide=0, n_wide4=0, comp_tab=0, comp_words=0, comp_warp=0, ftab=0, ftab_words=0, m=0, mpad=0,
+            fpad=0, th_h=1, th_w=1, tw_pad=0, n_cus=8)
+NO_SWITCH = dict.fromkeys(ref.SWITCH_FIELDS, 0)
+
+
 def test_choice_of_the_fine_kernel(harness, tmp_path):
-    plain8 = dict(cell_tab=1, tab_words=4096 * 8, tab_total=4096 * 8)
-    bayer8 = dict(m=1, mpad=1, fpad=1, th_h=8, th_w=8, tw_pad=11)
-    base = dict(mode=ref.MATRIX, K=256, is_integer=1, n_inner=51, n_px=3 * 120 * 203, hw=120 * 203, w=203, y0=0, x0=0, aligned=1, cell_tab=0,
-                tab_words=0, tab_total=0, cell_tab4=0, tab4_words=0, warp_tab=0, warp_words=0, warp_total=0, warp_bw=0, warp_adapt=0, adapt=0,
-                cell_perm=0, cell_perm4=0, n_wide=0, n_wide4=0, comp_tab=0, comp_words=0, comp_warp=0, ftab=0, ftab_words=0, m=0, mpad=0,
-                fpad=0, th_h=1, th_w=1, tw_pad=0, n_cus=8)
-    no_switch = dict.fromkeys(ref.SWITCH_FIELDS, 0)
+    plain8, bayer8, base, no_switch = PLAIN8, BAYER8, BASE, NO_SWITCH
     fine = dict(present=1, n_win=1793, n_wide=370)
     room = ref.K_LEAN_TAB_BYTES - fine_table_bytes(0, 370) - 8 * 11 * 4
     tables = (plain8, dict(plain8, cell_tab4=1, tab4_words=4096 * 4), dict(plain8, warp_tab=1, warp_bw=8, warp_words=33000, warp_total=33400),
