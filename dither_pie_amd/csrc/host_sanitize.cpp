@@ -52,6 +52,11 @@
 //   host_xxx finechoice <cases.bin> <n>   the fine kernel of a call (ordered_fine.h: choose_fine after plan_ordered): n records of one
 //                                     OrderedFacts, one OrderedSwitches, one FineTables and one FineSwitches; prints the plan's family,
 //                                     fine, keys, sub, and whether the product and the experiments build have that instance (fine_instance)
+//   host_xxx fineaddr <first> <n>     the address arithmetic of the fine kernel's main loop (ordered_fine.h) on the n colours from
+//                                     `first` on (0 16777216: all of them): fine_cell_offset against 2 * fine_cell, with and without a
+//                                     base and with garbage in bits 24-31; then, whatever the range, every rank and sub-cell:
+//                                     fine_stage_tag / fine_stage_tags2 / fine_tag_rank and fine_row_address against rows_at + 16 * rank
+//                                     + 2 * sub-cell on the 64 colours of the sub-cell; prints the counts and the number of mismatches
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -844,6 +849,43 @@ static int run_finesub(const char *path, const int K, const char *out_path)
     return bad ? 1 : 0;
 }
 
+static int run_fineaddr(const long first, const long n)
+{
+    if (first < 0 || n < 0 || first + n > (1L << 24)) {
+        fprintf(stderr, "fineaddr: colours within 0 .. 2^24\n");
+        return 2;
+    }
+    long bad_cell = 0, bad_row = 0, bad_tag = 0, rows = 0;
+    for (long i = first; i < first + n; ++i) {
+        const uint32_t x = (uint32_t)i;
+        const uint32_t want = 2u * (uint32_t)fine_cell((int)(x & 255u), (int)((x >> 8) & 255u), (int)(x >> 16));
+        bad_cell += fine_cell_offset(x) != want || fine_cell_offset(x, 73728u) != want + 73728u || fine_cell_offset(x | 0xa5000000u) != want;
+    }
+    const uint32_t rows_at[3] = {kFineRowsAt, 0x8000u, 147456u};  // where SUB 2 has the rows, the lowest address the form allows, a high one
+    for (uint32_t rank = 0; rank < (uint32_t)kFineIds; ++rank) {
+        const uint32_t tag = (uint32_t)kFineSubTag | rank, staged = fine_stage_tag(tag);
+        bad_tag += staged > 0xffffu || staged <= (uint32_t)kFineSubTag - 1u || fine_tag_rank(staged) != rank;
+        // two at a time, next to an ordinary window number on either side
+        const uint32_t plain = 1u + (rank * 37u) % 0x7fffu;
+        bad_tag += fine_stage_tags2(tag | (plain << 16)) != (staged | (plain << 16)) || fine_stage_tags2(plain | (tag << 16)) != (plain | (staged << 16)) ||
+                   fine_stage_tags2(tag | (tag << 16)) != (staged | (staged << 16)) || fine_stage_tags2(plain | (plain << 16)) != (plain | (plain << 16));
+        for (int sc = 0; sc < 8; ++sc)
+            for (int j = 0; j < 64; ++j) {
+                // the 64 colours of sub-cell sc of some cell (the cell does not enter the address)
+                const int cell = (int)((rank * 61u + (uint32_t)sc * 4099u) % (uint32_t)kFineCells);
+                const int r = (cell & 31) * 8 + (sc & 1) * 4 + (j & 3), g = ((cell >> 5) & 31) * 8 + ((sc >> 1) & 1) * 4 + ((j >> 2) & 3),
+                          b = (cell >> 10) * 8 + (sc >> 2) * 4 + (j >> 4);
+                const uint32_t x = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+                bad_row += fine_sub_cell(r, g, b) != sc;
+                for (const uint32_t at : rows_at) bad_row += fine_row_address(staged, x, at) != at + 16u * rank + 2u * (uint32_t)sc;
+                bad_row += (kFineRowsAt - (uint32_t)kFineSubTag) + fine_row_offset(staged, x | 0x5a000000u) != kFineRowsAt + 16u * rank + 2u * (uint32_t)sc;
+                ++rows;
+            }
+    }
+    printf("fineaddr colours=%ld rows=%ld bad_cell=%ld bad_row=%ld bad_tag=%ld\n", n, rows, bad_cell, bad_row, bad_tag);
+    return bad_cell || bad_row || bad_tag ? 1 : 0;
+}
+
 static int run_finesublevel(const char *path, const int n_cases)
 {
     FILE *f = fopen(path, "rb");
@@ -1145,7 +1187,7 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1163,6 +1205,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finesub") return argc > 4 ? run_finesub(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "finesublevel") return run_finesublevel(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finechoice") return run_finechoice(argv[2], atoi(argv[3]));
+    if (std::string(argv[1]) == "fineaddr") return run_fineaddr(atol(argv[2]), atol(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));

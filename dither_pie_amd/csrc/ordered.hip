@@ -1745,23 +1745,21 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 //   quads A | norms of A | pairs B | window or tag of every cell | rows [n_wide x 8 u16] | thresholds
 // ---------------------------------------------------------------------------------------------
 
-// byte offset of the window number of x's cell: cell = r>>3 | (g>>3)<<5 | (b>>3)<<10 (host_logic.h: fine_cell), times 2
-__device__ __forceinline__ uint32_t fine_cell_offset(const uint32_t x)
+// (the byte offset of the window number of x's cell, fine_cell_offset, and the address of a tagged cell's row entry,
+// fine_row_address: ordered_fine.h)
+// a constant held in a vector register: the main loop of the fine kernel is at the limit of its scalar registers and well below
+// that of the others
+template <uint32_t V>
+__device__ __forceinline__ uint32_t vgpr_const()
 {
-    return ((x >> 2) & 0x3eu) | ((x >> 5) & 0x7c0u) | ((x >> 8) & 0xf800u);
+    uint32_t r;
+    asm("v_mov_b32 %0, %1" : "=v"(r) : "i"(V));
+    return r;
 }
 
 struct FineLds {  // where the parts of the table are, in bytes from the start of LDS (wide_at: level 0 only; norm_at: levels 1, 2)
-    uint32_t wide_at, norm_at, pair_at, off_at, ids_at, thr_at;  // (SUB 2: ids_at is where the rows are)
+    uint32_t quad_at, wide_at, norm_at, pair_at, off_at, ids_at, thr_at;  // (SUB 2: ids_at is where the rows are; quad_at: 0 but there)
 };
-
-// SUB 2: LDS address of the row entry of a tagged window number `tag` for the colour x: rows + 16 * rank + 2 * sub-cell, the sub-cell
-// from bit 2 of r, g and b (host_logic.h: fine_sub_cell) as a dot product with the byte weights 2, 4, 8
-__device__ __forceinline__ uint32_t fine_row_address(const uint32_t tag, const uint32_t x, const uint32_t rows_at)
-{
-    const uint32_t sub2 = __builtin_amdgcn_udot4((x >> 2) & 0x010101u, 0x00080402u, rows_at, false);
-    return ((tag & (uint32_t)(kFineIds - 1)) << 4) + sub2;
-}
 
 // SUB 1: a pixel of a wide cell on the window `win` of its sub-cell in LDS, as resolve_wide does it on a flat list: false -- nothing
 // written -- at a tie among the three nearest or exact equality in the decision.
@@ -1807,15 +1805,16 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
     uint32_t c = 0;
     bool done = false, slow = false;
     if constexpr (SUB != 0) {
-        uint32_t tag = *reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2);
+        uint32_t tag = *reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + cell2);  // SUB 2: staged for use (fine_stage_tag)
         if constexpr (SUB == 1) {  // (staged as window 0: the tag is in the image)
             const uint32_t off_src = (uint32_t)pal.fsub_win * kFineWindow + (uint32_t)pal.fsub_wide * kWideList;
             tag = tag == 0u ? (uint32_t) reinterpret_cast<const uint16_t *>(pal.fsub_tab + off_src)[cell2 >> 1] : 0u;
+            if ((tag & kFineSubTag) != 0u) tag = fine_stage_tag(tag);
         }
         if ((tag & kFineSubTag) != 0u) {
             const uint32_t win = *reinterpret_cast<const uint16_t *>(s_bytes + fine_row_address(tag, x, at.ids_at));
             if (win == 0u)
-                done = resolve_wide<MODE>(x, th, thr.sh, pal.fsub_tab + (uint32_t)pal.fsub_win * kFineQuad + (tag & (uint32_t)(kFineIds - 1)) * kWideList,
+                done = resolve_wide<MODE>(x, th, thr.sh, pal.fsub_tab + (uint32_t)pal.fsub_win * kFineQuad + fine_tag_rank(tag) * kWideList,
                                           kWideList, c);
             else if constexpr (SUB == 1)
                 done = resolve_window<MODE>(x, th, thr.sh, s_bytes, win, at.pair_at, g.neg2, c);
@@ -1863,10 +1862,13 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         // and the thresholds right behind the table are written by other lanes)
         for (int i = threadIdx.x * 2; i < pal.fine_words; i += kCellBlock * 2)
             *reinterpret_cast<uint2 *>(&smem[i]) = *reinterpret_cast<const uint2 *>(&pal.fine_tab[i]);
+        at.quad_at = 0;
         at.wide_at = (uint32_t)pal.fine_win * (kFineQuad * 4);
         at.norm_at = 0;
         at.pair_at = at.wide_at + (uint32_t)pal.fine_wide * (kWideList * 4);
         at.off_at = at.pair_at + (uint32_t)pal.fine_win * ((kFineWindow - kFineQuad) * 4);
+        at.ids_at = at.off_at + kFineCells * 2;
+        at.thr_at = at.ids_at + (uint32_t)kFineIds * 2;
     } else {
         // quads A {c0..c3} | their norms {N0..N3} | pairs B (level 1) or records B' {c4, c5, N4, N5} (level 2) | off, ids: built from
         // the same image quads A | wide lists | pairs B | off, ids; the wide lists stay where they are.  Colours and norms of the quads
@@ -1877,23 +1879,30 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         const int n_win = SUB == 0 ? pal.fine_win : pal.fsub_win, n_wide = SUB == 0 ? pal.fine_wide : pal.fsub_wide;
         const int pair_src = n_win * kFineQuad + n_wide * kWideList;  // words into the image
         const int tail_src = pair_src + n_win * (kFineWindow - kFineQuad);
+        // SUB 2: off | rows | quads A | norms | pairs B -- `off` at 0 and the rows at kFineRowsAt, so that neither base is an operand
+        // of the main loop (ordered_fine.h); the same bytes in all
         at.wide_at = 0;
-        at.norm_at = (uint32_t)n_win * (kFineQuad * 4);
-        at.pair_at = 2 * at.norm_at;
-        at.off_at = at.pair_at + (uint32_t)n_win * (kPairRec * 4);
+        at.quad_at = SUB == 2 ? kFineRowsAt + (uint32_t)n_wide * 16u : 0u;
+        at.norm_at = at.quad_at + (uint32_t)n_win * (kFineQuad * 4);
+        at.pair_at = at.norm_at + (uint32_t)n_win * (kFineQuad * 4);
+        const uint32_t pair_end = at.pair_at + (uint32_t)n_win * (kPairRec * 4);
+        at.off_at = SUB == 2 ? 0u : pair_end;
+        at.ids_at = at.off_at + kFineCells * 2;
+        at.thr_at = SUB == 2 ? pair_end : at.ids_at + (SUB == 0 ? (uint32_t)kFineIds * 2 : (uint32_t)n_wide * 16);
+        uint32_t *s_quad = smem + at.quad_at / 4, *s_norm = smem + at.norm_at / 4, *s_pair = smem + at.pair_at / 4;
         for (int wi = threadIdx.x; wi < n_win; wi += kCellBlock) {
             const uint4 c = *reinterpret_cast<const uint4 *>(&tab[wi * kFineQuad]);
-            *reinterpret_cast<uint4 *>(&smem[wi * 4]) = c;
-            *reinterpret_cast<uint4 *>(&smem[n_win * 4 + wi * 4]) =
+            *reinterpret_cast<uint4 *>(&s_quad[wi * 4]) = c;
+            *reinterpret_cast<uint4 *>(&s_norm[wi * 4]) =
                 make_uint4((__builtin_amdgcn_udot4(c.x, c.x, 0u, false) << kLocalBits), (__builtin_amdgcn_udot4(c.y, c.y, 0u, false) << kLocalBits) + 4u,
                            (__builtin_amdgcn_udot4(c.z, c.z, 0u, false) << kLocalBits) + 8u, (__builtin_amdgcn_udot4(c.w, c.w, 0u, false) << kLocalBits) + 12u);
             const uint2 b = *reinterpret_cast<const uint2 *>(&tab[pair_src + wi * 2]);
             if constexpr (KEYS == 2)
-                *reinterpret_cast<uint4 *>(&smem[n_win * 8 + wi * 4]) =
+                *reinterpret_cast<uint4 *>(&s_pair[wi * 4]) =
                     make_uint4(b.x, b.y, (__builtin_amdgcn_udot4(b.x, b.x, 0u, false) << kLocalBits) + 16u,
                                (__builtin_amdgcn_udot4(b.y, b.y, 0u, false) << kLocalBits) + 20u);
             else
-                *reinterpret_cast<uint2 *>(&smem[n_win * 8 + wi * 2]) = b;
+                *reinterpret_cast<uint2 *>(&s_pair[wi * 2]) = b;
         }
         // (two words at a time: source and destination start at an even word)
         uint32_t *s_tail = smem + at.off_at / 4;
@@ -1904,11 +1913,13 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
                 v.x &= ~(((v.x & 0x80008000u) >> 15) * 0xffffu);
                 v.y &= ~(((v.y & 0x80008000u) >> 15) * 0xffffu);
             }
+            if (SUB == 2 && i < kFineCells / 2) {  // a tag becomes the offset of its row (fine_stage_tag)
+                v.x = fine_stage_tags2(v.x);
+                v.y = fine_stage_tags2(v.y);
+            }
             *reinterpret_cast<uint2 *>(&s_tail[i]) = v;
         }
     }
-    at.ids_at = at.off_at + kFineCells * 2;
-    at.thr_at = at.ids_at + (SUB == 0 ? (uint32_t)kFineIds * 2 : (uint32_t)pal.fsub_wide * 16);
     {
         const int n = thr.th_h * thr.tw_pad;
         const int thr_word = KEYS == 0 ? pal.fine_words : (int)(at.thr_at / 4);  // (the same place at level 0)
@@ -1923,10 +1934,23 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
     uint3 *out3 = reinterpret_cast<uint3 *>(out);
     const uint32_t n_full = g.n_px >> 2;  // groups of four whole pixels; a partial last group goes through the queue
 
+    // the quad of a window and, KEYS > 0, its norms: an add and a shift in one instruction each (the bases are multiples of 16)
+    const uint32_t quad16 = at.quad_at >> 4, norm16 = at.norm_at >> 4;
+    auto quad_of = [&](const uint32_t w) { return (w + quad16) << 4; };
+    // (SUB 2: the constants of the address arithmetic in vector registers, see vgpr_const)
+    const uint32_t w_cell = SUB == 2 ? vgpr_const<kFineCellWeights>() : kFineCellWeights;
+    const uint32_t w_sub = SUB == 2 ? vgpr_const<kFineSubWeights>() : kFineSubWeights;
+    const uint32_t last_win = SUB == 2 ? vgpr_const<(uint32_t)kFineSubTag - 1u>() : (uint32_t)kFineSubTag - 1u;
     // the window numbers of a group's four pixels
     auto windows = [&](const uint32_t xq[4], uint32_t win[4]) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + at.off_at + fine_cell_offset(xq[q]));
+        for (int q = 0; q < 4; ++q) {
+            win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + fine_cell_offset(xq[q], at.off_at, w_cell));
+            // SUB 2: the number is tested and shifted a tile later, in another block.  Left alone, the compiler narrows the test to the 16
+            // bits read and moves the widening to where the 32 bits are used, an instruction of its own there; through the annotation
+            // (no instruction) the widening stays with the read, which does it, and the uses see an opaque 32-bit value.
+            if constexpr (SUB == 2) win[q] = __builtin_annotation(win[q], "fine window");
+        }
     };
     auto drain = [&](const uint32_t n) {
         qcount -= n;
@@ -1936,6 +1960,10 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
     };
 
+    // (the tile stride as a value of its own: as the launch packet's field it is read again from memory in every trip once the scalar
+    // registers run short, and the wait for that read is a wait for the LDS reads in flight)
+    uint32_t n_blocks = gridDim.x;
+    asm("" : "+s"(n_blocks));
     uint32_t tile = blockIdx.x;
     uint32_t fy = 0, fx = 0;
     uint3 wn = make_uint3(0u, 0u, 0u), wnn = make_uint3(0u, 0u, 0u);  // the groups of the next tile and of the one after it
@@ -1944,8 +1972,8 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         const uint32_t gidx0 = tile * kCellBlock + threadIdx.x;
         if (gidx0 < n_full) wn = in3[gidx0];
         if (gidx0 * 4u < g.n_px) locate(g, gidx0 * 4u, fy, fx);
-        const uint32_t gidx1 = gidx0 + gridDim.x * kCellBlock;
-        if (tile + gridDim.x < n_tiles && gidx1 < n_full) wnn = in3[gidx1];
+        const uint32_t gidx1 = gidx0 + n_blocks * kCellBlock;
+        if (tile + n_blocks < n_tiles && gidx1 < n_full) wnn = in3[gidx1];
     }
     // SUB 2: the windows of the sub-cells in place of the tags, one branch per pixel slot (a wave has a tagged lane in a given
     // slot about every other time; a test over all four slots is taken by nearly every wave)
@@ -1953,7 +1981,8 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         if constexpr (SUB == 2) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if ((win[q] & kFineSubTag) != 0u) win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + fine_row_address(win[q], xq[q], at.ids_at));
+                if (win[q] > last_win)  // one compare on the 32-bit value (see windows)
+                    win[q] = *reinterpret_cast<const uint16_t *>(s_bytes + (kFineRowsAt - (uint32_t)kFineSubTag) + fine_row_offset(win[q], xq[q], w_sub));
         }
     };
     unpack4(wn, xn);
@@ -1975,7 +2004,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         cls_shift = (idx & 7u) * 4u;
     };
     if (tile < n_tiles) tile_class(fy, fx, tile * kCellBlock + threadIdx.x);
-    for (; tile < n_tiles; tile += gridDim.x) {
+    for (; tile < n_tiles; tile += n_blocks) {
         const uint32_t gidx = tile * kCellBlock + threadIdx.x;
         uint32_t xq[4], win[4];
 #pragma unroll
@@ -1989,7 +2018,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
             // the next tile's groups arrived during the last one: ask for their windows now, and for the groups after them
             unpack4(wnn, xn);
             windows(xn, winn);
-            const uint32_t next = tile + gridDim.x, next2 = next + gridDim.x;
+            const uint32_t next = tile + n_blocks, next2 = next + n_blocks;
             const uint32_t gn = next * kCellBlock + threadIdx.x, gn2 = next2 * kCellBlock + threadIdx.x;
             wnn = make_uint3(0u, 0u, 0u);
             if (next2 < n_tiles && gn2 < n_full) wnn = in3[gn2];
@@ -2004,8 +2033,8 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
             uint4 ca[4], na[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                ca[q] = *reinterpret_cast<const uint4 *>(s_bytes + (win[q] << 4));
-                if constexpr (KEYS != 0) na[q] = *reinterpret_cast<const uint4 *>(s_bytes + ((win[q] << 4) + at.norm_at));
+                ca[q] = *reinterpret_cast<const uint4 *>(s_bytes + quad_of(win[q]));
+                if constexpr (KEYS != 0) na[q] = *reinterpret_cast<const uint4 *>(s_bytes + ((win[q] + norm16) << 4));
             }
             // one straight-line body per class pattern (bit q: slot q takes its nearest entry whatever the second one is)
             auto body = [&](auto cls_c) {
@@ -2052,7 +2081,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
                         if constexpr (KEYS == 0) cand4n(x, ca[q], g.neg2, m0, m1);
                         else cand4k(x, ca[q], na[q], g.neg2, m0, m1);
                         rare[q] = ((uint32_t)(m0 ^ m1) < (1u << kLocalBits)) | straddle;  // a tie for the nearest entry; also: any wide cell
-                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((win[q] << 4) | ((uint32_t)m0 & 0xfcu)));
+                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + (quad_of(win[q]) | ((uint32_t)m0 & 0xfcu)));
                     } else {
                         int m0, m1, m2;
                         if constexpr (KEYS == 0) cand6(x, ca[q], cb[q].x, cb[q].y, g.neg2, m0, m1, m2);
@@ -2066,7 +2095,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
                         const bool nearest = lean_decide<MODE>(d0, S, th[q], thr.sh, eq);
                         rare[q] = tie | eq | straddle;
                         const uint32_t pos = (uint32_t)(nearest ? m0 : m1) & 0xfcu;  // 4 x the place in the window
-                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((pos < 16u ? (win[q] << 4) : pb[q]) + pos));
+                        col[q] = *reinterpret_cast<const uint32_t *>(s_bytes + ((pos < 16u ? quad_of(win[q]) : pb[q]) + pos));
                     }
                 }
                 out3[gidx] = pack4(col);
@@ -2080,10 +2109,11 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
             for (int q = 0; q < 4; ++q) rare[q] = gidx * 4u + (uint32_t)q < g.n_px;  // the partial last group
         }
         sub_windows(xn, winn);  // the next tile's: their tags arrived during the body
-        // one queue entry per group with deferred pixels: group << 4 | which of its four
-        const uint32_t rmask = (rare[0] ? 1u : 0u) | (rare[1] ? 2u : 0u) | (rare[2] ? 4u : 0u) | (rare[3] ? 8u : 0u);
-        const unsigned long long rb = __ballot(rmask != 0u);
+        // one queue entry per group with deferred pixels: group << 4 | which of its four.  The ballot is the OR of the four lane
+        // masks, scalar work; the entry is put together only where there is one.
+        const unsigned long long rb = __builtin_amdgcn_ballot_w64(rare[0] | rare[1] | rare[2] | rare[3]);
         if (rb != 0ull) {  // wave-uniform
+            const uint32_t rmask = (rare[0] ? 1u : 0u) | (rare[1] ? 2u : 0u) | (rare[2] ? 4u : 0u) | (rare[3] ? 8u : 0u);
             if (rmask != 0u)
                 s_queue[__builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, qcount))] = (gidx << 4) | rmask;
             qcount += (uint32_t)__popcll(rb);

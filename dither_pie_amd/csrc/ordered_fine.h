@@ -70,7 +70,8 @@ constexpr int kFineKeysShipped = 1;
 //   quads A [n_win x 16 B] | their norms [n_win x 16 B] | pairs B [n_win x 8 B] | window or tag of every cell [32768 x 2 B] | rows
 //   [n_wide x 16 B] | integer thresholds
 // (the sorted cell numbers of the wide cells are not staged: the tag is the rank), and the image in global memory, which also holds
-// the flat lists, is  A | flat lists [n_wide x 64 B] | B | off | rows.
+// the flat lists, is  A | flat lists [n_wide x 64 B] | B | off | rows.  SUB 2 stages the same parts in another order, `off` | rows |
+// quads A | norms | pairs B | thresholds, and the tags ready for use (kFineRowsAt, fine_stage_tag below); the bytes in all are the same.
 constexpr int64_t fine_sub_bytes(const int n_win, const int n_wide)
 {
     return (int64_t)n_win * 40 + kFineCells * 2 + (int64_t)n_wide * 16;
@@ -119,6 +120,60 @@ inline bool fine_plan_ok(const OrderedPlan &p)
 // above every run of the parent; level 1 measured exactly today's time -- it makes a wide pixel's drain cheaper, not rarer -- and
 // exists in the experiments build only (DP_FINE_SUB_MAX=1; DESIGN 4.1, profiles/experiments/fine_sub_levels.md).
 constexpr int kFineSubShipped = 2;
+
+// ---- the address arithmetic of the main loop, shared with the deferred path and, as plain C++, with the test harness
+// (host_sanitize.cpp `fineaddr`; tests/test_ordered_fine_addr_cpu.py) -----------------------------------------------------
+// a . b over the four bytes, plus c: one v_dot4_u32_u8 on the device
+DP_HD inline uint32_t fine_udot4(const uint32_t a, const uint32_t b, const uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(a, b, c, false);
+#else
+    uint32_t s = c;
+    for (int i = 0; i < 4; ++i) s += ((a >> (8 * i)) & 255u) * ((b >> (8 * i)) & 255u);
+    return s;
+#endif
+}
+// byte offset of the window number of x's cell, from `base`: 2 * fine_cell = 2 r5 + 64 g5 (the dot product) + (b5 << 11) (its
+// accumulator); bits 24-31 of x are ignored.  Five instructions, four where base is 0.  (The byte weights are a parameter so that
+// the kernel can say which register file holds them; so in fine_row_offset.)
+constexpr uint32_t kFineCellWeights = 0x00004002u, kFineSubWeights = 0x00080402u;
+DP_HD inline uint32_t fine_cell_offset(const uint32_t x, const uint32_t base = 0u, const uint32_t weights = kFineCellWeights)
+{
+    const uint32_t z = (x >> 3) & 0x1f1f1fu;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // byte 2 of z shifted in one instruction (the compiler makes a shift and a mask of x from the line below)
+    uint32_t hi;
+    asm("v_lshlrev_b32_sdwa %0, 11, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(hi) : "v"(z));
+#else
+    const uint32_t hi = (z >> 16) << 11;
+#endif
+    return fine_udot4(z, weights, hi + base);
+}
+// SUB 2 stages `off` first and the rows right behind it (the global image and the other levels are what they were): the base of
+// `off` is no operand at all, and the rows sit at a constant address.
+constexpr uint32_t kFineRowsAt = (uint32_t)kFineCells * 2u;
+// ... and stages the tag of a wide cell ready for use: bit 15 | rank << 4, the row's offset
+DP_HD inline uint32_t fine_stage_tag(const uint32_t tag) { return (uint32_t)kFineSubTag | ((tag & (uint32_t)(kFineIds - 1)) << 4); }
+DP_HD inline uint32_t fine_tag_rank(const uint32_t staged) { return (staged >> 4) & (uint32_t)(kFineIds - 1); }
+// two window numbers at a time, as the stager meets them (a tagged half has bit 15 set)
+DP_HD inline uint32_t fine_stage_tags2(const uint32_t v)
+{
+    const uint32_t t = v & 0x80008000u, m = (t >> 15) * 0xffffu;
+    return (v & ~m) | (m & (t | ((v & 0x01ff01ffu) << 4)));
+}
+static_assert(kFineIds == 512, "fine_stage_tags2: nine bits of rank");
+// the row entry of a staged tag for the colour x, less the tag bit: tag + 2 * sub-cell, the sub-cell from bit 2 of r, g and b
+// (host_logic.h: fine_sub_cell) as a dot product with the byte weights 2, 4, 8 and the tag as its accumulator
+DP_HD inline uint32_t fine_row_offset(const uint32_t staged, const uint32_t x, const uint32_t weights = kFineSubWeights)
+{
+    return fine_udot4((x >> 2) & 0x010101u, weights, staged);
+}
+// its address where the rows are at rows_at: rows_at + 16 * rank + 2 * sub-cell (a constant rows_at folds into the read)
+DP_HD inline uint32_t fine_row_address(const uint32_t staged, const uint32_t x, const uint32_t rows_at)
+{
+    return fine_row_offset(staged, x) + (rows_at - (uint32_t)kFineSubTag);
+}
 
 // ---- the choice of a call: everything above put together, as pure as plan_ordered (host_sanitize.cpp `finechoice`;
 // tests/test_ordered_fine_choice_cpu.py) ------------------------------------------------------------------------------------
