@@ -144,7 +144,7 @@ struct PalDev {
     const uint4 *ed_ext16;       // 17..256 colours: the 16^3 lists whose outermost cells are unbounded (EdTables::ext16), for the unclamped diffusers; or null
     const uint4 *ed_ext_nodes;   // the octree below its outermost cells whose list is too long (EdTables::ext_nodes), or null
     const uint4 *ed_lists16;    // palettes of 17..256 colours: lists of the 16^3 cells, count byte | up to 15 index bytes (255: too long)
-    const uint32_t *ed_h4;      // palettes of 17..256 colours: hierarchical table of <= 4 entries per leaf (host_logic.h EdTables::h4), or null
+    const uint32_t *ed_h4;      // palettes of 17..256 colours: hierarchical table of <= 4 entries per leaf (ed_tables.h: ed_build_h4), or null
     int ed_h4_words;
     int ed_h4_shallow;          // mean depth of the table at the palette's own colours <= 0.25: worth reading from L2 (ediff.hip)
     int ed_h4_global;           // the sixteen-wave instances read it from global memory (set per launch)

@@ -277,7 +277,7 @@ __device__ __forceinline__ void ed_nibble_exact_scan(Top2 &t, const uint32_t e, 
 }
 
 // ---- byte lists (17..256 colours): a block of 16 bytes per cell, the count n in byte 0 -- 1..15 entries in bytes 1..n;
-// 254: a crowded cell, refined (node number from bit 8 on); 255: no list.  The builder (host_logic.h: ed_tables_refine, pack)
+// 254: a crowded cell, refined (node number from bit 8 on); 255: no list.  The builder (ed_tables.h: pack)
 // pads lists of up to 12 entries to a multiple of four positions with an entry that is not on the list; other unused bytes
 // hold 0: a valid, ignored read.
 
@@ -332,7 +332,7 @@ __device__ __forceinline__ void ed_byte_exact_scan(Top2 &t, const uint4 blk, int
 }
 
 // ---- wide lists (257..1024 colours): the same block with up to twelve ten-bit entries from bit 8 on, padded like the byte
-// lists (host_logic.h: ed_list_put; ediff.hip: ed_cells_kernel)
+// lists (ed_tables.h: ed_list_put; ediff.hip: ed_cells_kernel)
 
 // entry `pos` (0-based) of a wide block
 __device__ __forceinline__ int ed_wide_entry(const uint4 blk, const uint32_t pos)
@@ -368,7 +368,7 @@ __device__ __forceinline__ void ed_wide_exact_scan(Top2 &t, const uint4 blk, con
     }
 }
 
-// ---- the hierarchical table of at most four entries per leaf (host_logic.h: EdTables::h4; palettes of 17..256 colours).
+// ---- the hierarchical table of at most four entries per leaf (ed_tables.h: ed_build_h4; palettes of 17..256 colours).
 // The wave pays for the longest candidate list among its 64 lanes, so instead of scanning a 16^3 cell's list in rounds of
 // four, a lane whose cell has more than four possible nearest entries descends to the cell's 8-wide child and, if need be, to
 // the 4-wide and 2-wide ones -- at most three more dependent reads -- and ranks ONE group of four.
@@ -488,7 +488,7 @@ __device__ __forceinline__ int nearest_ext(const PalDev &pal, const float4 *__re
 }
 
 // Palettes of 17..1024 colours, any query point: the key scan over the byte (above 256 colours: wide) list of the point's
-// cell in the extended 16^3 table `ext16` (host_logic.h: EdTables::ext16 -- the outermost cells are unbounded, a point is
+// cell in the extended 16^3 table `ext16` (ed_tables.h: ed_build_ext16 -- the outermost cells are unbounded, a point is
 // looked up by its clamped coordinates) and the octree pal.ed_ext_nodes below its crowded outermost cells.  `cand`: all
 // pal.K records, in LDS; `inside`: the point lies in the cube, where pal.ed_cells (if there) has lists for the cells whose
 // extended list is too long.  Near ties of a list go to its exact scan, what that cannot decide and exact ties to the full

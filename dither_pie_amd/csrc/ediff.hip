@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void ed_cells_kernel(const PalDev pal, uint4 *
             ++n;
             if (K <= 256) {
                 if (n <= 15) w[n >> 2] |= (uint32_t)j << (8 * (n & 3));
-            } else if (n <= 12) {   // 257..1024 colours: ten bits per entry from bit 8 on (host_logic.h: ed_list_put)
+            } else if (n <= 12) {   // 257..1024 colours: ten bits per entry from bit 8 on (ed_tables.h: ed_list_put)
                 const int off = 8 + 10 * (n - 1), wi = off >> 5, sh = off & 31;
                 w[wi] |= (uint32_t)j << sh;
                 if (sh > 22 && wi < 3) w[wi + 1] |= (uint32_t)j >> (32 - sh);
@@ -804,11 +804,11 @@ int build_ed_cells(PalDev &dev, const double *pts, void **blob_out)
         (void)hipFree(cells);
         return hip_fail(e, "error-diffusion candidate lists");
     }
-    // Everything between the kernel's geometric lists and the finished tables is host work (host_logic.h): the pairwise
+    // Everything between the kernel's geometric lists and the finished tables is host work (ed_tables.h): the pairwise
     // sharpening, the refinement of overflowing cells (palettes extracted from an image crowd their colours into a few
     // cells) into an octree down to unit cubes, the 16^3-cell lists for LDS.
     EdTables tb;
-    ed_tables_refine(pts, K, host, tb);
+    ed_tables_build(ed_palette(pts, K), host, tb);
     if (exp_env("DP_ED_H4_REPORT")) {
         fprintf(stderr, "ed tables: K %d, h4 %zu words (%zu wanted, limit %zu, in LDS up to %zu), mean depth at the palette's colours %.2f (no answer at %.3f of them), nodes %zu\n", K, tb.h4.size(), tb.h4_wanted, kEdH4MaxWords, kEdH4LdsWords, tb.h4_depth, tb.h4_none, tb.nodes.size());
         if (!tb.coarse.empty()) {   // K <= 16: how long the 16^3 nibble lists are (a wave pays for the longest among its 64 lanes)
@@ -863,7 +863,7 @@ int build_ed_cells(PalDev &dev, const double *pts, void **blob_out)
     return DP_OK;
 }
 
-// The extended 16^3 lists of the unclamped diffusers (host_logic.h: EdTables::ext16 / ext_nodes), 17..1024 colours: built when such a
+// The extended 16^3 lists of the unclamped diffusers (ed_tables.h: ed_ext_build), 17..1024 colours: built when such a
 // diffuser first meets the palette (5-16 ms of host time that plain error diffusion never needs).  No policy switch: a wave that
 // holds a lane without a usable list beyond the cube takes the whole-palette scan with ALL its lanes (vardiff.hip: nearest_ext16),
 // so a palette crowded at a face of the cube -- every palette under use_gamma is, at the dark end -- never costs more than without.
@@ -872,9 +872,8 @@ int build_ed_ext(PalDev &dev, const double *pts, void **blob_out)
     *blob_out = nullptr;
     const int K = dev.K;
     if (K <= 16) return DP_OK;
-    std::vector<U4> none;
     EdTables tb;
-    ed_tables_refine(pts, K, none, tb, 2);
+    ed_ext_build(ed_palette(pts, K), tb);
     if (tb.ext16.empty()) return DP_OK;
     uint4 *blob = nullptr;
     DP_HIP(hipMalloc((void **)&blob, sizeof(uint4) * (4096 + tb.ext_nodes.size())));

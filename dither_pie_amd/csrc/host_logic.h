@@ -1,6 +1,6 @@
 // Host-side logic of libditherpie_hip.so that never touches the GPU: the scipy-order KD-tree build, the assembly of
-// the search accelerator's cell table from membership masks, and the candidate tables of the diffusion kernels (with
-// their multi-threaded per-cell loops).  Pure C++17, no HIP headers: included by the .hip / .cpp translation units through
+// the search accelerator's cell table from membership masks, and (ed_tables.h) the candidate tables of the diffusion kernels with
+// their multi-threaded per-cell loops.  Pure C++17, no HIP headers: included by the .hip / .cpp translation units through
 // dp_internal.h AND compiled on its own under AddressSanitizer + UBSan and under ThreadSanitizer
 // (`make host_asan host_tsan` -> build/host_asan, build/host_tsan from host_sanitize.cpp; run by
 // tests/test_host_sanitizers.py in the CPU tier).
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/ditherpie_hip.h"
+#include "ed_tables.h"   // the candidate tables of the diffusion kernels
 
 namespace dp {
 
@@ -794,688 +795,6 @@ void fine_pack_sub(const uint32_t *tmask, const uint32_t *nmask, const int mw, c
     fine_pack_units(tmask, nmask, mw, K, coord4, fits, ft, true);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// Candidate tables of the diffusion kernels (ediff.hip / vardiff.hip): everything that happens on the host between the
-// download of ed_cells_kernel's geometric lists and the upload of the finished tables.
-// ---------------------------------------------------------------------------------------------
-struct U4 {  // layout of HIP's uint4
-    uint32_t x, y, z, w;
-};
-inline U4 make_u4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return U4{x, y, z, w}; }
-
-constexpr int kEdCells = 32 * 32 * 32;
-
-// The per-cell loops below are independent: split them over a few host threads (the tables of a new palette are built
-// at its first diffusion call, i.e. in front of a user's image).  Each thread writes only the cells of its own range.
-template <class F>
-inline void parallel_cells(const int n, F &&body, const int serial_below = 1024)
-{
-    unsigned nt = std::thread::hardware_concurrency();
-    nt = nt < 1 ? 1 : (nt > 8 ? 8 : nt);
-    if (n < serial_below || nt == 1) {
-        body(0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    const int chunk = (n + (int)nt - 1) / (int)nt;
-    for (unsigned t = 1; t < nt; ++t) {
-        const int lo = (int)t * chunk, hi = std::min(n, lo + chunk);
-        if (lo < hi) th.emplace_back([&body, lo, hi]() { body(lo, hi); });
-    }
-    body(0, std::min(n, chunk));
-    for (auto &t : th) t.join();
-}
-
-struct EdTables {
-    std::vector<U4> nodes;         // refinement of overflowing 8^3 cells (8 entries per node); empty if none / given up
-    bool give_up = false;          // more than 2^22 nodes: the overflowing cells keep count 255 (scan the palette)
-    std::vector<U4> l16;           // K > 16: lists of the 16^3 cells in the 8^3 table's format
-    std::vector<uint32_t> coarse;  // K <= 16: lists of the 16^3 cells, count | 7 index nibbles
-    std::vector<uint32_t> ext;     // K <= 16: the same over the extended grid (outermost cells = half-spaces)
-    std::vector<U4> ext16;         // 17..256 colours: l16 with the OUTERMOST cells standing for everything beyond them (unbounded boxes),
-                                   // for the diffusers that do not clamp their values (vardiff.hip: nearest_ext16); count 255: too long
-    std::vector<U4> ext_nodes;     // ... and the octree below the outermost cells whose list is too long (count 254 | node << 8: eight
-                                   // half-size children, the outer ones unbounded again), at most kEdExtMaxNodes nodes
-    // K > 16: the hierarchical nearest table of at most four entries per leaf (ed_nearest.hip.h: nearest_h4).  Words [0, 4096): the
-    // 16^3 cells; then nodes of 8 words: the 8-wide children of a cell, the 4-wide children of a child, the 2-wide ones of those.  A LEAF word holds four
-    // palette indices, byte 0 < byte 1 (listed entries, then an unlisted far entry as padding); a word with byte 0 >= byte 1 is a
-    // MARKER: 0x00ff | node << 16 (node 0xffff: no answer here, use the lists).  Empty when it would not fit kEdH4MaxWords.
-    std::vector<uint32_t> h4;
-    size_t h4_wanted = 0;          // words the table would take (reported by the experiments build)
-    double h4_none = 0.0;          // fraction of the palette's own colours at which the table has no answer
-    double h4_depth = 0.0;         // mean number of descents of nearest_h4 at the palette's own colours (4 = no answer): where a
-                                   // palette puts its colours is where its images put their pixels
-};
-constexpr size_t kEdH4LdsWords = 27648;   // 108 KB: all the LDS the few-frames diffusion kernel has left (256 random colours: 21 336 words, median cut 256 of smooth content: 25 120)
-constexpr size_t kEdH4MaxWords = 65536;   // largest table built (256 KB, node numbers stay below 0xffff): beyond the LDS size it is read from L2
-constexpr uint32_t kEdH4NoAnswer = 0xffff00ffu;
-
-// cells [kEdCells]: in = the kernel's lists (count byte | up to 15 index bytes, count 255 = overflow), out = sharpened,
-// padded, overflowing cells refined into `nodes`.  pts: K*3 float64 palette coordinates.
-// A list block (8^3 cells, their octree nodes, 16^3 cells): word 0's low byte is the count (254: node pointer in the upper 24 bits,
-// 255: too long -- scan the palette), then the entries' palette indices: one BYTE each (up to 15) for palettes of up to 256 colours,
-// TEN BITS each from bit 8 on (up to 12: 8 + 120 = 128 bits) for 257..1024 colours ("wide"; round 5 -- until then error diffusion with
-// more than 256 colours had no lists at all and ran the KD-tree query at every pixel step: 0.44 s per 4K frame at 1024 colours).
-constexpr size_t kEdExtMaxNodes = 2048;   // refinement nodes of the extended 16^3 lists (8 entries each: 256 KB)
-inline int ed_list_cap(const int K) { return K > 256 ? 12 : 15; }
-inline int ed_list_get(const uint32_t (&w)[4], const int pos /* 0-based */, const bool wide)
-{
-    if (!wide) return (int)((w[(pos + 1) >> 2] >> (8 * ((pos + 1) & 3))) & 255u);
-    const int off = 8 + 10 * pos, wi = off >> 5, sh = off & 31;
-    uint32_t v = w[wi] >> sh;
-    if (sh > 22 && wi < 3) v |= w[wi + 1] << (32 - sh);
-    return (int)(v & 1023u);
-}
-inline void ed_list_put(uint32_t (&w)[4], const int pos /* 0-based */, const int j, const bool wide)
-{
-    if (!wide) {
-        w[(pos + 1) >> 2] |= (uint32_t)j << (8 * ((pos + 1) & 3));
-        return;
-    }
-    const int off = 8 + 10 * pos, wi = off >> 5, sh = off & 31;
-    w[wi] |= (uint32_t)j << sh;
-    if (sh > 22 && wi < 3) w[wi + 1] |= (uint32_t)j >> (32 - sh);
-}
-
-// what: 1 = the tables every diffusion kernel uses (the 8^3 lists in `host` refined in place, their octree, 16^3 lists, hierarchical
-// table, nibble tables), 2 = ONLY the extended 16^3 lists of the unclamped diffusers (ext16 / ext_nodes; `host` is not touched) --
-// built when such a diffuser first meets the palette, so that plain error diffusion does not pay for them (5-16 ms) -- 3 = both.
-inline void ed_tables_refine(const double *pts, const int K, std::vector<U4> &host, EdTables &out, const int what = 1)
-{
-    const bool wide = K > 256;
-    const int cap = ed_list_cap(K);
-    std::vector<U4> &nodes = out.nodes;
-    nodes.clear();
-    auto box_list = [&](const std::vector<int> &from, const double lo[3], const double size, std::vector<int> &list) {
-        double bound = std::numeric_limits<double>::infinity();
-        for (int j : from) {
-            double far2 = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                const double c = pts[3 * j + k];
-                const double m = std::max(std::fabs(c - lo[k]), std::fabs(c - (lo[k] + size)));
-                far2 += m * m;
-            }
-            bound = std::min(bound, far2);
-        }
-        bound = bound * (1.0 + 1e-12) + 1e-9;
-        list.clear();
-        for (int j : from) {
-            double near2 = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                const double c = pts[3 * j + k];
-                const double m = std::max(std::max(lo[k] - c, c - (lo[k] + size)), 0.0);
-                near2 += m * m;
-            }
-            if (near2 <= bound) list.push_back(j);
-        }
-    };
-    // A sharper (still conservative) list for a box: entry j is dropped if some other listed entry k is closer to EVERY
-    // point of the box, i.e. the box lies strictly on k's side of the bisector of j and k:
-    //   max over the box of |x - c_k|^2 - |x - c_j|^2 = max of 2 x.(c_j - c_k) + |c_k|^2 - |c_j|^2 < 0   (linear in x).
-    // The true nearest entry of a point of the box is dominated by nobody, so it stays listed, with everything tied with it.
-    auto prune_list = [&](const double lo[3], const double size, std::vector<int> &list) {
-        std::vector<int> keep;
-        for (int j : list) {
-            bool dominated = false;
-            for (int k : list) {
-                if (k == j) continue;
-                double mx = 0.0;
-                for (int d = 0; d < 3; ++d) {
-                    const double a = 2.0 * (pts[3 * j + d] - pts[3 * k + d]);
-                    mx += std::max(a * lo[d], a * (lo[d] + size));
-                    mx += pts[3 * k + d] * pts[3 * k + d] - pts[3 * j + d] * pts[3 * j + d];
-                }
-                if (mx < -1e-9 * (1.0 + std::fabs(mx))) {
-                    dominated = true;
-                    break;
-                }
-            }
-            if (!dominated) keep.push_back(j);
-        }
-        list.swap(keep);
-    };
-    // the palette entry nearest to each corner of the cube: bit d of the index set = the corner's coordinate d is 255
-    int corner_entry[8];
-    for (int c = 0; c < 8; ++c) {
-        double best = std::numeric_limits<double>::infinity();
-        corner_entry[c] = 0;
-        for (int j = 0; j < K; ++j) {
-            double d2 = 0.0;
-            for (int d = 0; d < 3; ++d) {
-                const double m = pts[3 * j + d] - ((c >> d) & 1 ? 255.0 : 0.0);
-                d2 += m * m;
-            }
-            if (d2 < best) {
-                best = d2;
-                corner_entry[c] = j;
-            }
-        }
-    }
-    // count byte + up to 15 index bytes.  Lists of up to 12 entries are padded to a multiple of 4 positions with an entry that is
-    // NOT on the list (the one farthest from the box): the key scan of nearest_color_cells evaluates whole groups of four
-    // without per-position tests; an unlisted entry is never the nearest of a point of the box, and should float32
-    // rounding bring it within the margin of the nearest, the exact scan -- which honours the count -- decides.
-    auto pack = [&](const std::vector<int> &list, const double *lo = nullptr, const double size = 0.0) {
-        uint32_t w[4] = {(uint32_t)list.size(), 0u, 0u, 0u};
-        for (size_t n = 1; n <= list.size(); ++n) ed_list_put(w, (int)n - 1, list[n - 1], wide);
-        if (lo && !list.empty() && list.size() <= 12 && (int)list.size() < K) {
-            // (any unlisted entry will do; a far one keeps it out of the margin: the entry nearest to the cube corner
-            // opposite to the box, unless that one is listed -- then the farthest by scan)
-            const int oct = (lo[0] + 0.5 * size < 128.0 ? 1 : 0) | (lo[1] + 0.5 * size < 128.0 ? 2 : 0) | (lo[2] + 0.5 * size < 128.0 ? 4 : 0);
-            int filler = corner_entry[oct];
-            if (std::find(list.begin(), list.end(), filler) != list.end()) {
-                filler = -1;
-                double far_d = -1.0;
-                for (int j = 0; j < K; ++j) {
-                    if (std::find(list.begin(), list.end(), j) != list.end()) continue;
-                    double d2 = 0.0;
-                    for (int d = 0; d < 3; ++d) {
-                        const double m = pts[3 * j + d] - (lo[d] + 0.5 * size);
-                        d2 += m * m;
-                    }
-                    if (d2 > far_d) {
-                        far_d = d2;
-                        filler = j;
-                    }
-                }
-            }
-            const size_t upto = (list.size() + 3) / 4 * 4;
-            for (size_t n = list.size() + 1; n <= upto && filler >= 0; ++n) ed_list_put(w, (int)n - 1, filler, wide);
-        }
-        return make_u4(w[0], w[1], w[2], w[3]);
-    };
-    struct Work {
-        size_t slot;      // index into `nodes` (or, with top == true, into `host`)
-        bool top;
-        double lo[3];
-        double size;
-        std::vector<int> from;
-    };
-    std::vector<Work> stack;
-    std::vector<int> all(K);
-    for (int j = 0; j < K; ++j) all[j] = j;
-    // the kernel's lists (the geometric criterion), sharpened by the pairwise test
-    if (what & 1) parallel_cells(kEdCells, [&](const int c0, const int c1) {
-        std::vector<int> list;
-        for (int cell = c0; cell < c1; ++cell) {
-            const uint32_t w4[4] = {host[cell].x, host[cell].y, host[cell].z, host[cell].w};
-            const int n = (int)(w4[0] & 255u);
-            if (n < 1 || n > cap) continue;
-            list.clear();
-            for (int i = 1; i <= n; ++i) list.push_back(ed_list_get(w4, i - 1, wide));
-            const double lo[3] = {(double)((cell & 31) * 8), (double)(((cell >> 5) & 31) * 8), (double)((cell >> 10) * 8)};
-            prune_list(lo, 8.0, list);
-            host[cell] = pack(list, lo, 8.0);  // (re-packed even when nothing was dropped: the padding)
-        }
-    });
-    // The cells whose geometric list overflowed: their full pruned lists and, where even those are longer than 15, their octrees.
-    // Each such cell is refined on its own (in parallel: a crowded palette has hundreds of them, and a list of a hundred entries
-    // costs ten thousand pairwise tests) into a LOCAL node array whose node numbers are made global when the arrays are
-    // joined below -- in cell order and with the same depth-first order inside a cell as the single stack of rounds 2-5 had,
-    // so the tables come out byte for byte as before.
-    std::vector<int> over;
-    for (int cell = 0; (what & 1) && cell < kEdCells; ++cell)
-        if ((host[cell].x & 255u) == 255u) over.push_back(cell);
-    struct Local {
-        U4 top;
-        std::vector<U4> nodes;   // 8 per local node; child pointers hold LOCAL node numbers
-    };
-    std::vector<Local> locals(over.size());
-    auto refine_cell = [&](const int cell, Local &lc) {
-        std::vector<Work> st;
-        Work w0;
-        w0.slot = 0;
-        w0.top = true;
-        w0.lo[0] = (double)((cell & 31) * 8);
-        w0.lo[1] = (double)(((cell >> 5) & 31) * 8);
-        w0.lo[2] = (double)((cell >> 10) * 8);
-        w0.size = 8.0;
-        box_list(all, w0.lo, 8.0, w0.from);  // the cell's full list
-        prune_list(w0.lo, 8.0, w0.from);
-        st.push_back(std::move(w0));
-        while (!st.empty()) {
-            Work wk = std::move(st.back());
-            st.pop_back();
-            U4 entry;
-            if ((int)wk.from.size() <= cap) {
-                entry = pack(wk.from, wk.lo, wk.size);
-            } else if (wk.size <= 1.0) {
-                entry = make_u4(255u, 0u, 0u, 0u);  // a unit cube that still sees more than 15 entries: scan the palette
-            } else {
-                const size_t node = lc.nodes.size() / 8;
-                lc.nodes.resize(lc.nodes.size() + 8, make_u4(255u, 0u, 0u, 0u));
-                entry = make_u4(254u | ((uint32_t)node << 8), 0u, 0u, 0u);
-                const double hs = wk.size * 0.5;
-                for (int sub = 0; sub < 8; ++sub) {
-                    Work ch;
-                    ch.slot = node * 8 + (size_t)sub;
-                    ch.top = false;
-                    ch.lo[0] = wk.lo[0] + ((sub & 1) ? hs : 0.0);
-                    ch.lo[1] = wk.lo[1] + ((sub & 2) ? hs : 0.0);
-                    ch.lo[2] = wk.lo[2] + ((sub & 4) ? hs : 0.0);
-                    ch.size = hs;
-                    box_list(wk.from, ch.lo, hs, ch.from);
-                    prune_list(ch.lo, hs, ch.from);
-                    st.push_back(std::move(ch));
-                }
-            }
-            if (wk.top) lc.top = entry;
-            else lc.nodes[wk.slot] = entry;
-        }
-    };
-    if (over.size() >= 16) {
-        parallel_cells((int)over.size(), [&](const int i0, const int i1) {
-            for (int i = i0; i < i1; ++i) refine_cell(over[(size_t)i], locals[(size_t)i]);
-        }, 16);
-    } else {
-        for (size_t i = 0; i < over.size(); ++i) refine_cell(over[i], locals[i]);
-    }
-    bool give_up = false;
-    (void)stack;
-    // joined in the order the single stack visited them: it held the overflowing cells in ascending order and popped the LAST first
-    for (size_t ii = over.size(); ii-- > 0 && !give_up;) {
-        const Local &lc = locals[ii];
-        const size_t base = nodes.size() / 8;
-        if (base + lc.nodes.size() / 8 >= (1u << 22)) {
-            give_up = true;
-            break;
-        }
-        auto fix = [&](U4 e) {
-            if ((e.x & 255u) == 254u) e.x = 254u | ((uint32_t)(base + (e.x >> 8)) << 8);
-            return e;
-        };
-        host[(size_t)over[ii]] = fix(lc.top);
-        for (const U4 &e : lc.nodes) nodes.push_back(fix(e));
-    }
-    out.give_up = give_up;
-    if (give_up) {
-        // abandoned: no cell may point into the node array any more
-        for (int cell = 0; cell < kEdCells; ++cell)
-            if ((host[cell].x & 255u) == 254u) host[cell] = make_u4(255u, 0u, 0u, 0u);
-        nodes.clear();
-    }
-    out.l16.clear();
-    out.coarse.clear();
-    out.ext.clear();
-    out.ext16.clear();
-    out.ext_nodes.clear();
-    out.h4.clear();
-    if (K > 16) {
-        // lists of the 16x16x16 cells in the format of the 8x8x8 table, for the LDS of the wavefront kernel's few-frames
-        // variant (one wave per SIMD: the read of the 8x8x8 table from L2 is half of a step's latency there)
-        std::vector<U4> &l16 = out.l16;
-        l16.resize(4096);
-        std::vector<std::vector<int>> top16(4096);   // the cells' pruned lists: the hierarchical table below starts from them
-        parallel_cells(4096, [&](const int c0, const int c1) {
-            for (int cell = c0; cell < c1; ++cell) {
-                std::vector<int> &list = top16[cell];
-                const double lo[3] = {(double)((cell & 15) * 16), (double)(((cell >> 4) & 15) * 16), (double)((cell >> 8) * 16)};
-                box_list(all, lo, 16.0, list);
-                prune_list(lo, 16.0, list);
-                l16[cell] = (int)list.size() <= cap ? pack(list, lo, 16.0) : make_u4(255u, 0u, 0u, 0u);
-            }
-        });
-        // The extended table for query points that are NOT clamped to the cube (perceptual / hybrid / adaptive-variance): a point is
-        // looked up in the cell of its clamped coordinates, so an outermost cell stands for everything beyond it.  Over such an
-        // unbounded box the geometric criterion lists everybody; the pairwise test alone decides -- entry j stays unless some k is
-        // closer on the WHOLE box (in a direction in which the box is unbounded and |x - c_k|^2 - |x - c_j|^2 grows, k cannot be).
-        // Candidates k are tried nearest to the cell first (most entries fall to one of the first few).  Until round 5 these
-        // diffusers scanned the whole palette at every step above 16 colours: 59 ms per 1080p frame at 256 colours against 4.6 ms
-        // for plain error diffusion (tools/bench_scripts/cliff_hunt.py).
-        out.ext16.clear();
-        if (what & 2) {   // (byte entries up to 256 colours, ten-bit entries above: pack())
-            std::vector<U4> &ext16 = out.ext16;
-            ext16 = l16;
-            const double kInfE = std::numeric_limits<double>::infinity();
-            std::vector<int> shell;
-            for (int cell = 0; cell < 4096; ++cell) {
-                const int c0 = cell & 15, c1 = (cell >> 4) & 15, c2 = cell >> 8;
-                if (c0 == 0 || c0 == 15 || c1 == 0 || c1 == 15 || c2 == 0 || c2 == 15) shell.push_back(cell);
-            }
-            // the entries of `from` that no other entry of `from` dominates over the box [blo, bhi] (sides may be infinite); `lo`/`size`:
-            // the box's bounded part (where a point's clamped coordinates fall), by which the candidates are tried nearest-first
-            auto dom_list = [&](const std::vector<int> &from, const double blo[3], const double bhi[3], const double lo[3], const double size,
-                                std::vector<std::pair<double, int>> &order, std::vector<int> &list) {
-                order.clear();
-                for (int j : from) {
-                    double d2 = 0.0;
-                    for (int d = 0; d < 3; ++d) {
-                        const double c = pts[3 * j + d];
-                        const double m = std::max(std::max(lo[d] - c, c - (lo[d] + size)), 0.0);
-                        d2 += m * m;
-                    }
-                    order.emplace_back(d2, j);
-                }
-                std::sort(order.begin(), order.end());
-                list.clear();
-                for (int j : from) {
-                    bool dominated = false;
-                    for (size_t kk = 0; kk < order.size() && !dominated; ++kk) {
-                        const int k = order[kk].second;
-                        if (k == j) continue;
-                        double mx = 0.0;
-                        for (int d = 0; d < 3; ++d) {
-                            const double a = 2.0 * (pts[3 * j + d] - pts[3 * k + d]);
-                            if (a > 0.0) mx += bhi[d] == kInfE ? kInfE : a * bhi[d];
-                            else if (a < 0.0) mx += blo[d] == -kInfE ? kInfE : a * blo[d];
-                            mx += pts[3 * k + d] * pts[3 * k + d] - pts[3 * j + d] * pts[3 * j + d];
-                        }
-                        if (mx < -1e-9 * (1.0 + std::fabs(mx))) dominated = true;
-                    }
-                    if (!dominated) list.push_back(j);
-                }
-            };
-            // A cell whose list is too long (a palette crowded at a face of the cube -- every palette under use_gamma, at the dark end)
-            // is cut into its eight half-size children like the 8^3 cells are: an outer child stays unbounded on its outer side, a point
-            // beyond the cube falls into it by its clamped coordinates.  Local node arrays, joined in cell order below.
-            struct XItem {
-                size_t slot;   // 0: the cell's own entry; else 1 + index into the local node array
-                double blo[3], bhi[3], lo[3], size;
-                std::vector<int> from;
-            };
-            std::vector<std::vector<U4>> xlocal(shell.size());   // per shell cell: [0] its entry, then its nodes' entries (8 per node)
-            parallel_cells((int)shell.size(), [&](const int i0, const int i1) {
-                std::vector<std::pair<double, int>> order;
-                std::vector<int> list;
-                std::vector<XItem> todo;
-                for (int si = i0; si < i1; ++si) {
-                    const int cell = shell[(size_t)si];
-                    const int ci[3] = {cell & 15, (cell >> 4) & 15, cell >> 8};
-                    std::vector<U4> &xl = xlocal[(size_t)si];
-                    xl.assign(1, make_u4(255u, 0u, 0u, 0u));
-                    XItem top;
-                    top.slot = 0;
-                    top.size = 16.0;
-                    for (int d = 0; d < 3; ++d) {
-                        top.lo[d] = (double)(ci[d] * 16);
-                        top.blo[d] = ci[d] == 0 ? -kInfE : top.lo[d];
-                        top.bhi[d] = ci[d] == 15 ? kInfE : top.lo[d] + 16.0;
-                    }
-                    top.from = all;
-                    todo.clear();
-                    todo.push_back(std::move(top));
-                    while (!todo.empty()) {
-                        XItem it = std::move(todo.back());
-                        todo.pop_back();
-                        dom_list(it.from, it.blo, it.bhi, it.lo, it.size, order, list);
-                        if ((int)list.size() <= cap) {
-                            xl[it.slot] = pack(list, it.lo, it.size);
-                            continue;
-                        }
-                        // (stays 255, the whole-palette scan: unit boxes; more than 24 nodes in one cell; and cells far from every
-                        // colour of the palette -- error diffusion keeps its values near the palette, and it is exactly the far
-                        // cells of a crowded palette, to which all its colours look alike, that are expensive to refine: with them
-                        // the tables of a 256-colour median-cut palette took 77 ms instead of 17)
-                        if (it.size <= 1.0 || (xl.size() - 1) / 8 >= 24 || order.empty() || order[0].first > 40.0 * 40.0) continue;
-                        const size_t node = (xl.size() - 1) / 8;
-                        xl[it.slot] = make_u4(254u | ((uint32_t)node << 8), 0u, 0u, 0u);
-                        xl.resize(xl.size() + 8, make_u4(255u, 0u, 0u, 0u));
-                        const double hs = it.size * 0.5;
-                        for (int sub = 0; sub < 8; ++sub) {
-                            XItem ch;
-                            ch.slot = 1 + 8 * node + (size_t)sub;
-                            ch.size = hs;
-                            for (int d = 0; d < 3; ++d) {
-                                const int bit = (sub >> d) & 1;
-                                ch.lo[d] = it.lo[d] + (bit ? hs : 0.0);
-                                ch.blo[d] = (!bit && it.blo[d] == -kInfE) ? -kInfE : ch.lo[d];
-                                ch.bhi[d] = (bit && it.bhi[d] == kInfE) ? kInfE : ch.lo[d] + hs;
-                            }
-                            ch.from = list;
-                            todo.push_back(std::move(ch));
-                        }
-                    }
-                }
-            }, 64);
-            std::vector<U4> &xn = out.ext_nodes;
-            xn.clear();
-            for (size_t si = 0; si < shell.size(); ++si) {
-                const std::vector<U4> &xl = xlocal[si];
-                const size_t base = xn.size() / 8;
-                U4 topw = xl[0];
-                if (xl.size() > 1 && base + (xl.size() - 1) / 8 > kEdExtMaxNodes) topw = make_u4(255u, 0u, 0u, 0u);   // no room: scan
-                else
-                    for (size_t i = 1; i < xl.size(); ++i) {
-                        U4 e = xl[i];
-                        if ((e.x & 255u) == 254u) e.x = 254u | ((uint32_t)(base + (e.x >> 8)) << 8);
-                        xn.push_back(e);
-                    }
-                if ((topw.x & 255u) == 254u) topw.x = 254u | ((uint32_t)(base + (topw.x >> 8)) << 8);
-                ext16[(size_t)shell[si]] = topw;
-            }
-        }
-        out.h4_wanted = 0;
-        out.h4_depth = 0.0;
-        out.h4_none = 0.0;
-        if (!wide && (what & 1)) {   // (its leaves hold index BYTES: palettes of up to 256 colours)
-        // The hierarchical table: a wave of the diffusion kernel pays for the LONGEST list among its 64 lanes, and with 256 random
-        // colours 12 % of the 16^3 cells, 0.8 % of the 8-wide and 0.03 % of the 4-wide cells have more than four possible nearest
-        // entries -- so a cell with more than four is cut into its eight 8-wide children, such a child into its 4-wide children,
-        // and every lane ends at a leaf of at most four (what is still longer at 4-wide keeps the lists above).
-        auto leaf = [&](const std::vector<int> &list, const double lo[3], const double size) -> uint32_t {
-            // filler: an unlisted entry far from the box, as pack() chooses it
-            const int oct = (lo[0] + 0.5 * size < 128.0 ? 1 : 0) | (lo[1] + 0.5 * size < 128.0 ? 2 : 0) | (lo[2] + 0.5 * size < 128.0 ? 4 : 0);
-            int filler = corner_entry[oct];
-            if (std::find(list.begin(), list.end(), filler) != list.end()) {
-                filler = -1;
-                double far_d = -1.0;
-                for (int j = 0; j < K; ++j) {
-                    if (std::find(list.begin(), list.end(), j) != list.end()) continue;
-                    double d2 = 0.0;
-                    for (int d = 0; d < 3; ++d) {
-                        const double m = pts[3 * j + d] - (lo[d] + 0.5 * size);
-                        d2 += m * m;
-                    }
-                    if (d2 > far_d) {
-                        far_d = d2;
-                        filler = j;
-                    }
-                }
-            }
-            int b[4];
-            for (int n = 0; n < 4; ++n) b[n] = n < (int)list.size() ? list[n] : filler;
-            // byte 0 < byte 1 marks a leaf: two distinct indices always exist (a list of one is padded with its filler)
-            if (b[0] > b[1]) std::swap(b[0], b[1]);
-            return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-        };
-        std::vector<std::vector<uint32_t>> local(4096);   // per cell: [0] its word (marker: local node 0), then its nodes' words
-        parallel_cells(4096, [&](const int c0, const int c1) {
-            // (depth-first: a box with more than four entries becomes a node of its eight half-size children, down to 2-wide boxes)
-            struct Item {
-                size_t slot;
-                double lo[3];
-                double size;
-                std::vector<int> from;
-            };
-            std::vector<Item> todo;
-            std::vector<int> list;
-            for (int cell = c0; cell < c1; ++cell) {
-                std::vector<uint32_t> &lw = local[cell];
-                lw.assign(1, kEdH4NoAnswer);
-                todo.clear();
-                Item top;
-                top.slot = 0;
-                top.lo[0] = (double)((cell & 15) * 16);
-                top.lo[1] = (double)(((cell >> 4) & 15) * 16);
-                top.lo[2] = (double)((cell >> 8) * 16);
-                top.size = 16.0;
-                todo.push_back(std::move(top));
-                while (!todo.empty()) {
-                    Item it = std::move(todo.back());
-                    todo.pop_back();
-                    if (it.size == 16.0) {
-                        list = top16[cell];   // (box_list + prune_list of the whole palette: done above)
-                    } else {
-                        box_list(it.from, it.lo, it.size, list);
-                        prune_list(it.lo, it.size, list);
-                    }
-                    if (list.size() <= 4) {
-                        lw[it.slot] = leaf(list, it.lo, it.size);
-                        continue;
-                    }
-                    if (it.size <= 2.0) continue;   // still longer in a 2-wide box: no answer here (the lists decide)
-                    const uint32_t node = (uint32_t)((lw.size() - 1) / 8);   // local node number of the children
-                    lw[it.slot] = 0x00ffu | (node << 16);
-                    lw.resize(lw.size() + 8, kEdH4NoAnswer);
-                    const double hs = it.size * 0.5;
-                    for (int sub = 0; sub < 8; ++sub) {
-                        Item ch;
-                        ch.slot = 1 + 8 * (size_t)node + (size_t)sub;
-                        ch.lo[0] = it.lo[0] + ((sub & 1) ? hs : 0.0);
-                        ch.lo[1] = it.lo[1] + ((sub & 2) ? hs : 0.0);
-                        ch.lo[2] = it.lo[2] + ((sub & 4) ? hs : 0.0);
-                        ch.size = hs;
-                        ch.from = list;
-                        todo.push_back(std::move(ch));
-                    }
-                }
-            }
-        });
-        std::vector<uint32_t> &h4 = out.h4;
-        out.h4_wanted = 0;
-        for (int cell = 0; cell < 4096; ++cell) out.h4_wanted += local[cell].size();
-        h4.assign(4096, kEdH4NoAnswer);
-        bool fits = true;
-        for (int cell = 0; cell < 4096 && fits; ++cell) {
-            const std::vector<uint32_t> &lw = local[cell];
-            if (lw.size() == 1) {
-                h4[cell] = lw[0];
-                continue;
-            }
-            const size_t base = (h4.size() - 4096) / 8;   // global number of this cell's local node 0
-            if (h4.size() + (lw.size() - 1) > kEdH4MaxWords || base + (lw.size() - 1) / 8 >= 0xffffu) {
-                fits = false;
-                break;
-            }
-            h4[cell] = 0x00ffu | ((uint32_t)base << 16);
-            for (size_t i = 1; i < lw.size(); ++i) {
-                uint32_t w = lw[i];
-                const bool marker = (w & 0xffu) >= ((w >> 8) & 0xffu);
-                if (marker && w != kEdH4NoAnswer) w = 0x00ffu | ((uint32_t)(base + (w >> 16)) << 16);
-                h4.push_back(w);
-            }
-        }
-        if (!fits) h4.clear();   // a clustered palette: the lists (and their octree refinement) serve it
-        out.h4_depth = 0.0;
-        out.h4_none = 0.0;
-        if (!h4.empty()) {
-            auto marker = [](const uint32_t w) { return (w & 0xffu) >= ((w >> 8) & 0xffu); };
-            double total = 0.0, none = 0.0;
-            for (int j = 0; j < K; ++j) {
-                uint32_t x[3];
-                for (int d = 0; d < 3; ++d) x[d] = (uint32_t)std::min(255.0, std::max(0.0, std::floor(pts[3 * j + d] + 0.5)));
-                uint32_t w = h4[(x[0] >> 4) | ((x[1] >> 4) << 4) | ((x[2] >> 4) << 8)];
-                int depth = 0;
-                for (int bit = 3; bit >= 1 && marker(w); --bit) {
-                    if ((w >> 16) == 0xffffu) break;
-                    w = h4[4096u + (size_t)(w >> 16) * 8u + (((x[0] >> bit) & 1u) | (((x[1] >> bit) & 1u) << 1) | (((x[2] >> bit) & 1u) << 2))];
-                    ++depth;
-                }
-                total += marker(w) ? 4.0 : (double)depth;
-                none += marker(w) ? 1.0 : 0.0;
-            }
-            out.h4_depth = total / (double)K;
-            out.h4_none = none / (double)K;
-        }
-        }
-    }
-    if (K <= 16 && (what & 1)) {
-        // lists of the 16x16x16 cells for the wavefront kernel's LDS: count | up to 7 indices, one nibble each
-        std::vector<uint32_t> &coarse = out.coarse;
-        coarse.resize(4096);
-        parallel_cells(4096, [&](const int c0, const int c1) {
-            std::vector<int> list;
-            for (int cell = c0; cell < c1; ++cell) {
-                const double lo[3] = {(double)((cell & 15) * 16), (double)(((cell >> 4) & 15) * 16), (double)((cell >> 8) * 16)};
-                box_list(all, lo, 16.0, list);
-                prune_list(lo, 16.0, list);
-                uint32_t word = 15u;
-                if (list.size() <= 7) {
-                    word = (uint32_t)list.size();
-                    for (size_t n = 0; n < list.size(); ++n) word |= (uint32_t)list[n] << (4 * (n + 1));
-                    // The unused positions name the entry farthest from the cell that is not on the list (K > 8 > list size:
-                    // there is one).  The key scan of nearest_color_cells evaluates every position of a group of 4 (or 7)
-                    // without a per-position validity test; an entry that is not listed can never be the nearest one, and
-                    // if it comes within the margin of the nearest the exact scan (which honours the count) decides.
-                    int filler = -1;
-                    double far_d = -1.0;
-                    for (int j = 0; j < K; ++j) {
-                        if (std::find(list.begin(), list.end(), j) != list.end()) continue;
-                        double near2 = 0.0;
-                        for (int k = 0; k < 3; ++k) {
-                            const double c = pts[3 * j + k];
-                            const double m = std::max(std::max(lo[k] - c, c - (lo[k] + 16.0)), 0.0);
-                            near2 += m * m;
-                        }
-                        if (near2 > far_d) {
-                            far_d = near2;
-                            filler = j;
-                        }
-                    }
-                    for (size_t n = list.size(); n < 7 && filler >= 0; ++n) word |= (uint32_t)filler << (4 * (n + 1));
-                }
-                coarse[cell] = word;
-            }
-        });
-        // The same table for query points that are NOT clamped to the cube (the perceptual / hybrid / adaptive-variance
-        // diffusers of vardiff.hip): a point is looked up in the cell of its clamped coordinates, so the outermost cells
-        // stand for everything beyond them -- their boxes are unbounded on that side.  With an unbounded box the geometric
-        // criterion lists everybody; the pairwise test alone decides (K <= 16: 256 pairs per cell): over a box that is
-        // unbounded in a direction in which |x - c_k|^2 - |x - c_j|^2 grows, k cannot dominate j.
-        std::vector<uint32_t> &ext = out.ext;
-        ext.resize(4096);
-        const double kInf = std::numeric_limits<double>::infinity();
-        parallel_cells(4096, [&](const int c0, const int c1) {
-            std::vector<int> list;
-            for (int cell = c0; cell < c1; ++cell) {
-                const int ci[3] = {cell & 15, (cell >> 4) & 15, cell >> 8};
-                double blo[3], bhi[3];
-                for (int d = 0; d < 3; ++d) {
-                    blo[d] = ci[d] == 0 ? -kInf : (double)(ci[d] * 16);
-                    bhi[d] = ci[d] == 15 ? kInf : (double)(ci[d] * 16 + 16);
-                }
-                list.clear();
-                for (int j = 0; j < K; ++j) {
-                    bool dominated = false;
-                    for (int k = 0; k < K && !dominated; ++k) {
-                        if (k == j) continue;
-                        double mx = 0.0;
-                        for (int d = 0; d < 3; ++d) {
-                            const double a = 2.0 * (pts[3 * j + d] - pts[3 * k + d]);
-                            if (a > 0.0) mx += bhi[d] == kInf ? kInf : a * bhi[d];
-                            else if (a < 0.0) mx += blo[d] == -kInf ? kInf : a * blo[d];
-                            mx += pts[3 * k + d] * pts[3 * k + d] - pts[3 * j + d] * pts[3 * j + d];
-                        }
-                        if (mx < -1e-9 * (1.0 + std::fabs(mx))) dominated = true;
-                    }
-                    if (!dominated) list.push_back(j);
-                }
-                uint32_t word = 15u;
-                if (list.size() <= 7) {
-                    word = (uint32_t)list.size();
-                    for (size_t n = 0; n < list.size(); ++n) word |= (uint32_t)list[n] << (4 * (n + 1));
-                    int filler = -1;
-                    double far_d = -1.0;
-                    for (int j = 0; j < K; ++j) {  // unused positions: the unlisted entry farthest from the cell's inner corner
-                        if (std::find(list.begin(), list.end(), j) != list.end()) continue;
-                        double d2 = 0.0;
-                        for (int d = 0; d < 3; ++d) {
-                            const double m = pts[3 * j + d] - (double)(ci[d] * 16 + 8);
-                            d2 += m * m;
-                        }
-                        if (d2 > far_d) {
-                            far_d = d2;
-                            filler = j;
-                        }
-                    }
-                    for (size_t n = list.size(); n < 7 && filler >= 0; ++n) word |= (uint32_t)filler << (4 * (n + 1));
-                }
-                ext[cell] = word;
-            }
-        });
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Median cut as the reference runs it (ColorReducer.reduce_colors, dithering_lib.py:1813-1843):

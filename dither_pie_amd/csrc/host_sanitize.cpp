@@ -1,13 +1,16 @@
-// CPU-sanitizer harness for the host logic of libditherpie_hip.so (host_logic.h): built WITHOUT HIP by
+// CPU-sanitizer harness for the host logic of libditherpie_hip.so (host_logic.h, ed_tables.h): built WITHOUT HIP by
 //   make host_asan   ->  build/host_asan   (g++ -fsanitize=address,undefined)
 //   make host_tsan   ->  build/host_tsan   (g++ -fsanitize=thread: the multi-threaded per-cell loops)
 // and run by tests/test_host_sanitizers.py in the CPU tier.  Test infrastructure, not part of the product library.
 //
 //   host_xxx kdtree   <pts.f64> <K>   the scipy-order KD-tree build; prints indices / nodes / splits (compared with
 //                                     the golden cKDTree structures by the test)
-//   host_xxx edtables <pts.f64> <K>   the diffusion candidate tables from host-made geometric lists (the criterion of
+//   host_xxx edtables <pts.f64> <K>   the diffusion candidate tables (ed_tables.h) from host-made geometric lists (the criterion of
 //                                     ed_cells_kernel), then checks on sampled points that the true nearest entry (and
 //                                     everything tied with it) is on the list the kernels would search
+//   host_xxx edtablesdigest <pts.f64> <K> <what>   the same tables (what: 1 = ed_tables_build, 2 = ed_ext_build, 3 = both) without
+//                                     any check: prints size and CRC-32 of every table's bytes on one line (compared with
+//                                     tests/golden/ed_tables_digests.json, which pins the tables' bytes)
 //   host_xxx accel    <pts.f64> <K> <bw>   the accelerator's cell table from brute-force membership masks (what
 //                                     accel_scan_kernel computes on the device), nearest sets, staging orders, wide
 //                                     lists, node reordering, warp maps; checks on sampled colours that the block a
@@ -134,13 +137,10 @@ static bool listed(const U4 &e, int n_max, int j, bool wide = false)
     return false;
 }
 
-static int run_edtables(const std::vector<double> &pts, int K)
+// the 8^3 lists as ed_cells_kernel leaves them: the geometric criterion, count 255 where a list is longer than the format holds
+static std::vector<U4> geometric_cells(const std::vector<double> &pts, int K)
 {
-    if (K < 9 || K > 1024) {
-        fprintf(stderr, "edtables: 9 <= K <= 1024\n");
-        return 2;
-    }
-    const bool wide = K > 256;   // ten-bit list entries (host_logic.h: ed_list_put)
+    const bool wide = K > 256;   // ten-bit list entries (ed_tables.h: ed_list_put)
     const int cap = ed_list_cap(K);
     std::vector<U4> cells(kEdCells);
     std::vector<int> list;
@@ -154,8 +154,54 @@ static int run_edtables(const std::vector<double> &pts, int K)
         }
         cells[cell] = make_u4(w[0], w[1], w[2], w[3]);
     }
+    return cells;
+}
+
+// what: 1 = the tables every diffusion kernel uses, 2 = the extended lists of the unclamped diffusers, 3 = both
+static void build_edtables(const std::vector<double> &pts, int K, int what, std::vector<U4> &cells, EdTables &tb)
+{
+    const EdPalette pal = ed_palette(pts.data(), K);
+    if (what & 1) ed_tables_build(pal, cells, tb);
+    if (what & 2) ed_ext_build(pal, tb);
+}
+
+// No self-check: size and CRC-32 of every table's bytes on one line, for tests/golden/ed_tables_digests.json.
+static int run_edtablesdigest(const std::vector<double> &pts, int K, int what)
+{
+    if (K < 9 || K > 1024 || what < 1 || what > 3) {
+        fprintf(stderr, "edtablesdigest: 9 <= K <= 1024, what 1, 2 or 3\n");
+        return 2;
+    }
+    std::vector<U4> cells = geometric_cells(pts, K);
     EdTables tb;
-    ed_tables_refine(pts.data(), K, cells, tb, 3);   // (the diffusion tables AND the extended lists of the unclamped diffusers)
+    build_edtables(pts, K, what, cells, tb);
+    auto digest = [](const char *name, const void *p, const size_t n, const size_t elem) {
+        printf(" %s=%zu:%08x", name, n, crc32_bytes(static_cast<const uint8_t *>(p), n * elem));
+    };
+    printf("edtablesdigest K=%d what=%d", K, what);
+    digest("cells", cells.data(), cells.size(), sizeof(U4));
+    digest("nodes", tb.nodes.data(), tb.nodes.size(), sizeof(U4));
+    digest("l16", tb.l16.data(), tb.l16.size(), sizeof(U4));
+    digest("coarse", tb.coarse.data(), tb.coarse.size(), sizeof(uint32_t));
+    digest("ext", tb.ext.data(), tb.ext.size(), sizeof(uint32_t));
+    digest("ext16", tb.ext16.data(), tb.ext16.size(), sizeof(U4));
+    digest("ext_nodes", tb.ext_nodes.data(), tb.ext_nodes.size(), sizeof(U4));
+    digest("h4", tb.h4.data(), tb.h4.size(), sizeof(uint32_t));
+    printf(" h4_wanted=%zu h4_depth=%.17g h4_none=%.17g\n", tb.h4_wanted, tb.h4_depth, tb.h4_none);
+    return 0;
+}
+
+static int run_edtables(const std::vector<double> &pts, int K)
+{
+    if (K < 9 || K > 1024) {
+        fprintf(stderr, "edtables: 9 <= K <= 1024\n");
+        return 2;
+    }
+    const bool wide = K > 256;   // ten-bit list entries (ed_tables.h: ed_list_put)
+    const int cap = ed_list_cap(K);
+    std::vector<U4> cells = geometric_cells(pts, K);
+    EdTables tb;
+    build_edtables(pts, K, 3, cells, tb);   // (the diffusion tables AND the extended lists of the unclamped diffusers)
     // sampled points: uniform integers, the palette entries themselves (rounded) and their neighbours
     uint32_t seed = 12345u + (uint32_t)K;
     long checked = 0, bad = 0, h4_answers = 0, h4_none = 0;
@@ -280,8 +326,8 @@ static int run_edtables(const std::vector<double> &pts, int K)
         }
     }
     printf("ext16=%zu nodes=%zu (checked %ld, in cells with long lists %ld) ", tb.ext16.size(), tb.ext_nodes.size() / 8, ext_checked, ext_long);
-    printf("edtables K=%d nodes=%zu give_up=%d l16=%zu coarse=%zu ext=%zu h4=%zu (answers %ld, none %ld) checked=%ld bad=%ld\n", K, tb.nodes.size(),
-           (int)tb.give_up, tb.l16.size(), tb.coarse.size(), tb.ext.size(), tb.h4.size(), h4_answers, h4_none, checked, bad);
+    printf("edtables K=%d nodes=%zu l16=%zu coarse=%zu ext=%zu h4=%zu (answers %ld, none %ld) checked=%ld bad=%ld\n", K, tb.nodes.size(),
+           tb.l16.size(), tb.coarse.size(), tb.ext.size(), tb.h4.size(), h4_answers, h4_none, checked, bad);
     if (K > 16 && !tb.h4.empty() && h4_answers < 100 * std::max(h4_none, 1L)) return 1;   // the table must answer nearly always
     return bad ? 1 : 0;
 }
@@ -1187,7 +1233,7 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1216,6 +1262,7 @@ int main(int argc, char **argv)
     const std::string cmd = argv[1];
     if (cmd == "kdtree") return run_kdtree(pts, K);
     if (cmd == "edtables") return run_edtables(pts, K);
+    if (cmd == "edtablesdigest") return run_edtablesdigest(pts, K, argc > 4 ? atoi(argv[4]) : 3);
     if (cmd == "accel") return run_accel(pts, K, argc > 4 ? atoi(argv[4]) : 8);
     return 2;
 }

@@ -1,5 +1,5 @@
 """CPU tier: the host logic of libditherpie_hip.so (dither_pie_amd/csrc/host_logic.h: scipy-order KD-tree build,
-accelerator table assembly, diffusion candidate tables with their multi-threaded per-cell loops) compiled WITHOUT HIP
+accelerator table assembly; ed_tables.h: diffusion candidate tables with their multi-threaded per-cell loops) compiled WITHOUT HIP
 behind dither_pie_amd/csrc/host_sanitize.cpp, once with -fsanitize=address,undefined and once with -fsanitize=thread
 (`make -C dither_pie_amd/csrc host_asan host_tsan`), and run on the golden cKDTree palettes.  A sanitizer report makes
 the process exit non-zero (halt_on_error), a failed self-check exits 1."""
@@ -57,9 +57,9 @@ def _crowded(K, seed):
 
 @pytest.mark.parametrize("san", ["asan", "tsan"])
 def test_diffusion_tables_under_sanitizers(tools, gold, tmp_path, san):
-    """ed_tables_refine with its up-to-8-thread per-cell loops: random / uniform-grid / float (gamma) / crowded palettes
-    (the crowded ones overflow cells and go through the octree refinement); the harness checks on 40 000 points that the
-    true nearest entries are on every list a kernel would search."""
+    """ed_tables_build and ed_ext_build (ed_tables.h) with their up-to-8-thread per-cell loops: random / uniform-grid / float
+    (gamma) / crowded palettes (the crowded ones overflow cells and go through the octree refinement); the harness checks on
+    40 000 points that the true nearest entries are on every list a kernel would search."""
     wide = np.random.RandomState(5).randint(0, 256, (700, 3)).astype(np.float64)   # 257..1024 colours: ten-bit list entries
     cases = [gold["tree_p256_pts"], gold["tree_p32_pts"], gold["tree_p11_pts"], gold["tree_U16_pts"], gold["tree_lin256_pts"],
              gold["tree_dup40_pts"], _crowded(200, 1), _crowded(16, 2), wide, _crowded(300, 3)]
@@ -68,6 +68,51 @@ def test_diffusion_tables_under_sanitizers(tools, gold, tmp_path, san):
     for pts in cases:
         out = _run(tools[san], "edtables", pts, tmp_path)
         assert " bad=0" in out, out
+
+
+def _digest_palettes(gold):
+    """name -> palette of the table-digest cases: between them they take every branch of the table builders."""
+    R = np.random.RandomState
+    rs = R(21)
+    base = rs.randint(0, 256, (50, 3))
+    t = np.linspace(0, 2 * np.pi, 256, endpoint=False)
+    pal = {
+        "rand11": R(11).randint(0, 256, (11, 3)),                       # nibble tables coarse and ext
+        "crowd16": _crowded(16, 2),                                     # K = 16 edge of the nibble path
+        "rand32": R(32).randint(0, 256, (32, 3)),                       # plain l16, ext16, h4; no nodes
+        "rand256": R(256).randint(0, 256, (256, 3)),                    # ext_nodes present
+        "crowd200": _crowded(200, 1),                                   # 8^3 octree nodes, h4 kept
+        "crowd300": _crowded(300, 3),                                   # ten-bit entries, nodes, duplicates
+        "wide700": R(5).randint(0, 256, (700, 3)),                      # ten-bit entries, many ext_nodes
+        "wide1024crowd": np.clip(np.round(20 + R(6).randn(1024, 3) * 12), 0, 255),   # K = 1024; nodes and ext_nodes
+        "dark256": np.clip(np.round(4 + R(7).randn(256, 3) * 6), 0, 255),            # crowded at a cube face: ext16 refinement
+        "gamma64": 255 * R(3).rand(64, 3) ** 2.2,                       # non-integer coordinates
+        "dup5": np.concatenate([np.repeat(base, 5, axis=0), rs.randint(0, 256, (6, 3))]),   # h4 does not fit; ext_nodes full
+        "ring256": np.round(np.stack([128 + 100 * np.cos(t), 128 + 100 * np.sin(t), np.full(256, 128.0)], axis=1)),   # exact ties
+    }
+    for nm in ("lin256", "dup40", "U16"):                               # collinear colours, duplicates, uniform grid
+        pal["tree_" + nm] = gold[f"tree_{nm}_pts"]
+    return {k: np.asarray(v, np.float64) for k, v in pal.items()}
+
+
+def _digest_cases():
+    names = ["rand11", "crowd16", "rand32", "rand256", "crowd200", "crowd300", "wide700", "wide1024crowd", "dark256", "gamma64", "dup5",
+             "ring256", "tree_lin256", "tree_dup40", "tree_U16"]
+    # both entry points together everywhere; each alone where the other's tables are not trivial
+    return [(nm, 3) for nm in names] + [(nm, what) for nm in ("rand256", "crowd200", "dup5") for what in (1, 2)]
+
+
+@pytest.mark.parametrize("name,what", _digest_cases())
+def test_diffusion_tables_keep_their_bytes(tools, gold, tmp_path, name, what):
+    """Every table of ed_tables_build (what 1) and ed_ext_build (what 2), and of both on one EdTables (what 3): size and CRC-32 of
+    its bytes, and the h4 statistics to 17 digits, equal the lines in tests/golden/ed_tables_digests.json.  Those lines come from
+    the one function that built all the tables before the builders were separated; they are never regenerated from the
+    builders themselves, so they pin the tables' bytes across that change and every later one."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "ed_tables_digests.json")) as f:
+        recorded = json.load(f)
+    out = _run(tools["asan"], "edtablesdigest", _digest_palettes(gold)[name], tmp_path, what)
+    assert out.strip() == recorded[f"{name}/{what}"]
 
 
 @pytest.mark.parametrize("san", ["asan", "tsan"])

@@ -3,7 +3,7 @@ result; the generator's predicted queries equal that report bit for bit in every
 the floors of steer_ref's docstring hold -- all of it read from the oracle's report, nothing from a device.
 
 (The mutation check the design asked for -- corrupt one candidate list of the host tables and watch a gap target fall into it --
-is not here: ed_tables_refine is not reachable through the host C ABI, only from the library's own launch path.)"""
+is not here: ed_tables_build (ed_tables.h) is not reachable through the host C ABI, only from the library's own launch path.)"""
 import numpy as np
 import pytest
 

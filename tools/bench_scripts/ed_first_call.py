@@ -1,5 +1,5 @@
 """What the FIRST error-diffusion call on a fresh palette pays on top of the frame (KD-tree, 8^3 cell lists and their octree, 16^3
-lists, hierarchical table -- host_logic.h: ed_tables_refine; built on first use): first against second call, one 4K frame."""
+lists, hierarchical table -- ed_tables.h: ed_tables_build; built on first use): first against second call, one 4K frame."""
 import sys, time
 sys.path.insert(0, '.')
 import numpy as np, torch
