@@ -630,6 +630,7 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
     dev.warp_tab = nullptr;
     dev.warp_lut = nullptr;
     dev.warp_words = dev.warp_total = dev.warp_bw = dev.warp_adapt = 0;
+    dev.warp_slow_blocks = wbw != 0 ? wst.n_slow : 0;
     dev.adapt = (!use4 && u_crowded) ? 1 : 0;
     if (wbw != 0) {
         e = hipMemcpy(d_wtab, wtab.data(), sizeof(uint32_t) * wtab.size(), hipMemcpyHostToDevice);
@@ -777,6 +778,9 @@ int build_accel(PalDev &dev, const std::vector<uint32_t> &p4_host, void **blob_o
         dev.exc = d_exc;
         dev.n_exc = n_exc <= (uint32_t)kExcCap ? (int)n_exc : -1;
     }
+    // what decides whether a call with this palette keeps its fix-up pass (ordered_fix.h)
+    if (exp_env("DP_DEBUG_ACCEL"))
+        fprintf(stderr, "accel K=%d: fix-up facts: slow_blocks=%d warp_slow_blocks=%d n_exc=%d\n", K, dev.n_slow_blocks, dev.warp_slow_blocks, dev.n_exc);
     *blob_out = blob;
     *blob_bytes = bytes;
     return DP_OK;

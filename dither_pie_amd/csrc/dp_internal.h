@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -151,7 +152,10 @@ struct PalDev {
     int ed_h4_lds_words;        // the few-frames instances stage it in LDS up to this size (set per launch)
     const uint4 *exc;           // colours whose outcome no code expresses, sorted by colour:
     int n_exc;                  //   {colour, k=2 indices i0 | i1<<16, k=1 index, 0}; n_exc < 0: list overflowed
+    int warp_slow_blocks;       // 0xC0000000 markers of warp_tab, as n_slow_blocks counts those of cell_tab (host side only: ordered_fix.h;
+                                // in what was the struct's tail padding, so the kernels' arguments are where they were)
 };
+static_assert(sizeof(PalDev) == offsetof(PalDev, warp_slow_blocks) + sizeof(int), "warp_slow_blocks fills the tail padding");
 
 struct ThrDev {
     int th_h, th_w;

@@ -60,6 +60,8 @@
 //                                     base and with garbage in bits 24-31; then, whatever the range, every rank and sub-cell:
 //                                     fine_stage_tag / fine_stage_tags2 / fine_tag_rank and fine_row_address against rows_at + 16 * rank
 //                                     + 2 * sub-cell on the 64 colours of the sub-cell; prints the counts and the number of mismatches
+//   host_xxx fixneeded <cases.bin> <n>   whether a call keeps its fix-up pass (ordered_fix.h: fix_needed): n records of one FixFacts and
+//                                     one FixSwitches; prints 0 / 1 per line (compared with tests/ordered_fix_ref.py by the test)
 // Exit code 0 = all checks passed (and the sanitizer had nothing to say).
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +71,7 @@
 #include "host_logic.h"
 #include "ordered_plan.h"
 #include "ordered_fine.h"
+#include "ordered_fix.h"
 
 using namespace dp;
 
@@ -1003,6 +1006,28 @@ static int run_finechoice(const char *path, const int n_cases)
     return 0;
 }
 
+static int run_fixneeded(const char *path, const int n_cases)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        FixFacts ff;
+        FixSwitches sw;
+        if (fread(&ff, sizeof(ff), 1, f) != 1 || fread(&sw, sizeof(sw), 1, f) != 1 || ff.family < kFamBrute || ff.family > kFamCompactFloat ||
+            ff.table < kTabPlain8 || ff.table > kTabWarped || ff.slow_blocks < 0) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            fclose(f);
+            return 2;
+        }
+        printf("fix %d %s %d\n", c, family_name((OrderedFamily)ff.family), (int)fix_needed(ff, sw));
+    }
+    fclose(f);
+    return 0;
+}
+
 static int run_finekeys(const char *path, const int n_cases)
 {
     FILE *f = fopen(path, "rb");
@@ -1233,7 +1258,7 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  fixneeded <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1252,6 +1277,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "finesublevel") return run_finesublevel(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "finechoice") return run_finechoice(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "fineaddr") return run_fineaddr(atol(argv[2]), atol(argv[3]));
+    if (std::string(argv[1]) == "fixneeded") return run_fixneeded(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "idiffplan") return run_idiffplan(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));

@@ -22,6 +22,7 @@
 #include "dp_internal.h"
 #include "ordered_plan.h"
 #include "ordered_fine.h"
+#include "ordered_fix.h"
 #include "tree_query.hip.h"
 #include "ordered_cand.hip.h"
 
@@ -1743,6 +1744,8 @@ __global__ __launch_bounds__(kCellBlock) void ordered_fast_kernel(const uint8_t 
 // build only): the main loop is SUB 0's -- the tags are staged as window 0 -- and the deferred path ranks a wide cell's pixel on its
 // sub-cell's window in LDS (resolve_window) instead of the sixteen entries of the global list.  LDS:
 //   quads A | norms of A | pairs B | window or tag of every cell | rows [n_wide x 8 u16] | thresholds
+// NOFLAGS (ordered_fix.h: fix_needed says no): the call has no fix-up pass, so the kernel neither clears the tile's flag words nor
+// has a flag to set; the queue, the drains and the deferred path are the same.
 // ---------------------------------------------------------------------------------------------
 
 // (the byte offset of the window number of x's cell, fine_cell_offset, and the address of a tagged cell's row entry,
@@ -1789,7 +1792,8 @@ __device__ __forceinline__ bool resolve_window(const uint32_t x, const LeanThr &
 // in memory; returns the entry without that pixel.  KEYS > 0: the flat lists of the wide cells are read where the table image has
 // them in global memory (pal.fine_tab, behind the quads), not from LDS.  SUB 2: a tagged cell's pixel takes the flat list the tag
 // names where its sub-cell is still wide (row entry 0), and the index-ordered table like every other deferred pixel where it is not.
-template <int MODE, int KEYS, int SUB>
+// NOFLAGS: the palette can never flag a pixel (ordered_fix.h: fix_needed), `flags` and Geo::dirty are not touched.
+template <int MODE, int KEYS, int SUB, bool NOFLAGS>
 __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                     unsigned long long *__restrict__ flags, const Geo &g, const PalDev &pal,
                                                     const ThrDev &thr, const uint32_t *s_words, const FineLds &at)
@@ -1840,12 +1844,14 @@ __device__ __forceinline__ uint32_t fine_pixel_full(const uint32_t entry, const 
     o[0] = (uint8_t)c;
     o[1] = (uint8_t)(c >> 8);
     o[2] = (uint8_t)(c >> 16);
-    if (slow) flag_slow_pixel(p, flags, g);
+    if constexpr (!NOFLAGS) {
+        if (slow) flag_slow_pixel(p, flags, g);
+    }
     const uint32_t rest = mask & (mask - 1u);
     return rest ? ((entry & ~15u) | rest) : 0u;
 }
 
-template <int MODE, int KEYS, int SUB = 0>
+template <int MODE, int KEYS, int SUB = 0, bool NOFLAGS = false>
 __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
                                                                     unsigned long long *__restrict__ flags, const Geo g,
                                                                     const PalDev pal, const ThrDev thr, const float sx, const float sy,
@@ -1956,7 +1962,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
         qcount -= n;
         __threadfence_block();  // the group stores that are about to be overwritten
         uint32_t rest = 0u;
-        if (lane < n) rest = fine_pixel_full<MODE, KEYS, SUB>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
+        if (lane < n) rest = fine_pixel_full<MODE, KEYS, SUB, NOFLAGS>(s_queue[qcount + lane], in, out, flags, g, pal, thr, smem, at);
         queue_push(s_queue, qcount, rest != 0u, rest);  // groups with a further deferred pixel go back
     };
 
@@ -2026,7 +2032,7 @@ __global__ __launch_bounds__(kCellBlock, 4) void ordered_fine_kernel(const uint8
             cls_word = 0;
             if (next < n_tiles) tile_class(fy, fx, gn);
         }
-        clear_flags(flags, gidx, lane);
+        if constexpr (!NOFLAGS) clear_flags(flags, gidx, lane);
         bool rare[4] = {false, false, false, false};
         if (gidx < n_full) {
             constexpr int kPairShift = KEYS == 2 ? 4 : 3;  // pairs B of 8 B / records B' of 16 B
@@ -2844,21 +2850,23 @@ int num_cus()
 // product library compiles to nothing here
 // `fc.fine`: ordered_fine_kernel runs in place of the plan's kernel (ordered_fine.h: choose_fine); the line then ends in
 // "kernel=fine keys=<level> sub=<level>"
-static inline void trace_plan(const OrderedPlan &p, bool aligned, const FineChoice &fc)
+// `fix`: the memset of the count and the fix-up launch surround the kernel (ordered_fix.h: fix_needed); " fix=0|1" ends every line
+static inline void trace_plan(const OrderedPlan &p, bool aligned, const FineChoice &fc, const bool fix)
 {
 #ifdef DP_EXPERIMENTS
     if (std::getenv("DP_ORDERED_TRACE")) {
         constexpr const char *tables[] = {"plain8", "plain4", "warped"};
         char keys_s[32] = "";
         if (fc.fine) snprintf(keys_s, sizeof(keys_s), " keys=%d sub=%d", fc.keys, fc.sub);
-        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s%s\n",
+        fprintf(stderr, "dp_ordered_u8: pass 1 = %s (4-byte aligned frames: %d) mode=%d bw=%d adapt=%d warp=%d half=%d table=%s fix_big_queue=%d kernel=%s%s fix=%d\n",
                 family_name(p.family), aligned ? 1 : 0, p.mode, p.bw, p.adapt ? 1 : 0, p.warp ? 1 : 0, p.half ? 1 : 0, tables[p.table],
-                p.fix_big_queue ? 1 : 0, fc.fine ? "fine" : family_name(p.family), keys_s);
+                p.fix_big_queue ? 1 : 0, fc.fine ? "fine" : family_name(p.family), keys_s, fix ? 1 : 0);
     }
 #else
     (void)p;
     (void)aligned;
     (void)fc;
+    (void)fix;
 #endif
 }
 
@@ -2916,19 +2924,25 @@ TileKernel tile_kernel(const OrderedPlan &p)
 // build only, the A/B partner that showed it slower than level 1) and a SUB level (fine_sub_level, kFineSubShipped): the instances
 // fine_instance (ordered_fine.h) lists for this build, no more and no fewer.  (The order in which the instances are named here is
 // the order of the kernels in the device code: renaming them in another order gives a different code object.)
-TileKernel fine_kernel(const int keys, const int sub)
+// Every instance twice: as it was, and NOFLAGS for the calls without a fix-up pass (ordered_fix.h).
+template <bool NOFLAGS>
+TileKernel fine_kernel_of(const int keys, const int sub)
 {
-    if (!fine_instance(keys, sub, kExperiments)) return nullptr;
-    if (sub == 2) return ordered_fine_kernel<1, 1, 2>;
+    if (sub == 2) return ordered_fine_kernel<1, 1, 2, NOFLAGS>;
 #ifdef DP_EXPERIMENTS
-    if (sub == 1) return ordered_fine_kernel<1, 1, 1>;
+    if (sub == 1) return ordered_fine_kernel<1, 1, 1, NOFLAGS>;
 #endif
-    if (keys == 0) return ordered_fine_kernel<1, 0>;
-    if (keys == 1) return ordered_fine_kernel<1, 1>;
+    if (keys == 0) return ordered_fine_kernel<1, 0, 0, NOFLAGS>;
+    if (keys == 1) return ordered_fine_kernel<1, 1, 0, NOFLAGS>;
 #ifdef DP_EXPERIMENTS
-    if (keys == 2) return ordered_fine_kernel<1, 2>;
+    if (keys == 2) return ordered_fine_kernel<1, 2, 0, NOFLAGS>;
 #endif
     return nullptr;  // (not reached: the predicate lists nothing else)
+}
+TileKernel fine_kernel(const int keys, const int sub, const bool noflags)
+{
+    if (!fine_instance(keys, sub, kExperiments)) return nullptr;
+    return noflags ? fine_kernel_of<true>(keys, sub) : fine_kernel_of<false>(keys, sub);
 }
 
 // (ordered_f64_kernel<1> is named but never planned: MODE 1 needs an integer palette)
@@ -2990,6 +3004,8 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
     FineSwitches fsw{exp_env("DP_NO_FINE_KERNEL") != nullptr, kFineKeysShipped, kFineSubShipped};
     if (const char *cap = exp_env("DP_FINE_KEYS_MAX")) fsw.keys_cap = std::min(2, std::max(0, std::atoi(cap)));
     if (const char *cap = exp_env("DP_FINE_SUB_MAX")) fsw.sub_cap = std::min(2, std::max(0, std::atoi(cap)));
+    // ... and of the fix-up pass's (ordered_fix.h: fix_needed): DP_ALWAYS_FIXUP keeps the three dispatches whatever the palette
+    const FixSwitches xsw{exp_env("DP_ALWAYS_FIXUP") != nullptr};
 
     const float sx = (float)((double)ign_seed * 0.37), sy = (float)((double)ign_seed * 0.73);
     const int64_t hw = (int64_t)h * w;
@@ -3025,14 +3041,19 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
         // the fine kernel takes over the lean kernel's plan (grid, tile stride, fix-up pass) where a table of its exists and fits
         const FineChoice fc = choose_fine(plan, FineTables{pal.fine_tab != nullptr, pal.fine_win, pal.fine_wide, pal.fsub_tab != nullptr,
                                                            pal.fsub_win, pal.fsub_wide, thr.th_h * thr.tw_pad * 4}, fsw);
+        // a palette that can never flag a pixel needs neither the count reset nor the fix-up launch (the lean kernels then clear a
+        // bitmap nobody reads; the fine kernel has instances that do not)
+        const int slow_blocks = plan.table == kTabWarped ? pal.warp_slow_blocks : (plan.table == kTabPlain4 ? 0 : pal.n_slow_blocks);
+        const bool fix = fix_needed(FixFacts{plan.family, fc.fine, pal.is_integer, pal.code1 != nullptr && pal.code2 != nullptr && pal.exc != nullptr,
+                                             plan.table, slow_blocks, pal.n_exc}, xsw);
         const BruteKernel brute_k = brute ? brute_kernel(plan, pal.is_integer != 0) : nullptr;
-        const TileKernel tile_k = brute ? nullptr : (fc.fine ? fine_kernel(fc.keys, fc.sub) : tile_kernel(plan));
+        const TileKernel tile_k = brute ? nullptr : (fc.fine ? fine_kernel(fc.keys, fc.sub, !fix) : tile_kernel(plan));
         const FixKernel fix_k = fix_kernel(plan);
         if ((brute ? brute_k == nullptr : tile_k == nullptr) || fix_k == nullptr) {
             set_error("dp_ordered_u8: no %s kernel for mode %d", family_name(plan.family), plan.mode);
             return DP_EUNSUPPORTED;
         }
-        DP_HIP(hipMemsetAsync(g.dirty, 0, sizeof(uint32_t), s));  // the count; queue entries need no reset
+        if (fix) DP_HIP(hipMemsetAsync(g.dirty, 0, sizeof(uint32_t), s));  // the count; queue entries need no reset
         ProfMark *pm = prof_begin(s);
         if (brute) {
             hipLaunchKernelGGL(brute_k, dim3(plan.grid), dim3(plan.block), 0, s, in_c, out_c, fl, g, pal, thr, sx, sy, ign_scale);
@@ -3055,10 +3076,12 @@ int launch_ordered(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
                                plan.n_tiles);
         }
         DP_HIP(hipGetLastError());
-        trace_plan(plan, g.aligned, fc);
-        prof_mid(pm, s);
-        hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
-        prof_end(pm, s);
+        trace_plan(plan, g.aligned, fc, fix);
+        if (fix) {
+            prof_mid(pm, s);
+            hipLaunchKernelGGL(fix_k, dim3(plan.fix_grid), dim3(kBlock), 0, s, in_c, out_c, fl, plan.n_words, g, pal, thr, sx, sy, ign_scale);
+        }
+        prof_end(pm, s);  // (records the middle mark itself where there was no fix-up pass)
         DP_HIP(hipGetLastError());
     }
     return DP_OK;
