@@ -251,6 +251,26 @@ _SIGS_RESAMPLE = {
     "dp_resample_host": (_i, [_i, _vp, _vp, _i64, _i, _i, _i, _i]),
 }
 EXPORTS_RESAMPLE = tuple(_SIGS_RESAMPLE)
+# include/ditherpie_hip_hold.h: the temporal hold for video (cells whose source has not moved keep their indices) and its host
+# statement; a table of its own for the same reason.  dp_hold_u8 and dp_hold_host_u8 take a descriptor, as dp_resample_u8 does.
+HOLD_CELLS = (1, 2, 4, 8, 16)
+HOLD_MAX_FRAMES = 65535     # DP_HOLD_MAX_FRAMES: frames per call
+
+
+class HoldArgs(C.Structure):
+    """dp_hold_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("src_dev", C.c_void_p), ("planes_dev", C.c_void_p), ("n_frames", C.c_int64),
+                ("h", C.c_int), ("w", C.c_int), ("cell", C.c_int), ("tol", C.c_int), ("share256", C.c_int),
+                ("anchor_dev", C.c_void_p), ("held_dev", C.c_void_p), ("has_state", C.c_int), ("out_dev", C.c_void_p),
+                ("refreshed_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+_SIGS_HOLD = {
+    "dp_hold_u8": (_i, [C.POINTER(HoldArgs)]),
+    "dp_hold_host_u8": (_i, [C.POINTER(HoldArgs)]),
+    "dp_hold_state_bytes": (_i, [_i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
+}
+EXPORTS_HOLD = tuple(_SIGS_HOLD)
 
 
 def build(force=False):
@@ -297,7 +317,8 @@ def load():
                                           + list(_SIGS_PNG_FILE.items()) + list(_SIGS_DOTDIFF.items())
                                           + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
                                           + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())
-                                          + list(_SIGS_OKFIT.items()) + list(_SIGS_RESAMPLE.items())):
+                                          + list(_SIGS_OKFIT.items()) + list(_SIGS_RESAMPLE.items())
+                                          + list(_SIGS_HOLD.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

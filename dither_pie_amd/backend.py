@@ -1721,6 +1721,189 @@ class DeltaStream:
         return self
 
 
+# ------------------------------------------------------------------------------------- temporal hold
+# include/ditherpie_hip_hold.h.  Cells of a video whose source has not moved keep the indices they show; it sits between the
+# dither's index planes and the inter-frame delta above.
+HOLD_CELLS = _lib.HOLD_CELLS
+HOLD_MAX_FRAMES = _lib.HOLD_MAX_FRAMES
+
+
+def _hold_settings(cell, tol, share256):
+    try:
+        c, t, s = int(cell), int(tol), int(share256)
+    except (TypeError, ValueError):
+        raise ValueError(f"cell, tol and share256 must be integers, not {cell!r}, {tol!r}, {share256!r}") from None
+    if c not in HOLD_CELLS or c != cell:
+        raise ValueError(f"cell must be one of {HOLD_CELLS}, not {cell!r}")
+    if not 0 <= t <= 255 or t != tol:
+        raise ValueError(f"tol must be an integer in 0 ... 255, not {tol!r}")
+    if not 0 <= s <= 256 or s != share256:
+        raise ValueError(f"share256 must be an integer in 0 ... 256, not {share256!r}")
+    return c, t, s
+
+
+def _hold_geometry(n, h, w):
+    if h < 1 or w < 1 or h * w >= 1 << 31:
+        raise ValueError(f"frames of {h} x {w}: h and w must be >= 1 and h * w below 2^31")
+
+
+def _hold_inputs(src, planes):
+    """-> contiguous src [N,H,W,3] and planes [N,H,W] (uint8 CUDA tensors of one device and one geometry)"""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+        raise TypeError("src must be a CUDA uint8 tensor")
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda):
+        raise TypeError("planes must be a CUDA tensor")
+    if planes.dtype != torch.uint8:
+        raise ValueError(f"planes must be one-byte indices (torch.uint8), not {planes.dtype}: the hold takes at most 256 colours")
+    if src.dim() != 4 or src.shape[-1] != 3 or planes.dim() != 3 or tuple(planes.shape) != tuple(src.shape[:3]):
+        raise ValueError(f"src must be [N,H,W,3] and planes [N,H,W] of the same frames, not {tuple(src.shape)} and {tuple(planes.shape)}")
+    if planes.device != src.device:
+        raise ValueError(f"src is on {src.device}, planes on {planes.device}")
+    return src.contiguous(), planes.contiguous()
+
+
+def _hold_into(s, p, anchor, held, has_state, cell, tol, share256, out, refreshed):
+    n, h, w = p.shape
+    L = _lib.load()
+    for a in range(0, n, HOLD_MAX_FRAMES):
+        b = min(n, a + HOLD_MAX_FRAMES)
+        args = _lib.HoldArgs(C.sizeof(_lib.HoldArgs), s[a:b].data_ptr(), p[a:b].data_ptr(), b - a, h, w, cell, tol, share256, anchor.data_ptr(),
+                             held.data_ptr(), 1 if (has_state or a) else 0, out[a:b].data_ptr(), refreshed[a:b].data_ptr(), _stream().value)
+        check(L.dp_hold_u8(C.byref(args)))
+
+
+def hold(src, planes, state, cell, tol, share256, out=None):
+    """The temporal hold of one batch (dp_hold_u8, include/ditherpie_hip_hold.h): src [N,H,W,3] uint8 CUDA frames as handed to the
+    ditherer, planes [N,H,W] uint8 their fresh dither -> (out [N,H,W] uint8, refreshed [N] int64 on the device, state').
+    state: None for the first frame of a stream, else the (anchor [H,W,3], held [H,W]) pair an earlier call returned; a given
+    pair is UPDATED in place and returned (HoldStream does the bookkeeping).  A cell of cell x cell pixels refreshes -- takes the
+    fresh indices -- when at least share256 / 256 of its pixels (and one at least) differ from their anchor by more than tol in
+    some channel; every other pixel keeps what it showed.  One kernel launch per 65535 frames, nothing read back; `out` must not
+    be the planes.  ValueError for two-byte planes: the hold takes at most 256 colours."""
+    cell, tol, share256 = _hold_settings(cell, tol, share256)
+    s, p = _hold_inputs(src, planes)
+    n, h, w = p.shape
+    _hold_geometry(n, h, w)
+    dev = p.device
+    if state is None:
+        anchor = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        held = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    else:
+        anchor = _check_buffer(state[0], dev, (h, w, 3), torch.uint8, "state anchor")
+        held = _check_buffer(state[1], dev, (h, w), torch.uint8, "state held")
+    res = _check_buffer(out, dev, (n, h, w), torch.uint8, "out")
+    refreshed = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return res, refreshed, state
+    if res.data_ptr() == p.data_ptr():
+        raise ValueError("hold does not work in place: out must not be the planes")
+    with torch.cuda.device(dev):
+        _hold_into(s, p, anchor, held, state is not None, cell, tol, share256, res, refreshed)
+    return res, refreshed, (anchor, held)
+
+
+def hold_host(src, planes, state, cell, tol, share256):
+    """The same on the CPU (dp_hold_host_u8: the host statement of the kernel): numpy arrays in and out, state None or (anchor,
+    held), which is NOT modified -> (out, refreshed, state').  Needs no device."""
+    cell, tol, share256 = _hold_settings(cell, tol, share256)
+    s, p = np.ascontiguousarray(src), np.ascontiguousarray(planes)
+    if s.dtype != np.uint8 or s.ndim != 4 or s.shape[-1] != 3:
+        raise ValueError("src must be [N,H,W,3] uint8")
+    if p.dtype != np.uint8:
+        raise ValueError(f"planes must be one-byte indices (uint8), not {p.dtype}: the hold takes at most 256 colours")
+    if p.shape != s.shape[:3]:
+        raise ValueError(f"planes must be [N,H,W] of the same frames, not {p.shape} beside {s.shape}")
+    n, h, w = p.shape
+    _hold_geometry(n, h, w)
+    if state is None:
+        anchor, held = np.empty((h, w, 3), np.uint8), np.empty((h, w), np.uint8)
+    else:
+        anchor, held = np.array(state[0], dtype=np.uint8, order="C"), np.array(state[1], dtype=np.uint8, order="C")
+        if anchor.shape != (h, w, 3) or held.shape != (h, w):
+            raise ValueError(f"the state must be (anchor [{h},{w},3], held [{h},{w}])")
+    out, refreshed = np.empty((n, h, w), np.uint8), np.empty(n, np.int64)
+    if n == 0:
+        return out, refreshed, state
+    args = _lib.HoldArgs(C.sizeof(_lib.HoldArgs), s.ctypes.data, p.ctypes.data, n, h, w, cell, tol, share256, anchor.ctypes.data, held.ctypes.data,
+                         0 if state is None else 1, out.ctypes.data, refreshed.ctypes.data, None)
+    check(_lib.load().dp_hold_host_u8(C.byref(args)))
+    return out, refreshed, (anchor, held)
+
+
+class HoldStream:
+    """The temporal hold over a STREAM of batches: add(src, planes) -> (out, refreshed) as hold(), with the anchor and the held
+    indices resident between calls (4 H W bytes), so the result does not depend on how the stream was cut into batches; the very
+    first frame, and the first after reset(), refreshes everywhere.  cell, tol and share (the fraction of a cell's pixels that must
+    have changed, rounded to 256ths) are fixed for the object's life; the defaults (8, 4, 1/16) are untuned design choices
+    (DESIGN.md 8).  `palette` is the caller's note of the palette the held indices belong to: process_frames_indexed resets the
+    stream when it changes.  Calls into one object are ordered on one stream (the caller's current one)."""
+
+    def __init__(self, device=None, cell=8, tol=4, share=1 / 16):
+        require_gpu()
+        dev = torch.device(device or "cuda")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.cell, self.tol, self.share256 = _hold_settings(cell, tol, min(256, max(0, int(round(float(share) * 256)))))
+        self.anchor = self.held = None
+        self._has_state = False
+        self.palette = None
+
+    @property
+    def settings(self):
+        """(cell, tol, share256)"""
+        return self.cell, self.tol, self.share256
+
+    def reset(self):
+        """Forget the state: the next frame refreshes everywhere."""
+        self._has_state = False
+        self.palette = None
+        return self
+
+    def add(self, src, planes):
+        s, p = _hold_inputs(src, planes)
+        if p.device != self.device:
+            raise ValueError(f"the hold stream lives on {self.device}, planes on {p.device}")
+        n, h, w = p.shape
+        if n == 0:
+            return torch.empty_like(p), torch.empty(0, dtype=torch.int64, device=self.device)
+        _hold_geometry(n, h, w)
+        if self._has_state and tuple(self.held.shape) != (h, w):
+            raise ValueError(f"frames of {h} x {w} follow frames of {self.held.shape[0]} x {self.held.shape[1]}: call reset() first")
+        out = torch.empty_like(p)
+        refreshed = torch.empty(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            if self.held is None or tuple(self.held.shape) != (h, w):
+                self.anchor = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
+                self.held = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+            _hold_into(s, p, self.anchor, self.held, self._has_state, self.cell, self.tol, self.share256, out, refreshed)
+        self._has_state = True
+        return out, refreshed
+
+
+def as_hold_stream(hold, device):
+    """The `hold` argument of the video path: None, a HoldStream (of `device`), or the settings (cell, tol, share) of a new one."""
+    if hold is None or isinstance(hold, HoldStream):
+        if hold is not None and torch.device(device) != hold.device and torch.device(device).index is not None:
+            raise ValueError(f"the hold stream lives on {hold.device}, the frames on {device}")
+        return hold
+    cell, tol, share = check_hold_argument(hold)
+    return HoldStream(device, cell, tol, share)
+
+
+def check_hold_argument(hold):
+    """ValueError for a `hold` argument that is neither None, a HoldStream nor usable settings (cell, tol, share); no device
+    needed, so the video path calls it before a decoder starts.  -> the argument."""
+    if hold is None or isinstance(hold, HoldStream):
+        return hold
+    try:
+        cell, tol, share = hold
+        _hold_settings(cell, tol, min(256, max(0, int(round(float(share) * 256)))))
+    except TypeError:
+        raise ValueError(f"hold must be None, a HoldStream or a tuple (cell, tol, share), not {hold!r}") from None
+    return hold
+
+
 def gif_lzw_stride(h, w, chunk_px=None):
     """The bytes dp_gif_lzw_encode_u8 may write per frame (dp_gif_lzw_bound_bytes): the row length of gif_lzw's payload."""
     return int(_lib.load().dp_gif_lzw_bound_bytes(int(h), int(w), int(chunk_px or GIF_CHUNK_PX)))

@@ -2680,4 +2680,66 @@ inline void resample_host(const ResamplePlanHost &p, const uint8_t *in, uint8_t 
     }
 }
 
+// ---- temporal hold (include/ditherpie_hip_hold.h; tests/hold_ref.py states it in numpy) ---------------------------------------
+constexpr int kHoldMaxCell = 16;
+constexpr int64_t kHoldMaxFrames = 65535;
+
+// -> 0, or the rule broken by the scalars of a hold call: 1 n_frames < 0, 2 h or w < 1 or h * w >= 2^31, 3 a cell that is none of
+// 1, 2, 4, 8, 16, 4 tol outside 0 .. 255, 5 share256 outside 0 .. 256, 6 more than 65535 frames
+inline int hold_rule(const int64_t n, const int h, const int w, const int cell, const int tol, const int share256)
+{
+    if (n < 0) return 1;
+    if (h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31)) return 2;
+    if (cell < 1 || cell > kHoldMaxCell || (cell & (cell - 1))) return 3;
+    if (tol < 0 || tol > 255) return 4;
+    if (share256 < 0 || share256 > 256) return 5;
+    if (n > kHoldMaxFrames) return 6;
+    return 0;
+}
+
+// does a cell of cell_px pixels, `changed` of them changed, refresh?  (the one line the kernels and the statement share: constexpr,
+// so device code may call it)
+constexpr bool hold_refreshes(const uint32_t changed, const uint32_t cell_px, const uint32_t share256)
+{
+    return changed > 0 && changed * 256u >= share256 * cell_px;
+}
+
+// The statement: n frames in order, the state carried in anchor / held (not read when has_state is 0)
+inline void hold_apply(const uint8_t *src, const uint8_t *planes, const int64_t n, const int h, const int w, const int cell, const int tol,
+                       const int share256, uint8_t *anchor, uint8_t *held, const bool has_state, uint8_t *out, int64_t *refreshed)
+{
+    const size_t px = (size_t)h * (size_t)w;
+    for (int64_t f = 0; f < n; ++f) {
+        const uint8_t *s = src + (size_t)f * px * 3u;
+        const uint8_t *p = planes + (size_t)f * px;
+        int64_t count = 0;
+        for (int y0 = 0; y0 < h; y0 += cell)
+            for (int x0 = 0; x0 < w; x0 += cell) {
+                const int y1 = std::min(h, y0 + cell), x1 = std::min(w, x0 + cell);
+                const uint32_t cell_px = (uint32_t)(y1 - y0) * (uint32_t)(x1 - x0);
+                bool refresh = true;
+                if (has_state || f > 0) {
+                    uint32_t changed = 0;
+                    for (int y = y0; y < y1; ++y)
+                        for (int x = x0; x < x1; ++x) {
+                            const size_t i = ((size_t)y * (size_t)w + (size_t)x) * 3u;
+                            int d = 0;
+                            for (int c = 0; c < 3; ++c) d = std::max(d, std::abs((int)s[i + c] - (int)anchor[i + c]));
+                            changed += d > tol ? 1u : 0u;
+                        }
+                    refresh = hold_refreshes(changed, cell_px, (uint32_t)share256);
+                }
+                if (!refresh) continue;
+                count += cell_px;
+                for (int y = y0; y < y1; ++y) {
+                    const size_t i = (size_t)y * (size_t)w + (size_t)x0;
+                    std::memcpy(anchor + i * 3u, s + i * 3u, 3u * (size_t)(x1 - x0));
+                    std::memcpy(held + i, p + i, (size_t)(x1 - x0));
+                }
+            }
+        std::memcpy(out + (size_t)f * px, held, px);
+        refreshed[f] = count;
+    }
+}
+
 }  // namespace dp

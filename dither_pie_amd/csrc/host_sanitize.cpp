@@ -1255,10 +1255,76 @@ static int run_resample(const char *path, const int n_cases, const char *out_pat
     return 0;
 }
 
+// ---- temporal hold: the host statement -------------------------------------------------------------------------------------------
+// hold record: n, h, w, cell, tol, share256, has_state, cut (int32), then n*h*w*3 source bytes, n*h*w plane bytes, h*w*3 anchor bytes
+// and h*w held bytes (the state is read from the record whatever has_state says: without state it must not matter).  The batch goes
+// through hold_apply as one call (cut < 0) or as the frames [0, cut) and [cut, n).  Per accepted case out_path gets n*h*w out
+// bytes, n int64 counts, the anchor and the held plane, back to back; every vector has exactly the stated size.
+static int run_hold(const char *path, const int n_cases, const char *out_path)
+{
+    FILE *f = fopen(path, "rb");
+    FILE *g = fopen(out_path, "wb");
+    if (!f || !g) {
+        fprintf(stderr, "cannot open %s or %s\n", path, out_path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[8];
+        if (fread(head, sizeof(int32_t), 8, f) != 8) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const int n = head[0], h = head[1], w = head[2], cell = head[3], tol = head[4], share256 = head[5], cut = head[7];
+        const int rule = hold_rule(n, h, w, cell, tol, share256);
+        printf("hold %d %d", c, rule);
+        if (!rule) {
+            if (n > 64 || cut > n) {
+                fprintf(stderr, "bad record %d in %s\n", c, path);
+                return 2;
+            }
+            const size_t px = (size_t)h * (size_t)w;
+            std::vector<uint8_t> src((size_t)n * px * 3u), planes((size_t)n * px), anchor(px * 3u), held(px), out((size_t)n * px);
+            std::vector<int64_t> refreshed((size_t)n, -1);
+            if (fread(src.data(), 1, src.size(), f) != src.size() || fread(planes.data(), 1, planes.size(), f) != planes.size() ||
+                fread(anchor.data(), 1, anchor.size(), f) != anchor.size() || fread(held.data(), 1, held.size(), f) != held.size()) {
+                fprintf(stderr, "bad record %d in %s\n", c, path);
+                return 2;
+            }
+            bool state = head[6] != 0;
+            const int k = cut < 0 ? n : cut;
+            if (k > 0) {   // exactly the frames of the call: a vector per call, so that a read past them is seen
+                const std::vector<uint8_t> s(src.begin(), src.begin() + (ptrdiff_t)((size_t)k * px * 3u)), p(planes.begin(), planes.begin() + (ptrdiff_t)((size_t)k * px));
+                std::vector<uint8_t> o((size_t)k * px);
+                hold_apply(s.data(), p.data(), k, h, w, cell, tol, share256, anchor.data(), held.data(), state, o.data(), refreshed.data());
+                std::copy(o.begin(), o.end(), out.begin());
+                state = true;
+            }
+            if (n - k > 0) {
+                const std::vector<uint8_t> s(src.begin() + (ptrdiff_t)((size_t)k * px * 3u), src.end()), p(planes.begin() + (ptrdiff_t)((size_t)k * px), planes.end());
+                std::vector<uint8_t> o((size_t)(n - k) * px);
+                std::vector<int64_t> r((size_t)(n - k), -1);
+                hold_apply(s.data(), p.data(), n - k, h, w, cell, tol, share256, anchor.data(), held.data(), state, o.data(), r.data());
+                std::copy(o.begin(), o.end(), out.begin() + (ptrdiff_t)((size_t)k * px));
+                std::copy(r.begin(), r.end(), refreshed.begin() + k);
+            }
+            if (fwrite(out.data(), 1, out.size(), g) != out.size() || fwrite(refreshed.data(), sizeof(int64_t), refreshed.size(), g) != refreshed.size() ||
+                fwrite(anchor.data(), 1, anchor.size(), g) != anchor.size() || fwrite(held.data(), 1, held.size(), g) != held.size())
+                return 2;
+            long long total = 0;
+            for (const int64_t v : refreshed) total += v;
+            printf(" %lld", total);
+        }
+        printf("\n");
+    }
+    fclose(f);
+    fclose(g);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  fixneeded <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  fixneeded <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>  |  hold <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1282,6 +1348,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "okfit") return run_okfit(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resample") return argc > 4 ? run_resample(argv[2], atoi(argv[3]), argv[4]) : 2;
+    if (std::string(argv[1]) == "hold") return argc > 4 ? run_hold(argv[2], atoi(argv[3]), argv[4]) : 2;
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

@@ -129,10 +129,15 @@ def process_frames(frames, ditherer: ImageDitherer, pixelize_method: Optional[st
 
 
 def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Optional[str] = None, max_size: int = 64,
-                           final_resize_multiplier: Optional[int] = None, downscale_filter: str = "nearest"):
+                           final_resize_multiplier: Optional[int] = None, hold=None, downscale_filter: str = "nearest"):
     """process_frames() as palette-index planes: uint8 CUDA tensor [N,H,W,3] -> (planes [N,H',W'], palette_u8 [K,3]) with
     palette_u8[planes] == process_frames(...).  The final up-scale runs on the index plane (the same NEAREST coordinates),
-    so the index pass looks up the small frames only.  downscale_filter: as for process_frames."""
+    so the index pass looks up the small frames only.  downscale_filter: as for process_frames.
+    hold (an addition, in front of downscale_filter, which stays the last parameter: pass both by keyword; None leaves every byte
+    as it was): a backend.HoldStream, or the settings (cell, tol, share) of a new one that lives for this call.  The temporal hold then runs on the small planes, between the dither and the final up-scale, with
+    the frames as handed to the ditherer as its source: cells whose source has not moved keep the indices of an earlier frame, so
+    the planes are no longer process_frames() of each frame on its own.  The stream is reset() when the palette is not the one
+    its indices belong to (a palette fitted per call); two-byte planes (more than 256 colours) are refused with a ValueError."""
     from . import backend
     downscale_filter = _downscale_filter(downscale_filter)
     if pixelize_method in (PixelizeMethod.NEURAL.value, "neural"):
@@ -142,6 +147,15 @@ def process_frames_indexed(frames, ditherer: ImageDitherer, pixelize_method: Opt
         tw, th = _even_dimensions(x.shape[2], x.shape[1], max_size)
         x = _downscale(x, th, tw, downscale_filter)
     planes, colours = ditherer.apply_dithering_frames_indexed(x)
+    if hold is not None:
+        stream = backend.as_hold_stream(hold, x.device)
+        if len(colours) > 256:
+            raise ValueError(f"the temporal hold takes one-byte planes: at most 256 colours, the palette has {len(colours)}")
+        pal = np.ascontiguousarray(colours, dtype=np.uint8)
+        if stream.palette is None or stream.palette.shape != pal.shape or not np.array_equal(stream.palette, pal):
+            stream.reset()   # held indices of another palette mean other colours
+        planes, _ = stream.add(x, planes)
+        stream.palette = pal
     if final_resize_multiplier:
         nw, nh = _final_size(planes.shape[2], planes.shape[1], final_resize_multiplier)
         planes = backend.resize_nearest_plane(planes, nh, nw)
@@ -156,7 +170,7 @@ def process_frames_png(frames, ditherer: ImageDitherer, pixelize_method: Optiona
     device and only the compressed streams come back (assemble="device": the finished files, png.encode_png).  ValueError above
     256 colours."""
     from . import png
-    planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
+    planes, colours = process_frames_indexed(frames, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter=downscale_filter)
     return png.encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)
 
 
@@ -706,7 +720,7 @@ class VideoProcessor:
         return scenes
 
     def process_video_gif(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                          scene_palettes=None, delta=True, max_frames=None, chunk_px=None, downscale_filter="nearest") -> int:
+                          scene_palettes=None, delta=True, max_frames=None, chunk_px=None, hold=None, downscale_filter="nearest") -> int:
         """The video as an animated GIF of palette indices (gif.GifWriter): decode -> GPU -> file, no encoder pipe and no RGB
         frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded: the same decoder
         line, reader thread and rotating pinned slots).  Per batch: process_frames_indexed -- piece by piece with each
@@ -715,6 +729,10 @@ class VideoProcessor:
         the container in Python.  A scene's palette that is not the first one travels as a local colour table, and the
         delta starts over at every palette change.  Decoding a frame of the file gives process_frames of that frame (with
         its scene's palette), exactly.  The file plays at gif.delay_cs(fps) centiseconds per frame.
+        hold (an addition; None leaves every byte as it was): a backend.HoldStream or the settings (cell, tol, share) of one --
+        the temporal hold of process_frames_indexed over the whole file: cells whose source has not moved keep their indices, so
+        the delta finds them equal and drops them.  Decoding a frame then gives the held planes, not process_frames of that
+        frame alone.  The hold starts over wherever the palette changes: at every scene start under scene_palettes.
         One device: the first of `devices`; a list of several is refused (frames of one file are written in order by one
         writer).  Failure policy: a batch that fails RAISES -- the rawvideo path's substitution of the nearest good frame is
         not mirrored: a GIF with a silently substituted frame is worse than an error -- and so does a device failure, a
@@ -747,6 +765,9 @@ class VideoProcessor:
 
             def pieces_of(first, n):
                 return [(lo - first, hi - first, scene_ditherers[scene_of(scene_list, lo)]) for lo, hi in split_at(first, n, cut_points)]
+        if hold is not None:
+            from . import backend
+            backend.check_hold_argument(hold)
         info = self.get_video_info(input_path)
         fps = info.get("fps") or 25.0
         made = {}
@@ -757,14 +778,21 @@ class VideoProcessor:
                 self.error = error
 
         def setup(dev, gpu_stream, h, w, stats):
+            from . import backend
             oh, ow = output_size(h, w, pixelize_method, max_size, final_resize_multiplier)
             writer = made["writer"] = GifWriter(made["file"], ow, oh, fps, 0, chunk_px)
+            held = made["hold"] = backend.as_hold_stream(hold, dev)
+            if held is not None:
+                held.reset()   # a file is a stream of its own
 
             def feed(x, first):
                 try:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
-                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
+                        if held is not None and pieces_of and (first + a) in cut_points:
+                            held.reset()   # a scene starts: its palette is another one (and were it equal, a cut refreshes everything)
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, hold=held,
+                                                                 downscale_filter=downscale_filter)
                         writer.add(planes, colours, delta)
                 except Exception as e:  # noqa: BLE001
                     raise _BatchFailed(e) from e
@@ -784,7 +812,7 @@ class VideoProcessor:
         return made["writer"].n_frames
 
     def process_video_apng(self, input_path, output_path, ditherer, pixelize_method=None, max_size=64, final_resize_multiplier=None,
-                           delta=True, max_frames=None, seg_bytes=None, blocks="fixed", downscale_filter="nearest") -> int:
+                           delta=True, max_frames=None, seg_bytes=None, blocks="fixed", hold=None, downscale_filter="nearest") -> int:
         """The video as an animated PNG of palette indices (apng.ApngWriter): decode -> GPU -> file, no encoder pipe and no
         RGB frames on the way out.  Built on the decode-only loop of scan_palette / scan_scenes (_scan_decoded), exactly as
         process_video_gif is.  Per batch: process_frames_indexed, the inter-frame delta, the zlib streams, the chunk CRCs and
@@ -794,6 +822,7 @@ class VideoProcessor:
         One palette: an APNG has a single PLTE, so there is no scene_palettes argument, and a ditherer that fits its palette
         per frame is refused at the first frame whose colours differ from the file's.  A palette fitted to the whole clip
         (scan_palette) is the natural companion.
+        hold (an addition; None leaves every byte as it was): as for process_video_gif -- the temporal hold over the whole file.
         One device: the first of `devices`; a list of several is refused.  Failure policy as process_video_gif: a batch that
         fails RAISES, and so does a device failure, a malformed stream or a decoder that exits with an error; the partial
         file is left as it is.
@@ -813,6 +842,9 @@ class VideoProcessor:
             raise ValueError(f"blocks must be 'fixed' or 'dynamic', not {blocks!r}")
         if getattr(ditherer, "palette", None) is not None and len(ditherer.palette) > APNG_MAX_COLOURS:
             raise ValueError(f"the ditherer has {len(ditherer.palette)} colours: a PNG palette holds {APNG_MAX_COLOURS}")
+        if hold is not None:
+            from . import backend
+            backend.check_hold_argument(hold)
         info = self.get_video_info(input_path)
         fps = info.get("fps") or 25.0
         made = {}
@@ -823,12 +855,17 @@ class VideoProcessor:
                 self.error = error
 
         def setup(dev, gpu_stream, h, w, stats):
+            from . import backend
             oh, ow = output_size(h, w, pixelize_method, max_size, final_resize_multiplier)
             writer = made["writer"] = ApngWriter(made["file"], ow, oh, fps, 0, delta, seg_bytes, "device", blocks)
+            held = made["hold"] = backend.as_hold_stream(hold, dev)
+            if held is not None:
+                held.reset()   # a file is a stream of its own
 
             def feed(x, first):
                 try:
-                    planes, colours = process_frames_indexed(x, ditherer, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
+                    planes, colours = process_frames_indexed(x, ditherer, pixelize_method, max_size, final_resize_multiplier, hold=held,
+                                                             downscale_filter=downscale_filter)
                     writer.add(planes, colours)
                 except Exception as e:  # noqa: BLE001
                     raise _BatchFailed(e) from e
@@ -912,7 +949,7 @@ class VideoProcessor:
                 try:
                     pieces = pieces_of(first, x.shape[0]) if pieces_of else [(0, x.shape[0], ditherer)]
                     for a, b, d in pieces:
-                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, downscale_filter)
+                        planes, colours = process_frames_indexed(x[a:b], d, pixelize_method, max_size, final_resize_multiplier, downscale_filter=downscale_filter)
                         for k, data in enumerate(encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble)):
                             with open(str(out_pattern) % (int(start) + first + a + k), "wb") as f:
                                 f.write(data)
