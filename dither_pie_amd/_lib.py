@@ -271,6 +271,60 @@ _SIGS_HOLD = {
     "dp_hold_state_bytes": (_i, [_i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
 }
 EXPORTS_HOLD = tuple(_SIGS_HOLD)
+# include/ditherpie_hip_alpha.h: transparency (RGBA split, key index, RGBA join and their host statements; the masked integer
+# error diffusion and the masked dot diffusion); a table of its own for the same reason.  Every entry point takes a descriptor.
+ALPHA_MODES = ("threshold", "ordered")   # DP_ALPHA_THRESHOLD, DP_ALPHA_ORDERED
+ALPHA_MATRICES = (2, 4, 8)
+ALPHA_MAX_FRAMES = 65535                 # DP_ALPHA_MAX_FRAMES: frames per call of split, key and join
+ALPHA_MAX_ORIGIN = 1 << 30               # DP_ALPHA_MAX_ORIGIN
+_rgb3 = C.c_uint8 * 3
+
+
+class AlphaSplitArgs(C.Structure):
+    """dp_alpha_split_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("rgba_dev", C.c_void_p), ("n_frames", C.c_int64), ("h", C.c_int), ("w", C.c_int),
+                ("mode", C.c_int), ("threshold", C.c_int), ("m", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("has_matte", C.c_int),
+                ("matte", _rgb3), ("rgb_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("masked_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class AlphaKeyArgs(C.Structure):
+    """dp_alpha_key_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("planes_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("n_frames", C.c_int64), ("h", C.c_int),
+                ("w", C.c_int), ("key", C.c_int), ("out_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class AlphaJoinArgs(C.Structure):
+    """dp_alpha_join_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("rgb_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("n_frames", C.c_int64), ("h", C.c_int),
+                ("w", C.c_int), ("fill", _rgb3), ("rgba_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class AlphaIdiffArgs(C.Structure):
+    """dp_alpha_idiff_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("in_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_frames", C.c_int64),
+                ("h", C.c_int), ("w", C.c_int), ("pal", C.c_void_p), ("dx", C.c_void_p), ("dy", C.c_void_p), ("weight", C.c_void_p),
+                ("n_taps", C.c_int), ("divisor", C.c_int), ("strength256", C.c_int), ("fill", _rgb3), ("workspace_dev", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class AlphaDotdiffArgs(C.Structure):
+    """dp_alpha_dotdiff_args"""
+    _fields_ = [("struct_size", C.c_size_t), ("in_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_frames", C.c_int64),
+                ("h", C.c_int), ("w", C.c_int), ("pal", C.c_void_p), ("classes_host", C.c_void_p), ("m", C.c_int), ("strength256", C.c_int),
+                ("fill", _rgb3), ("stream", C.c_void_p)]
+
+
+_SIGS_ALPHA = {
+    "dp_alpha_split_u8": (_i, [C.POINTER(AlphaSplitArgs)]),
+    "dp_alpha_split_host_u8": (_i, [C.POINTER(AlphaSplitArgs)]),
+    "dp_alpha_key_u8": (_i, [C.POINTER(AlphaKeyArgs)]),
+    "dp_alpha_key_host_u8": (_i, [C.POINTER(AlphaKeyArgs)]),
+    "dp_alpha_join_u8": (_i, [C.POINTER(AlphaJoinArgs)]),
+    "dp_alpha_join_host_u8": (_i, [C.POINTER(AlphaJoinArgs)]),
+    "dp_alpha_idiff_u8": (_i, [C.POINTER(AlphaIdiffArgs)]),
+    "dp_alpha_dotdiff_u8": (_i, [C.POINTER(AlphaDotdiffArgs)]),
+}
+EXPORTS_ALPHA = tuple(_SIGS_ALPHA)
 
 
 def build(force=False):
@@ -318,7 +372,7 @@ def load():
                                           + list(_SIGS_CELLS.items()) + list(_SIGS_VOIDCLUSTER.items())
                                           + list(_SIGS_METRIC.items()) + list(_SIGS_IDIFF.items())
                                           + list(_SIGS_OKFIT.items()) + list(_SIGS_RESAMPLE.items())
-                                          + list(_SIGS_HOLD.items())):
+                                          + list(_SIGS_HOLD.items()) + list(_SIGS_ALPHA.items())):
                     try:
                         fn = getattr(L, name)
                     except AttributeError:

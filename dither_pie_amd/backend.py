@@ -1904,6 +1904,236 @@ def check_hold_argument(hold):
     return hold
 
 
+ALPHA_MODES = _lib.ALPHA_MODES
+ALPHA_MATRICES = _lib.ALPHA_MATRICES
+ALPHA_MAX_FRAMES = _lib.ALPHA_MAX_FRAMES
+
+
+def _rgb_triple(c, what):
+    """A colour as three bytes (a ctypes array for a descriptor); ValueError otherwise."""
+    try:
+        t = tuple(int(v) for v in c)
+        exact = len(t) == 3 and all(a == b for a, b in zip(t, c)) and all(0 <= v <= 255 for v in t)
+    except (TypeError, ValueError):
+        exact = False
+    if not exact:
+        raise ValueError(f"{what} must be three integers in 0 .. 255, not {c!r}")
+    return _lib._rgb3(*t)
+
+
+def _alpha_settings(mode, threshold, matrix, matte, y0, x0):
+    """The argument rules of dp_alpha_split_u8 as ValueError -> (mode index, threshold, m, has_matte, matte bytes, y0, x0)."""
+    if mode not in ALPHA_MODES:
+        raise ValueError(f"alpha mode must be one of {ALPHA_MODES}, not {mode!r}")
+    if not (isinstance(threshold, (int, np.integer)) and 0 <= threshold <= 256):
+        raise ValueError(f"alpha threshold must be an integer in 0 .. 256, not {threshold!r}")
+    if matrix not in ALPHA_MATRICES:
+        raise ValueError(f"alpha matrix must be one of {ALPHA_MATRICES}, not {matrix!r}")
+    for v in (y0, x0):
+        if not (isinstance(v, (int, np.integer)) and 0 <= v <= _lib.ALPHA_MAX_ORIGIN):
+            raise ValueError(f"y0 and x0 must be integers in 0 .. 2^30, not {y0!r}, {x0!r}")
+    m = _rgb_triple((0, 0, 0) if matte is None else matte, "matte")
+    return ALPHA_MODES.index(mode), int(threshold), int(matrix), 0 if matte is None else 1, m, int(y0), int(x0)
+
+
+def _alpha_geometry(h, w):
+    if h < 1 or w < 1 or h * w >= 1 << 31:
+        raise ValueError(f"frames of {h} x {w}: h and w must be >= 1 and h * w below 2^31")
+
+
+def _alpha_tensor(t, last, what):
+    """-> t as a contiguous [N,H,W(,last)] uint8 CUDA tensor and whether a frame axis was added"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
+        raise TypeError(f"{what} must be a CUDA uint8 tensor")
+    dims = 3 if last is None else 4
+    single = t.dim() == dims - 1
+    if single:
+        t = t.unsqueeze(0)
+    if t.dim() != dims or (last is not None and t.shape[-1] != last):
+        raise ValueError(f"{what} must be [N,H,W{'' if last is None else ',' + str(last)}] (or one frame), not {tuple(t.shape)}")
+    return t.contiguous(), single
+
+
+def alpha_split(rgba, mode="threshold", threshold=128, matrix=4, matte=None, y0=0, x0=0):
+    """dp_alpha_split_u8 (include/ditherpie_hip_alpha.h): rgba [N,H,W,4] (or [H,W,4]) uint8 CUDA -> (rgb [..,3], mask [N,H,W] of 0 / 1,
+    masked [N] int64 on the device: the transparent pixels per frame).  mode "threshold": transparent where alpha < threshold;
+    "ordered": where the m x m Bayer matrix at the global position (y0 + y, x0 + x) says so.  matte: None, or the colour the RGB is
+    composited over.  One clearing and one launch per 65535 frames, nothing read back."""
+    md, thr, m, has_matte, mt, y0, x0 = _alpha_settings(mode, threshold, matrix, matte, y0, x0)
+    f, single = _alpha_tensor(rgba, 4, "rgba")
+    n, h, w, _ = f.shape
+    _alpha_geometry(h, w)
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=f.device)
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=f.device)
+    masked = torch.empty(n, dtype=torch.int64, device=f.device)
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):
+        for a in range(0, n, ALPHA_MAX_FRAMES):
+            b = min(n, a + ALPHA_MAX_FRAMES)
+            args = _lib.AlphaSplitArgs(C.sizeof(_lib.AlphaSplitArgs), f[a:b].data_ptr(), b - a, h, w, md, thr, m, y0, x0, has_matte, mt,
+                                       rgb[a:b].data_ptr(), mask[a:b].data_ptr(), masked[a:b].data_ptr(), _stream().value)
+            check(L.dp_alpha_split_u8(C.byref(args)))
+    return (rgb[0], mask[0], masked) if single else (rgb, mask, masked)
+
+
+def alpha_split_host(rgba, mode="threshold", threshold=128, matrix=4, matte=None, y0=0, x0=0):
+    """The same on the CPU (dp_alpha_split_host_u8: the host statement of the kernel): numpy in and out.  Needs no device."""
+    md, thr, m, has_matte, mt, y0, x0 = _alpha_settings(mode, threshold, matrix, matte, y0, x0)
+    f = np.ascontiguousarray(rgba)
+    single = f.ndim == 3
+    f = f[None] if single else f
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[-1] != 4:
+        raise ValueError("rgba must be [N,H,W,4] (or [H,W,4]) uint8")
+    n, h, w, _ = f.shape
+    _alpha_geometry(h, w)
+    rgb, mask, masked = np.empty((n, h, w, 3), np.uint8), np.empty((n, h, w), np.uint8), np.empty(n, np.int64)
+    for a in range(0, n, ALPHA_MAX_FRAMES):
+        b = min(n, a + ALPHA_MAX_FRAMES)
+        args = _lib.AlphaSplitArgs(C.sizeof(_lib.AlphaSplitArgs), f[a:b].ctypes.data, b - a, h, w, md, thr, m, y0, x0, has_matte, mt,
+                                   rgb[a:b].ctypes.data, mask[a:b].ctypes.data, masked[a:b].ctypes.data, None)
+        check(_lib.load().dp_alpha_split_host_u8(C.byref(args)))
+    return (rgb[0], mask[0], masked) if single else (rgb, mask, masked)
+
+
+def _alpha_key_value(key):
+    if not (isinstance(key, (int, np.integer)) and 0 <= key <= 255):
+        raise ValueError(f"the key index must be an integer in 0 .. 255, not {key!r}")
+    return int(key)
+
+
+def alpha_key(planes, mask, key, out=None):
+    """dp_alpha_key_u8: planes [N,H,W] (or [H,W]) uint8 index planes, mask of the same shape -> planes with `key` at the masked
+    pixels.  out=planes works in place.  ValueError for two-byte planes: the key is one byte."""
+    key = _alpha_key_value(key)
+    if isinstance(planes, torch.Tensor) and planes.dtype != torch.uint8:
+        raise ValueError(f"planes must be one-byte indices (torch.uint8), not {planes.dtype}: the key index is one byte")
+    p, single = _alpha_tensor(planes, None, "planes")
+    k, _ = _alpha_tensor(mask, None, "mask")
+    if k.shape != p.shape or k.device != p.device:
+        raise ValueError(f"mask must be of the planes' shape and device, not {tuple(k.shape)} beside {tuple(p.shape)}")
+    n, h, w = p.shape
+    _alpha_geometry(h, w)
+    res = _check_buffer(out, p.device, (n, h, w), torch.uint8, "out")
+    L = _lib.load()
+    with torch.cuda.device(p.device), _Launch(p.device, None):
+        for a in range(0, n, ALPHA_MAX_FRAMES):
+            b = min(n, a + ALPHA_MAX_FRAMES)
+            args = _lib.AlphaKeyArgs(C.sizeof(_lib.AlphaKeyArgs), p[a:b].data_ptr(), k[a:b].data_ptr(), b - a, h, w, key, res[a:b].data_ptr(),
+                                     _stream().value)
+            check(L.dp_alpha_key_u8(C.byref(args)))
+    return res[0] if single else res
+
+
+def alpha_key_host(planes, mask, key):
+    """The same on the CPU (dp_alpha_key_host_u8): numpy in and out."""
+    key = _alpha_key_value(key)
+    p, k = np.ascontiguousarray(planes), np.ascontiguousarray(mask)
+    if p.dtype != np.uint8 or k.dtype != np.uint8 or p.shape != k.shape or p.ndim not in (2, 3):
+        raise ValueError("planes and mask must be uint8 arrays of one shape, [N,H,W] or [H,W]")
+    q, kk = (p[None], k[None]) if p.ndim == 2 else (p, k)
+    n, h, w = q.shape
+    _alpha_geometry(h, w)
+    out = np.empty_like(q)
+    for a in range(0, n, ALPHA_MAX_FRAMES):
+        b = min(n, a + ALPHA_MAX_FRAMES)
+        args = _lib.AlphaKeyArgs(C.sizeof(_lib.AlphaKeyArgs), q[a:b].ctypes.data, kk[a:b].ctypes.data, b - a, h, w, key, out[a:b].ctypes.data, None)
+        check(_lib.load().dp_alpha_key_host_u8(C.byref(args)))
+    return out.reshape(p.shape)
+
+
+def alpha_join(rgb, mask, fill=(0, 0, 0), out=None):
+    """dp_alpha_join_u8: rgb [N,H,W,3] (or [H,W,3]) and mask [N,H,W] -> rgba [N,H,W,4]: (fill, 0) at the masked pixels, (rgb, 255)
+    elsewhere."""
+    fl = _rgb_triple(fill, "fill")
+    f, single = _alpha_tensor(rgb, 3, "rgb")
+    k, _ = _alpha_tensor(mask, None, "mask")
+    if tuple(k.shape) != tuple(f.shape[:3]) or k.device != f.device:
+        raise ValueError(f"mask must be [N,H,W] of the frames and on their device, not {tuple(k.shape)} beside {tuple(f.shape)}")
+    n, h, w, _ = f.shape
+    _alpha_geometry(h, w)
+    res = _check_buffer(out, f.device, (n, h, w, 4), torch.uint8, "out")
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):
+        for a in range(0, n, ALPHA_MAX_FRAMES):
+            b = min(n, a + ALPHA_MAX_FRAMES)
+            args = _lib.AlphaJoinArgs(C.sizeof(_lib.AlphaJoinArgs), f[a:b].data_ptr(), k[a:b].data_ptr(), b - a, h, w, fl, res[a:b].data_ptr(),
+                                      _stream().value)
+            check(L.dp_alpha_join_u8(C.byref(args)))
+    return res[0] if single else res
+
+
+def alpha_join_host(rgb, mask, fill=(0, 0, 0)):
+    """The same on the CPU (dp_alpha_join_host_u8): numpy in and out."""
+    fl = _rgb_triple(fill, "fill")
+    f, k = np.ascontiguousarray(rgb), np.ascontiguousarray(mask)
+    if f.dtype != np.uint8 or k.dtype != np.uint8 or f.ndim not in (3, 4) or f.shape[-1] != 3 or k.shape != f.shape[:-1]:
+        raise ValueError("rgb must be [N,H,W,3] (or [H,W,3]) uint8 and mask [N,H,W] (or [H,W]) uint8 of the same frames")
+    q, kk = (f[None], k[None]) if f.ndim == 3 else (f, k)
+    n, h, w, _ = q.shape
+    _alpha_geometry(h, w)
+    out = np.empty((n, h, w, 4), np.uint8)
+    for a in range(0, n, ALPHA_MAX_FRAMES):
+        b = min(n, a + ALPHA_MAX_FRAMES)
+        args = _lib.AlphaJoinArgs(C.sizeof(_lib.AlphaJoinArgs), q[a:b].ctypes.data, kk[a:b].ctypes.data, b - a, h, w, fl, out[a:b].ctypes.data, None)
+        check(_lib.load().dp_alpha_join_host_u8(C.byref(args)))
+    return out[0] if f.ndim == 3 else out
+
+
+def _masked_inputs(frames, mask, out, what):
+    f = _frames(frames)
+    k, _ = _alpha_tensor(mask, None, "mask")
+    if tuple(k.shape) != tuple(f.shape[:3]) or k.device != f.device:
+        raise ValueError(f"mask must be [N,H,W] of the frames and on their device, not {tuple(k.shape)} beside {tuple(f.shape)}")
+    out = _check_out(out, f)
+    if f.shape[0] and out.data_ptr() in (f.data_ptr(), k.data_ptr()):
+        raise ValueError(f"{what} does not work in place: out must be neither the frames nor the mask")
+    return f, k, out
+
+
+def idiff_masked(frames, mask, pal: Palette, taps, divisor, strength256, fill=(0, 0, 0), out=None):
+    """idiff() under a mask (dp_alpha_idiff_u8, include/ditherpie_hip_alpha.h): mask [N,H,W] uint8, non-zero = transparent.  A
+    transparent pixel becomes `fill`, receives no error and hands none on; its hidden colour is never looked at.  With an all-zero
+    mask the result is idiff()'s."""
+    dx, dy, wt = _idiff_taps(taps, divisor, strength256)
+    fl = _rgb_triple(fill, "fill")
+    if pal.K > 256:
+        raise ValueError(f"integer error diffusion supports at most 256 colours, the palette has {pal.K}")
+    f, k, out = _masked_inputs(frames, mask, out, "integer error diffusion")
+    n, h, w, _ = f.shape
+    _check_palette_device(pal, f)
+    L = _lib.load()
+    ws_bytes = L.dp_idiff_workspace_bytes(n, h, w)
+    with torch.cuda.device(f.device), _Launch(f.device, ws_bytes) as ws:
+        args = _lib.AlphaIdiffArgs(C.sizeof(_lib.AlphaIdiffArgs), f.data_ptr(), k.data_ptr(), out.data_ptr(), n, h, w, pal._h, dx.ctypes.data,
+                                   dy.ctypes.data, wt.ctypes.data, len(dx), int(divisor), int(strength256), fl, ws.data_ptr(), ws.numel(),
+                                   _stream().value)
+        check(L.dp_alpha_idiff_u8(C.byref(args)))
+    return out.view(frames.shape)
+
+
+def dotdiff_masked(frames, mask, pal: Palette, classes, strength256, fill=(0, 0, 0), out=None):
+    """dotdiff() under a mask (dp_alpha_dotdiff_u8): a transparent pixel becomes `fill` and hands on nothing, and an opaque pixel
+    shares its error among its OPAQUE neighbours of a higher class.  With an all-zero mask the result is dotdiff()'s."""
+    c = _dotdiff_classes(classes)
+    fl = _rgb_triple(fill, "fill")
+    if not (isinstance(strength256, (int, np.integer)) and 0 <= strength256 <= 256):
+        raise ValueError(f"dot diffusion strength256 must be an integer in 0 .. 256, not {strength256!r}")
+    if pal.K > 256:
+        raise ValueError(f"dot diffusion supports at most 256 colours, the palette has {pal.K}")
+    reach = dotdiff_reach(c)
+    if reach > DOTDIFF_MAX_REACH:
+        raise ValueError(f"dot diffusion: the class matrix has reach {reach}, at most {DOTDIFF_MAX_REACH} is supported")
+    f, k, out = _masked_inputs(frames, mask, out, "dot diffusion")
+    n, h, w, _ = f.shape
+    _check_palette_device(pal, f)
+    L = _lib.load()
+    with torch.cuda.device(f.device), _Launch(f.device, None):
+        args = _lib.AlphaDotdiffArgs(C.sizeof(_lib.AlphaDotdiffArgs), f.data_ptr(), k.data_ptr(), out.data_ptr(), n, h, w, pal._h, c.ctypes.data,
+                                     int(c.shape[0]), int(strength256), fl, _stream().value)
+        check(L.dp_alpha_dotdiff_u8(C.byref(args)))
+    return out.view(frames.shape)
+
+
 def gif_lzw_stride(h, w, chunk_px=None):
     """The bytes dp_gif_lzw_encode_u8 may write per frame (dp_gif_lzw_bound_bytes): the row length of gif_lzw's payload."""
     return int(_lib.load().dp_gif_lzw_bound_bytes(int(h), int(w), int(chunk_px or GIF_CHUNK_PX)))

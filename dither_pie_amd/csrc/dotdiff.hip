@@ -66,11 +66,26 @@ __device__ __forceinline__ void shares(const int e, const uint32_t strength, con
     d2 = (uint32_t)(e < 0 ? -(int)q2 : (int)q2) & 0xffffu;
 }
 
-template <int T, int BLOCK>
+// the arguments of a MASKED instance behind strength: the mask (n_frames x h x w bytes, non-zero = transparent) and fill (r | g << 8 | b << 16)
+__device__ __forceinline__ const uint8_t *dot_mask_of(const uint8_t *mask_all, uint32_t) { return mask_all; }
+__device__ __forceinline__ uint32_t dot_fill_of(const uint8_t *, const uint32_t fill) { return fill; }
+
+// MASK is empty -- the instance of include/ditherpie_hip_dotdiff.h, whose argument list and code are what they were before the pack
+// existed -- or (const uint8_t *, uint32_t): the MASKED instance of include/ditherpie_hip_alpha.h.  There bit 24 of a slot's word 0
+// says "transparent" while the slot still holds the source colour: a neighbour of greater class is of a later level, so its flag is
+// readable when W is formed (a neighbour beyond the region has no slot: its mask byte is read from memory, which only pixels on the
+// region's edge do).  A transparent pixel hands on nothing (a slot of zeros) and its output bytes are `fill`.  No LDS is added.
+// Why a pack and not a `bool MASKED` with two trailing arguments: a trailing kernel argument, used or not, moves the hidden arguments
+// (the group size the runtime passes behind the explicit ones), which changes an immediate in the unmasked instances; with an empty
+// pack their argument list is byte for byte the old one and their gfx950 instruction streams are unchanged (DESIGN.md 4.4 has the
+// comparison).  Whoever adds a trailing argument to this kernel moves them for every instance and repeats that comparison.
+template <int T, int BLOCK, typename... MASK>
 __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int h, const int w,
                                                         const uint32_t ntx, const uint32_t ntiles, const PatDev pd,
-                                                        const uint8_t *__restrict__ lut, const DotDev dd, const uint32_t strength)
+                                                        const uint8_t *__restrict__ lut, const DotDev dd, const uint32_t strength, const MASK... mask_args)
 {
+    constexpr bool MASKED = sizeof...(MASK) != 0;
+    static_assert(sizeof...(MASK) == 0 || sizeof...(MASK) == 2, "no mask arguments, or the mask and the fill");
     constexpr int R = kDotDiffMaxReach, RS = T + 2 * R, NPX = RS * RS, WAVES = BLOCK / 64;
     static_assert(T % 16 == 0 && RS % 16 == 0, "the region's origin is a multiple of every matrix size");
     __shared__ uint32_t s_px[NPX * 3];   // the slots: source colour r | g<<8 | b<<16 in word 0, then d1.r | d1.g<<16, d1.b | d2.r<<16, d2.g | d2.b<<16
@@ -98,6 +113,12 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
     uint8_t *fout = out + fbase;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint8_t *s_bytes = reinterpret_cast<uint8_t *>(s_px);
+    const uint8_t *__restrict__ fmask = nullptr;
+    uint32_t fill = 0u;
+    if constexpr (MASKED) {
+        fmask = dot_mask_of(mask_args...) + (size_t)blockIdx.y * (size_t)h * (size_t)w;
+        fill = dot_fill_of(mask_args...);
+    }
 
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int ty0 = (int)(tile / ntx) * T, tx0 = (int)(tile % ntx) * T;        // the tile's first pixel; inside the image
@@ -129,6 +150,29 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
                     if (row < rh && b < 3 * rw) s_bytes[(row * RS + px) * 12 + ch] = s_lut[v[r][j]];
                 }
             }
+            if constexpr (MASKED) {   // the flags: byte 3 of every slot of the region
+                constexpr int MCHUNKS = (RS + 63) / 64;
+                uint8_t mv[ROWS][MCHUNKS];
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    const int row = wave + r * WAVES;
+                    const uint8_t *src = fmask + (size_t)(ry0 + min(row, rh - 1)) * (size_t)w + (size_t)rx0;
+#pragma unroll
+                    for (int j = 0; j < MCHUNKS; ++j) {
+                        const int px = lane + 64 * j;
+                        mv[r][j] = row < rh && px < rw ? src[px] : (uint8_t)0;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    const int row = wave + r * WAVES;
+#pragma unroll
+                    for (int j = 0; j < MCHUNKS; ++j) {
+                        const int px = lane + 64 * j;
+                        if (row < rh && px < rw) s_bytes[(row * RS + px) * 12 + 3] = mv[r][j] ? (uint8_t)1 : (uint8_t)0;
+                    }
+                }
+            }
         }
         __syncthreads();
 
@@ -143,6 +187,13 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
                 const int ly = (int)(tyr << log2m) + (int)(cell >> log2m), lx = (int)(txr << log2m) + (int)(cell & (uint32_t)mm);
                 if (ly >= rh || lx >= rw) continue;                               // beyond the image
                 const int gy = ry0 + ly, gx = rx0 + lx;
+                if constexpr (MASKED) {
+                    uint32_t *own = &s_px[(ly * RS + lx) * 3];
+                    if (own[0] >> 24) {   // transparent: it hands on nothing; its bytes come from `fill` at the end
+                        own[0] = own[1] = own[2] = 0u;
+                        continue;
+                    }
+                }
                 int ar = 0, ag = 0, ab = 0;
                 uint32_t W = 0;
 #pragma unroll
@@ -153,7 +204,13 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
                     if (ngy < 0 || ngy >= h || ngx < 0 || ngx >= w) continue;     // not in the image
                     const uint32_t ncls = s_cls[((ngy & mm) << log2m) | (ngx & mm)];
                     if (ncls > cls) {
-                        W += orth ? 2u : 1u;
+                        if constexpr (MASKED) {   // E holds the opaque neighbours only
+                            const bool inside = ny >= 0 && nx >= 0 && ny < rh && nx < rw;
+                            const bool hidden = inside ? (s_px[(ny * RS + nx) * 3] >> 24) != 0u : fmask[(size_t)ngy * (size_t)w + (size_t)ngx] != 0;
+                            W += hidden ? 0u : (orth ? 2u : 1u);
+                        } else {
+                            W += orth ? 2u : 1u;
+                        }
                     } else if (ny >= 0 && nx >= 0) {                              // (ny < rh and nx < rw: it is in the image)
                         const uint32_t *q = &s_px[(ny * RS + nx) * 3];
                         if (orth) {
@@ -170,7 +227,7 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
                     }
                 }
                 uint32_t *slot = &s_px[(ly * RS + lx) * 3];
-                const uint32_t c = slot[0];
+                const uint32_t c = slot[0];   // (MASKED: bit 24 is clear, the pixel is opaque)
                 const int ur = min(max(16 * (int)(c & 255u) + ar, 0), 4080), ug = min(max(16 * (int)((c >> 8) & 255u) + ag, 0), 4080),
                           ub = min(max(16 * (int)((c >> 16) & 255u) + ab, 0), 4080);
                 const uint32_t rk = nearest_rank(pd, (uint32_t)(ur + 8) >> 4, (uint32_t)(ug + 8) >> 4, (uint32_t)(ub + 8) >> 4);   // < 2^24 by the clamp
@@ -195,14 +252,20 @@ __global__ __launch_bounds__(BLOCK) void dotdiff_kernel(const uint8_t *__restric
             uint8_t *dst = fout + ((size_t)(ty0 + row) * (size_t)w + (size_t)tx0) * 3u;
             for (int b = lane; b < 3 * tw; b += 64) {
                 const int px = b / 3, ch = b - 3 * px;
-                dst[b] = (uint8_t)(s_out[s_rank[row * T + px]] >> (8 * ch));
+                if constexpr (MASKED) {
+                    const bool hidden = fmask[(size_t)(ty0 + row) * (size_t)w + (size_t)(tx0 + px)] != 0;
+                    dst[b] = (uint8_t)((hidden ? fill : s_out[s_rank[row * T + px]]) >> (8 * ch));
+                } else {
+                    dst[b] = (uint8_t)(s_out[s_rank[row * T + px]] >> (8 * ch));
+                }
             }
         }
     }
 }
 
+// mask: nullptr for the unmasked instance, else n_frames x h x w bytes and the MASKED one (masked pixels become `fill`)
 int launch_dotdiff(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PatDev &pd, const uint8_t *lut,
-                   const DotDev &dd, int strength, hipStream_t s)
+                   const DotDev &dd, int strength, hipStream_t s, const uint8_t *mask = nullptr, const uint32_t fill = 0)
 {
     constexpr int T = kDotTile;
     const size_t frame = 3 * (size_t)h * (size_t)w;
@@ -212,8 +275,13 @@ int launch_dotdiff(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
     for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
         const uint32_t nf = (uint32_t)std::min<int64_t>(65535, n_frames - f0);
         ProfMark *pm = prof_begin(s);
-        hipLaunchKernelGGL((dotdiff_kernel<T, kDotBlock>), dim3(std::min(ntiles, cap), nf), dim3(kDotBlock), 0, s, in + (size_t)f0 * frame,
-                           out + (size_t)f0 * frame, h, w, ntx, ntiles, pd, lut, dd, (uint32_t)strength);
+        if (mask)
+            hipLaunchKernelGGL((dotdiff_kernel<T, kDotBlock, const uint8_t *, uint32_t>), dim3(std::min(ntiles, cap), nf), dim3(kDotBlock), 0, s,
+                               in + (size_t)f0 * frame, out + (size_t)f0 * frame, h, w, ntx, ntiles, pd, lut, dd, (uint32_t)strength,
+                               mask + (size_t)f0 * (frame / 3), fill);
+        else
+            hipLaunchKernelGGL((dotdiff_kernel<T, kDotBlock>), dim3(std::min(ntiles, cap), nf), dim3(kDotBlock), 0, s, in + (size_t)f0 * frame,
+                               out + (size_t)f0 * frame, h, w, ntx, ntiles, pd, lut, dd, (uint32_t)strength);
         prof_end(pm, s);
         DP_HIP(hipGetLastError());
     }
@@ -221,42 +289,45 @@ int launch_dotdiff(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
 }
 
 }  // namespace
-}  // namespace dp
 
-using namespace dp;
-
-extern "C" {
-
-int dp_dotdiff_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
-                  const uint8_t *classes_host, int m, int strength256, void *stream)
+int dotdiff_call(const char *fn, const bool masked, const uint8_t *in_dev, const uint8_t *mask_dev, const uint32_t fill, uint8_t *out_dev, int64_t n_frames,
+                 int h, int w, const dp_palette *pal, const uint8_t *classes_host, int m, int strength256, void *stream)
 {
     const bool sizes_ok = n_frames >= 0 && h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)1 << 30;
-    if (!pal || !classes_host || !sizes_ok || (n_frames > 0 && (!in_dev || !out_dev))) {
-        set_error("dp_dotdiff_u8: bad argument (pointers, n_frames >= 0, h, w >= 1, h * w <= 2^30)");
+    if (!pal || !classes_host || !sizes_ok || (n_frames > 0 && (!in_dev || !out_dev || (masked && !mask_dev)))) {
+        set_error("%s: bad argument (pointers, n_frames >= 0, h, w >= 1, h * w <= 2^30)", fn);
         return DP_EINVAL;
     }
     if (m != 2 && m != 4 && m != 8 && m != 16) {
-        set_error("dp_dotdiff_u8: the class matrix must be 2, 4, 8 or 16 wide, not %d", m);
+        set_error("%s: the class matrix must be 2, 4, 8 or 16 wide, not %d", fn, m);
         return DP_EINVAL;
     }
     if (!dotdiff_matrix_ok(classes_host, m)) {
-        set_error("dp_dotdiff_u8: the class matrix is not a permutation of 0 .. %d", m * m - 1);
+        set_error("%s: the class matrix is not a permutation of 0 .. %d", fn, m * m - 1);
         return DP_EINVAL;
     }
     if (strength256 < 0 || strength256 > 256) {
-        set_error("dp_dotdiff_u8: strength256 must lie in 0 .. 256, not %d", strength256);
+        set_error("%s: strength256 must lie in 0 .. 256, not %d", fn, strength256);
         return DP_EINVAL;
     }
     if (in_dev && out_dev == in_dev) {
-        set_error("dp_dotdiff_u8: out_dev must not be in_dev (tiles read a halo of their neighbours' input)");
+        set_error("%s: out_dev must not be in_dev (tiles read a halo of their neighbours' input)", fn);
         return DP_EINVAL;
     }
-    int rc = pattern_check_palette("dp_dotdiff_u8", pal);
+    if (masked && n_frames > 0) {
+        const size_t px = (size_t)n_frames * (size_t)h * (size_t)w;
+        const uintptr_t o = (uintptr_t)out_dev, i = (uintptr_t)in_dev, k = (uintptr_t)mask_dev;
+        if ((o < i + 3u * px && i < o + 3u * px) || (o < k + px && k < o + 3u * px)) {
+            set_error("%s: out_dev must not overlap in_dev or mask_dev", fn);
+            return DP_EINVAL;
+        }
+    }
+    int rc = pattern_check_palette(fn, pal);
     if (rc != DP_OK) return rc;
     int level[kDotDiffMaxCells];
     const int reach = dotdiff_levels(classes_host, m, level);
     if (reach > kDotDiffMaxReach) {
-        set_error("dp_dotdiff_u8: the class matrix has reach %d, at most %d is supported", reach, kDotDiffMaxReach);
+        set_error("%s: the class matrix has reach %d, at most %d is supported", fn, reach, kDotDiffMaxReach);
         return DP_EUNSUPPORTED;
     }
     if (n_frames == 0) return DP_OK;
@@ -279,7 +350,19 @@ int dp_dotdiff_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int
         std::lock_guard<std::mutex> lock(p->dev_mu);
         lut = p->dev.lut_in;
     }
-    return launch_dotdiff(in_dev, out_dev, n_frames, h, w, pattern_snapshot(pal), lut, dd, strength256, (hipStream_t)stream);
+    return launch_dotdiff(in_dev, out_dev, n_frames, h, w, pattern_snapshot(pal), lut, dd, strength256, (hipStream_t)stream, masked ? mask_dev : nullptr, fill);
+}
+
+}  // namespace dp
+
+using namespace dp;
+
+extern "C" {
+
+int dp_dotdiff_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h, int w, const dp_palette *pal,
+                  const uint8_t *classes_host, int m, int strength256, void *stream)
+{
+    return dotdiff_call("dp_dotdiff_u8", false, in_dev, nullptr, 0u, out_dev, n_frames, h, w, pal, classes_host, m, strength256, stream);
 }
 
 }  // extern "C"

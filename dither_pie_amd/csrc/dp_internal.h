@@ -336,6 +336,14 @@ int launch_wavelet(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int
 int pattern_check_palette(const char *fn, const dp_palette *p);
 int pattern_ensure_table(const dp_palette *pal, hipStream_t s);
 PatDev pattern_snapshot(const dp_palette *pal);
+// dp_idiff_u8 and dp_dotdiff_u8 behind their argument lists (idiff.hip, dotdiff.hip): checks, table build and launch, the refusals
+// naming `fn`.  masked: the call of include/ditherpie_hip_alpha.h -- mask (n_frames x h x w) must be there, out must overlap neither
+// in nor mask, masked pixels become `fill` (r | g << 8 | b << 16); otherwise mask and fill are not looked at
+int idiff_call(const char *fn, bool masked, const uint8_t *in_dev, const uint8_t *mask_dev, uint32_t fill, uint8_t *out_dev, int64_t n_frames, int h, int w,
+               const dp_palette *pal, const int32_t *dx, const int32_t *dy, const int32_t *weight, int n_taps, int divisor, int strength256,
+               void *workspace_dev, size_t workspace_bytes, void *stream);
+int dotdiff_call(const char *fn, bool masked, const uint8_t *in_dev, const uint8_t *mask_dev, uint32_t fill, uint8_t *out_dev, int64_t n_frames, int h, int w,
+                 const dp_palette *pal, const uint8_t *classes_host, int m, int strength256, void *stream);
 // metric palettes (metric.hip).  metric_refused: THE refusal of the entry points that would search a metric palette in RGB --
 // true (and the error set, naming `fn`) when pal is one.  metric_ensure_table_locked: the top-2 table, built on `s` and waited
 // for; the caller holds pal->build_mu.  launch_metric_rank_table: tab[a] = rank_of[nearest(a)], the pattern table of a metric palette

@@ -2742,4 +2742,87 @@ inline void hold_apply(const uint8_t *src, const uint8_t *planes, const int64_t 
     }
 }
 
+// ---- transparency (include/ditherpie_hip_alpha.h; tests/alpha_ref.py states it in numpy) ---------------------------------------
+constexpr int64_t kAlphaMaxFrames = 65535;
+constexpr int kAlphaMaxOrigin = 1 << 30;
+
+// -> 0, or the rule broken by the geometry of an alpha call: 1 n_frames < 0, 2 h or w < 1 or h * w >= 2^31, 3 more than 65535 frames
+inline int alpha_geometry_rule(const int64_t n, const int h, const int w)
+{
+    if (n < 0) return 1;
+    if (h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31)) return 2;
+    if (n > kAlphaMaxFrames) return 3;
+    return 0;
+}
+
+// -> 0, or the rule broken by the settings of a split: 4 a mode that is neither, 5 a threshold outside 0 .. 256, 6 an m that is none
+// of 2, 4, 8, 7 a y0 or x0 outside 0 .. 2^30.  Only the fields of the mode are looked at
+inline int alpha_split_rule(const int mode, const int threshold, const int m, const int y0, const int x0)
+{
+    if (mode != 0 && mode != 1) return 4;
+    if (mode == 0) return threshold < 0 || threshold > 256 ? 5 : 0;
+    if (m != 2 && m != 4 && m != 8) return 6;
+    if (y0 < 0 || y0 > kAlphaMaxOrigin || x0 < 0 || x0 > kAlphaMaxOrigin) return 7;
+    return 0;
+}
+
+// B_m[y mod m][x mod m] for m = 1 << bits (the rank matrix of cells_bayer_rank); constexpr, so device code may call it
+constexpr uint32_t alpha_bayer_rank(const int bits, const uint32_t y, const uint32_t x)
+{
+    uint32_t r = 0;
+    for (int j = 0; j < bits; ++j) {
+        const uint32_t yb = (y >> j) & 1u, xb = (x >> j) & 1u;
+        r |= (((xb ^ yb) << 1) | yb) << (2 * (bits - 1 - j));
+    }
+    return r;
+}
+
+// is the pixel at global (gy, gx) with this alpha transparent?  bits: 0 for DP_ALPHA_THRESHOLD, else log2 m of DP_ALPHA_ORDERED
+constexpr bool alpha_masked(const int bits, const uint32_t threshold, const uint32_t alpha, const uint32_t gy, const uint32_t gx)
+{
+    return bits == 0 ? alpha < threshold : (2u << (2 * bits)) * alpha < 255u * (2u * alpha_bayer_rank(bits, gy, gx) + 1u);
+}
+
+// a channel over the matte: (c alpha + M (255 - alpha) + 127) / 255
+constexpr uint32_t alpha_matte(const uint32_t c, const uint32_t alpha, const uint32_t matte)
+{
+    return (c * alpha + matte * (255u - alpha) + 127u) / 255u;
+}
+
+constexpr int alpha_bits(const int mode, const int m) { return mode == 0 ? 0 : (m == 8 ? 3 : (m == 4 ? 2 : 1)); }
+
+// The statements behind the _host_ entry points
+inline void alpha_split(const uint8_t *rgba, const int64_t n, const int h, const int w, const int mode, const int threshold, const int m,
+                        const int y0, const int x0, const bool has_matte, const uint8_t *matte, uint8_t *rgb, uint8_t *mask, int64_t *masked)
+{
+    const int bits = alpha_bits(mode, m);
+    const size_t px = (size_t)h * (size_t)w;
+    for (int64_t f = 0; f < n; ++f) {
+        int64_t count = 0;
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t i = (size_t)f * px + (size_t)y * (size_t)w + (size_t)x;
+                const uint32_t a = rgba[4 * i + 3];
+                for (int c = 0; c < 3; ++c) rgb[3 * i + c] = has_matte ? (uint8_t)alpha_matte(rgba[4 * i + c], a, matte[c]) : rgba[4 * i + c];
+                const bool t = alpha_masked(bits, (uint32_t)threshold, a, (uint32_t)y0 + (uint32_t)y, (uint32_t)x0 + (uint32_t)x);
+                mask[i] = t ? 1 : 0;
+                count += t ? 1 : 0;
+            }
+        masked[f] = count;
+    }
+}
+
+inline void alpha_key(const uint8_t *planes, const uint8_t *mask, const size_t px, const int key, uint8_t *out)
+{
+    for (size_t i = 0; i < px; ++i) out[i] = mask[i] ? (uint8_t)key : planes[i];
+}
+
+inline void alpha_join(const uint8_t *rgb, const uint8_t *mask, const size_t px, const uint8_t *fill, uint8_t *rgba)
+{
+    for (size_t i = 0; i < px; ++i) {
+        for (int c = 0; c < 3; ++c) rgba[4 * i + c] = mask[i] ? fill[c] : rgb[3 * i + c];
+        rgba[4 * i + 3] = mask[i] ? 0 : 255;
+    }
+}
+
 }  // namespace dp

@@ -1321,10 +1321,66 @@ static int run_hold(const char *path, const int n_cases, const char *out_path)
     return 0;
 }
 
+// ---- transparency: the host statements ---------------------------------------------------------------------------------------------
+// alpha record: n, h, w, mode, threshold, m, y0, x0, has_matte, key (int32), 3 matte bytes, 3 fill bytes, then (accepted cases only)
+// n*h*w*4 RGBA bytes.  The frames go through alpha_split; the planes of the key are the red channel mod 200, keyed with the mask the
+// split made; the join takes the split's RGB and mask.  Per accepted case out_path gets the RGB, the mask, n int64 counts, the keyed
+// planes and the RGBA, back to back; every vector has exactly the stated size.
+static int run_alpha(const char *path, const int n_cases, const char *out_path)
+{
+    FILE *f = fopen(path, "rb");
+    FILE *g = fopen(out_path, "wb");
+    if (!f || !g) {
+        fprintf(stderr, "cannot open %s or %s\n", path, out_path);
+        return 2;
+    }
+    for (int c = 0; c < n_cases; ++c) {
+        int32_t head[10];
+        uint8_t colours[6];
+        if (fread(head, sizeof(int32_t), 10, f) != 10 || fread(colours, 1, 6, f) != 6) {
+            fprintf(stderr, "bad record %d in %s\n", c, path);
+            return 2;
+        }
+        const int n = head[0], h = head[1], w = head[2], mode = head[3], threshold = head[4], m = head[5], y0 = head[6], x0 = head[7], key = head[9];
+        int rule = alpha_geometry_rule(n, h, w);
+        if (!rule) rule = alpha_split_rule(mode, threshold, m, y0, x0);
+        printf("alpha %d %d", c, rule);
+        if (!rule) {
+            if (n > 64 || key < 0 || key > 255) {
+                fprintf(stderr, "bad record %d in %s\n", c, path);
+                return 2;
+            }
+            const size_t px = (size_t)n * (size_t)h * (size_t)w;
+            std::vector<uint8_t> rgba(px * 4u), rgb(px * 3u), mask(px), planes(px), keyed(px), joined(px * 4u);
+            std::vector<int64_t> masked((size_t)n, -1);
+            if (fread(rgba.data(), 1, rgba.size(), f) != rgba.size()) {
+                fprintf(stderr, "bad record %d in %s\n", c, path);
+                return 2;
+            }
+            alpha_split(rgba.data(), n, h, w, mode, threshold, m, mode == 1 ? y0 : 0, mode == 1 ? x0 : 0, head[8] != 0, colours, rgb.data(), mask.data(),
+                        masked.data());
+            for (size_t i = 0; i < px; ++i) planes[i] = (uint8_t)(rgba[4 * i] % 200);
+            alpha_key(planes.data(), mask.data(), px, key, keyed.data());
+            alpha_join(rgb.data(), mask.data(), px, colours + 3, joined.data());
+            if (fwrite(rgb.data(), 1, rgb.size(), g) != rgb.size() || fwrite(mask.data(), 1, mask.size(), g) != mask.size() ||
+                fwrite(masked.data(), sizeof(int64_t), masked.size(), g) != masked.size() || fwrite(keyed.data(), 1, keyed.size(), g) != keyed.size() ||
+                fwrite(joined.data(), 1, joined.size(), g) != joined.size())
+                return 2;
+            long long total = 0;
+            for (const int64_t v : masked) total += v;
+            printf(" %lld", total);
+        }
+        printf("\n");
+    }
+    fclose(f);
+    fclose(g);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  fixneeded <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>  |  hold <cases.bin> <n> <out.bin>\n", argv[0]);
+        fprintf(stderr, "usage: %s kdtree|edtables|accel <pts.f64> <K> [bw]  |  edtablesdigest <pts.f64> <K> <what>  |  mediancut <rgb.u8> <n> <depth>  |  indexmap <lists.bin> <n>  |  giflzw <cases.bin> <n>  |  pngdeflate|pngdyn|pngfile <cases.bin> <n>  |  orderedplan <cases.bin> <n>  |  voidcluster <cases.bin> <n>  |  metric <cases.bin> <n>  |  finepack <pal.u8> <K> <out.bin>  |  fineplan <cases.bin> <n>  |  finekeys <cases.bin> <n>  |  finesub <pal.u8> <K> <out.bin>  |  finesublevel <cases.bin> <n>  |  finechoice <cases.bin> <n>  |  fineaddr <first> <n>  |  fixneeded <cases.bin> <n>  |  idiffplan <cases.bin> <n>  |  okfit <cases.bin> <n>  |  resamplecoeffs <cases.bin> <n>  |  resample <cases.bin> <n> <out.bin>  |  hold <cases.bin> <n> <out.bin>  |  alpha <cases.bin> <n> <out.bin>\n", argv[0]);
         return 2;
     }
     if (std::string(argv[1]) == "mediancut") return run_mediancut(argv[2], atol(argv[3]), argc > 4 ? atoi(argv[4]) : 4);
@@ -1349,6 +1405,7 @@ int main(int argc, char **argv)
     if (std::string(argv[1]) == "resamplecoeffs") return run_resamplecoeffs(argv[2], atoi(argv[3]));
     if (std::string(argv[1]) == "resample") return argc > 4 ? run_resample(argv[2], atoi(argv[3]), argv[4]) : 2;
     if (std::string(argv[1]) == "hold") return argc > 4 ? run_hold(argv[2], atoi(argv[3]), argv[4]) : 2;
+    if (std::string(argv[1]) == "alpha") return argc > 4 ? run_alpha(argv[2], atoi(argv[3]), argv[4]) : 2;
     const int K = atoi(argv[3]);
     if (K < 1 || K > 1024) return 2;
     const std::vector<double> pts = read_pts(argv[2], K);

@@ -47,11 +47,28 @@ __device__ __forceinline__ uint32_t nearest_rank(const PatDev &pd, const uint32_
 // sign(e) * ((|e| * q) >> 16): the arithmetic shift floors, so a negative e gets 65535 added first.  |e| <= 4080, q <= 65536
 __device__ __forceinline__ int share(const int e, const int q) { return (__mul24(e, q) + (int)((uint32_t)e >> 16)) >> 16; }
 
-template <int PERIOD, int NT>
+// the arguments of a MASKED instance behind bnd_all: the mask (n_frames x h x w bytes, non-zero = transparent) and fill (r | g << 8 | b << 16)
+__device__ __forceinline__ const uint8_t *id_mask_of(const uint8_t *mask_all, uint32_t) { return mask_all; }
+__device__ __forceinline__ uint32_t id_fill_of(const uint8_t *, const uint32_t fill) { return fill; }
+
+// MASK is empty -- the instances of include/ditherpie_hip_idiff.h, whose argument list and code are what they were before the pack
+// existed -- or (const uint8_t *, uint32_t): the MASKED instances of include/ditherpie_hip_alpha.h.  There the PERIOD mask bytes of a
+// lane's next period travel with its pixel prefetch; a step at a transparent pixel stores zero errors into the ring and into s_bout
+// and `fill` into the output bytes, and skips its LDS reads and the gather as a step outside the row does; fences and wave barriers
+// stand where they stood.  (mpix, mcur, frame_px, fmask and fill are declared in every instance; an unmasked one never reads them and
+// the compiler drops them.)
+// Why a pack and not a `bool MASKED` with two trailing arguments: a trailing kernel argument, used or not, moves the hidden arguments
+// (the group size the runtime passes behind the explicit ones), which changes an immediate in the unmasked instances; with an empty
+// pack their argument list is byte for byte the old one and their gfx950 instruction streams are unchanged (DESIGN.md 4.4 has the
+// comparison).  Whoever adds a trailing argument to this kernel moves them for every instance and repeats that comparison.
+template <int PERIOD, int NT, typename... MASK>
 __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const int h,
                                                                  const int w, const PatDev pd, const uint8_t *__restrict__ lut,
-                                                                 const IdiffPlan taps, uint64_t *__restrict__ bnd_all)
+                                                                 const IdiffPlan taps, uint64_t *__restrict__ bnd_all, const MASK... mask_args)
 {
+    constexpr bool MASKED = sizeof...(MASK) != 0;
+    static_assert(sizeof...(MASK) == 0 || sizeof...(MASK) == 2, "no mask arguments, or the mask and the fill");
+    constexpr int MW = PERIOD / 4;       // dwords of a period's mask bytes (MASKED)
     constexpr int PW = PERIOD * 3 / 4;   // dwords of a period's pixels
     static_assert(PERIOD % 4 == 0 && PERIOD >= 8 && PERIOD <= 16, "the boundary fetch covers 32 columns per period");
     __shared__ uint32_t s_ring[kIdMaxWaves][64][kIdRingStride];   // errors of the band's own rows: r | g << 16, b
@@ -75,6 +92,13 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
     const uint8_t *fin = in + (size_t)blockIdx.x * (size_t)frame_bytes;
     uint8_t *fout = out + (size_t)blockIdx.x * (size_t)frame_bytes;
     uint64_t *bnd = bnd_all + (size_t)blockIdx.x * 4u * (size_t)w;   // [2 buffers][2 rows][w]
+    const long frame_px = (long)h * w;
+    const uint8_t *__restrict__ fmask = nullptr;
+    uint32_t fill = 0u;
+    if constexpr (MASKED) {
+        fmask = id_mask_of(mask_args...) + (size_t)blockIdx.x * (size_t)frame_px;
+        fill = id_fill_of(mask_args...);
+    }
     const int skew = taps.skew;
     const int n_bands = (h + 63) / 64;
     const uint32_t w1 = (uint32_t)w + 1u;
@@ -108,6 +132,9 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
         for (int k = 0; k < PW; ++k) pix[k] = 0;
 #pragma unroll
         for (int k = 0; k < PW + 1; ++k) cur[k] = outb[k] = 0;
+        uint32_t mpix[MW], mcur[MW];                   // (MASKED) a period's mask bytes in flight / being consumed, one per column
+#pragma unroll
+        for (int k = 0; k < MW; ++k) mpix[k] = mcur[k] = 0;
 
         for (int t0 = -PERIOD; t0 < steps + PERIOD; t0 += PERIOD) {
             // ================= period boundary: everything issued one period ago has landed =================
@@ -138,6 +165,10 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
             // ---- the pixels fetched during the previous period become current; fetch the next period's
 #pragma unroll
             for (int k = 0; k < PW; ++k) cur[k] = pix[k];
+            if constexpr (MASKED) {
+#pragma unroll
+                for (int k = 0; k < MW; ++k) mcur[k] = mpix[k];
+            }
             {
                 const int xn = (t0 + PERIOD) - skew * L;   // first column of the NEXT period
                 const long B = row_byte + (long)xn * 3;
@@ -155,6 +186,26 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                                 if (a >= 0 && a < frame_bytes) v |= (uint32_t)fin[a] << (8 * bb);
                             }
                             pix[k] = v;
+                        }
+                    }
+                    if constexpr (MASKED) {
+                        // the PERIOD mask bytes of the same columns: byte r * w + xn of the frame's mask, at any alignment; bytes in front
+                        // of the frame or behind it read as 0 (the columns they stand for are outside the row and never looked at)
+                        const long MB = (long)r * w + xn;
+                        if (MB >= 0 && MB + 4 * MW <= frame_px) {
+#pragma unroll
+                            for (int k = 0; k < MW; ++k) mpix[k] = *reinterpret_cast<const uint32_t *>(fmask + MB + 4 * k);
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < MW; ++k) {
+                                uint32_t v = 0;
+#pragma unroll
+                                for (int bb = 0; bb < 4; ++bb) {
+                                    const long a = MB + 4 * k + bb;
+                                    if (a >= 0 && a < frame_px) v |= (uint32_t)fmask[a] << (8 * bb);
+                                }
+                                mpix[k] = v;
+                            }
                         }
                     }
                 }
@@ -196,7 +247,14 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     const bool act = row_ok && (uint32_t)x < (uint32_t)w;
                     int e0 = 0, e1 = 0, e2 = 0;
                     uint32_t cbytes = 0;
-                    if (act) {
+                    // (MASKED) a transparent pixel takes no part: zero errors go into the ring and into s_bout below, its bytes are `fill`
+                    bool live = act;
+                    if constexpr (MASKED) {
+                        const bool hidden = ((mcur[0] >> (8 * q)) & 255u) != 0u;
+                        live = act && !hidden;
+                        if (act && hidden) cbytes = fill;
+                    }
+                    if (live) {
                         const uint32_t pxv = band_pixel(cur, q);
                         uint32_t c0 = pxv & 255u, c1 = (pxv >> 8) & 255u, c2 = (pxv >> 16) & 255u;
                         if (lut) {
@@ -250,6 +308,11 @@ __global__ __launch_bounds__(64 * kIdMaxWaves) void idiff_kernel(const uint8_t *
                     __builtin_amdgcn_wave_barrier();
                 }
                 band_advance<PERIOD>(cur, outb, cb);
+                if constexpr (MASKED) {   // the round's four mask bytes are consumed
+#pragma unroll
+                    for (int k = 0; k < MW - 1; ++k) mcur[k] = mcur[k + 1];
+                    mcur[MW - 1] = 0u;
+                }
             }
         }
         // band finished: once its boundary stores have landed the band below may read any column
@@ -266,17 +329,24 @@ size_t idiff_ws_bytes(const int64_t n_frames, const int h, const int w)
     return (size_t)n_frames * 4u * (size_t)w * sizeof(uint64_t);
 }
 
-template <int PERIOD>
+template <int PERIOD, bool MASKED>
 void launch_one(const dim3 grid, const dim3 block, hipStream_t s, const uint8_t *in, uint8_t *out, int h, int w, const PatDev &pd, const uint8_t *lut,
-                const IdiffPlan &taps, uint64_t *bnd)
+                const IdiffPlan &taps, uint64_t *bnd, const uint8_t *mask, const uint32_t fill)
 {
-    if (taps.n <= 4) hipLaunchKernelGGL((idiff_kernel<PERIOD, 4>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
-    else if (taps.n <= 7) hipLaunchKernelGGL((idiff_kernel<PERIOD, 7>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
-    else hipLaunchKernelGGL((idiff_kernel<PERIOD, kIdiffMaxTaps>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
+    if constexpr (MASKED) {
+        if (taps.n <= 4) hipLaunchKernelGGL((idiff_kernel<PERIOD, 4, const uint8_t *, uint32_t>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd, mask, fill);
+        else if (taps.n <= 7) hipLaunchKernelGGL((idiff_kernel<PERIOD, 7, const uint8_t *, uint32_t>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd, mask, fill);
+        else hipLaunchKernelGGL((idiff_kernel<PERIOD, kIdiffMaxTaps, const uint8_t *, uint32_t>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd, mask, fill);
+    } else {
+        if (taps.n <= 4) hipLaunchKernelGGL((idiff_kernel<PERIOD, 4>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
+        else if (taps.n <= 7) hipLaunchKernelGGL((idiff_kernel<PERIOD, 7>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
+        else hipLaunchKernelGGL((idiff_kernel<PERIOD, kIdiffMaxTaps>), grid, block, 0, s, in, out, h, w, pd, lut, taps, bnd);
+    }
 }
 
+// mask: nullptr for the unmasked instances, else n_frames x h x w bytes and the MASKED ones (masked pixels become `fill`)
 int launch_idiff(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w, const PatDev &pd, const uint8_t *lut, const IdiffPlan &plan,
-                 void *ws, hipStream_t s)
+                 void *ws, hipStream_t s, const uint8_t *mask = nullptr, const uint32_t fill = 0)
 {
     IdiffPlan taps = plan;
     for (int k = taps.n; k < kIdiffMaxTaps; ++k) {   // the spare slots of an instance: a tap of the row itself with share 0
@@ -293,12 +363,68 @@ int launch_idiff(const uint8_t *in, uint8_t *out, int64_t n_frames, int h, int w
         const uint32_t nf = (uint32_t)std::min<int64_t>(65535, n_frames - f0);
         uint64_t *bnd = reinterpret_cast<uint64_t *>(ws) + (size_t)f0 * 4u * (size_t)w;
         ProfMark *pm = prof_begin(s);
-        if (period == 8) launch_one<8>(dim3(nf), block, s, in + (size_t)f0 * frame, out + (size_t)f0 * frame, h, w, pd, lut, taps, bnd);
-        else launch_one<16>(dim3(nf), block, s, in + (size_t)f0 * frame, out + (size_t)f0 * frame, h, w, pd, lut, taps, bnd);
+        const uint8_t *fin = in + (size_t)f0 * frame, *fm = mask ? mask + (size_t)f0 * (frame / 3) : nullptr;
+        uint8_t *fout = out + (size_t)f0 * frame;
+        if (mask && period == 8) launch_one<8, true>(dim3(nf), block, s, fin, fout, h, w, pd, lut, taps, bnd, fm, fill);
+        else if (mask) launch_one<16, true>(dim3(nf), block, s, fin, fout, h, w, pd, lut, taps, bnd, fm, fill);
+        else if (period == 8) launch_one<8, false>(dim3(nf), block, s, fin, fout, h, w, pd, lut, taps, bnd, nullptr, 0u);
+        else launch_one<16, false>(dim3(nf), block, s, fin, fout, h, w, pd, lut, taps, bnd, nullptr, 0u);
         prof_end(pm, s);
         DP_HIP(hipGetLastError());
     }
     return DP_OK;
+}
+
+int idiff_call(const char *fn, const bool masked, const uint8_t *in_dev, const uint8_t *mask_dev, const uint32_t fill, uint8_t *out_dev, int64_t n_frames,
+               int h, int w, const dp_palette *pal, const int32_t *dx, const int32_t *dy, const int32_t *weight, int n_taps, int divisor, int strength256,
+               void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    const bool sizes_ok = n_frames >= 0 && h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)1 << 30;
+    if (!pal || !dx || !dy || !weight || !sizes_ok || (n_frames > 0 && (!in_dev || !out_dev || !workspace_dev || (masked && !mask_dev)))) {
+        set_error("%s: bad argument (pointers, n_frames >= 0, h, w >= 1, h * w <= 2^30)", fn);
+        return DP_EINVAL;
+    }
+    IdiffPlan plan;
+    static const char *const kRule[] = {"", "a NULL tap array", "n_taps must lie in 1 .. 12", "the divisor must be at least 1",
+                                        "strength256 must lie in 0 .. 256", "a tap outside dy 0 .. 2, dx -2 .. 2, dy == 0 with dx >= 1",
+                                        "a (dx, dy) given twice", "a negative weight", "weights that sum to more than the divisor"};
+    if (const int bad = idiff_plan(dx, dy, weight, n_taps, divisor, strength256, plan)) {
+        set_error("%s: %s (n_taps %d, divisor %d, strength256 %d)", fn, kRule[bad], n_taps, divisor, strength256);
+        return DP_EINVAL;
+    }
+    if (in_dev && out_dev == in_dev) {
+        set_error("%s: out_dev must not be in_dev", fn);
+        return DP_EINVAL;
+    }
+    if (masked && n_frames > 0) {
+        const size_t px = (size_t)n_frames * (size_t)h * (size_t)w;
+        const uintptr_t o = (uintptr_t)out_dev, i = (uintptr_t)in_dev, m = (uintptr_t)mask_dev;
+        if ((o < i + 3u * px && i < o + 3u * px) || (o < m + px && m < o + 3u * px)) {
+            set_error("%s: out_dev must not overlap in_dev or mask_dev", fn);
+            return DP_EINVAL;
+        }
+    }
+    if (workspace_dev && ((uintptr_t)workspace_dev & 15u)) {
+        set_error("%s: the workspace must be 16-byte aligned", fn);
+        return DP_EINVAL;
+    }
+    int rc = pattern_check_palette(fn, pal);
+    if (rc != DP_OK) return rc;
+    if (n_frames == 0) return DP_OK;
+    if (workspace_bytes < idiff_ws_bytes(n_frames, h, w)) {
+        set_error("%s: workspace too small (need %zu bytes)", fn, idiff_ws_bytes(n_frames, h, w));
+        return DP_EWORKSPACE;
+    }
+    rc = pattern_ensure_table(pal, (hipStream_t)stream);
+    if (rc != DP_OK) return rc;
+    const uint8_t *lut;
+    {
+        dp_palette *p = const_cast<dp_palette *>(pal);
+        std::lock_guard<std::mutex> lock(p->dev_mu);
+        lut = p->dev.lut_in;
+    }
+    return launch_idiff(in_dev, out_dev, n_frames, h, w, pattern_snapshot(pal), lut, plan, workspace_dev, (hipStream_t)stream, masked ? mask_dev : nullptr,
+                        fill);
 }
 
 }  // namespace dp
@@ -313,43 +439,8 @@ int dp_idiff_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int h
                 const int32_t *dy, const int32_t *weight, int n_taps, int divisor, int strength256, void *workspace_dev, size_t workspace_bytes,
                 void *stream)
 {
-    const bool sizes_ok = n_frames >= 0 && h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)1 << 30;
-    if (!pal || !dx || !dy || !weight || !sizes_ok || (n_frames > 0 && (!in_dev || !out_dev || !workspace_dev))) {
-        set_error("dp_idiff_u8: bad argument (pointers, n_frames >= 0, h, w >= 1, h * w <= 2^30)");
-        return DP_EINVAL;
-    }
-    IdiffPlan plan;
-    static const char *const kRule[] = {"", "a NULL tap array", "n_taps must lie in 1 .. 12", "the divisor must be at least 1",
-                                        "strength256 must lie in 0 .. 256", "a tap outside dy 0 .. 2, dx -2 .. 2, dy == 0 with dx >= 1",
-                                        "a (dx, dy) given twice", "a negative weight", "weights that sum to more than the divisor"};
-    if (const int bad = idiff_plan(dx, dy, weight, n_taps, divisor, strength256, plan)) {
-        set_error("dp_idiff_u8: %s (n_taps %d, divisor %d, strength256 %d)", kRule[bad], n_taps, divisor, strength256);
-        return DP_EINVAL;
-    }
-    if (in_dev && out_dev == in_dev) {
-        set_error("dp_idiff_u8: out_dev must not be in_dev");
-        return DP_EINVAL;
-    }
-    if (workspace_dev && ((uintptr_t)workspace_dev & 15u)) {
-        set_error("dp_idiff_u8: the workspace must be 16-byte aligned");
-        return DP_EINVAL;
-    }
-    int rc = pattern_check_palette("dp_idiff_u8", pal);
-    if (rc != DP_OK) return rc;
-    if (n_frames == 0) return DP_OK;
-    if (workspace_bytes < idiff_ws_bytes(n_frames, h, w)) {
-        set_error("dp_idiff_u8: workspace too small (need %zu bytes)", idiff_ws_bytes(n_frames, h, w));
-        return DP_EWORKSPACE;
-    }
-    rc = pattern_ensure_table(pal, (hipStream_t)stream);
-    if (rc != DP_OK) return rc;
-    const uint8_t *lut;
-    {
-        dp_palette *p = const_cast<dp_palette *>(pal);
-        std::lock_guard<std::mutex> lock(p->dev_mu);
-        lut = p->dev.lut_in;
-    }
-    return launch_idiff(in_dev, out_dev, n_frames, h, w, pattern_snapshot(pal), lut, plan, workspace_dev, (hipStream_t)stream);
+    return idiff_call("dp_idiff_u8", false, in_dev, nullptr, 0u, out_dev, n_frames, h, w, pal, dx, dy, weight, n_taps, divisor, strength256, workspace_dev,
+                      workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -52,14 +52,15 @@ def _pinned_pair(nbytes: int):
         bufs.move_to_end(nbytes)
     return pair
 
-def _pil_rgbx_into(rgb, host_u8) -> bool:
+def _pil_rgbx_into(rgb, host_u8, rawmode="RGBX") -> bool:
     """The pixels of a PIL 'RGB' image in Pillow's own four-bytes-per-pixel layout, written into `host_u8` (a uint8 numpy view of
     h * w * 4 bytes) in pieces, with no intermediate bytes object of the whole image: what Image.tobytes("raw", "RGBX") does,
-    minus its b"".join and the caller's copy.  False when the (private, long-stable) encoder interface is not there."""
+    minus its b"".join and the caller's copy.  False when the (private, long-stable) encoder interface is not there.
+    rawmode="RGBA" does the same for an 'RGBA' image (the alpha paths)."""
     try:
         from PIL import Image
         rgb.load()
-        enc = Image._getencoder(rgb.mode, "raw", "RGBX")
+        enc = Image._getencoder(rgb.mode, "raw", rawmode)
         enc.setimage(rgb.im, (0, 0) + rgb.size)
         pos, total = 0, host_u8.shape[0]
         piece = max(1 << 20, rgb.size[0] * 4)   # (the raw encoder emits whole rows: RawEncode.c)
@@ -84,7 +85,7 @@ __all__ = [
     "ErrorDiffusionDitherStrategy", "PolkaDotDitherStrategy", "PerceptualDitherStrategy", "HybridDitherStrategy",
     "AdaptiveVarianceDitherStrategy", "OstromoukhovDitherStrategy", "RiemersmaDitherStrategy", "HalftoneDitherStrategy",
     "WaveletDitherStrategy", "PatternDitherStrategy", "DotDiffusionDitherStrategy", "CellPaletteDitherStrategy",
-    "IntegerErrorDiffusionDitherStrategy",
+    "IntegerErrorDiffusionDitherStrategy", "AlphaMode",
     "generate_blue_noise", "generate_void_and_cluster", "VoidAndClusterDitherStrategy",
 ]
 
@@ -1329,6 +1330,12 @@ class DotDiffusionDitherStrategy(BaseDitherStrategy):
         classes, s256 = self._settings()
         return backend.dotdiff(frames, pal, classes, s256, out=out)
 
+    def _run_masked(self, frames, mask, pal, fill, out=None):
+        """_run under a mask (backend.dotdiff_masked): transparent pixels become `fill` and take no part in the diffusion."""
+        from . import backend
+        classes, s256 = self._settings()
+        return backend.dotdiff_masked(frames, mask, pal, classes, s256, fill=fill, out=out)
+
     def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
         h, w = image_size
         if h <= 0 or w <= 0:
@@ -1406,6 +1413,12 @@ class IntegerErrorDiffusionDitherStrategy(BaseDitherStrategy):
             raise ValueError("integer error diffusion hands errors across every band edge and cannot be tiled by the caller")
         taps, divisor, s256 = self._settings()
         return backend.idiff(frames, pal, taps, divisor, s256, out=out)
+
+    def _run_masked(self, frames, mask, pal, fill, out=None):
+        """_run under a mask (backend.idiff_masked): transparent pixels become `fill` and take no part in the diffusion."""
+        from . import backend
+        taps, divisor, s256 = self._settings()
+        return backend.idiff_masked(frames, mask, pal, taps, divisor, s256, fill=fill, out=out)
 
     def dither(self, pixels: np.ndarray, palette_arr: np.ndarray, image_size: Tuple[int, int]) -> np.ndarray:
         h, w = image_size
@@ -1580,6 +1593,62 @@ ORDERED_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradien
 # through the palette's top-2 table (backend.ordered in nearest and matrix mode) or its rank table (pattern, dotdiff, idiff)
 _METRIC_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, PatternDitherStrategy, DotDiffusionDitherStrategy,
                       IntegerErrorDiffusionDitherStrategy)
+
+
+# ------------------------------------------------------------------------------------- Transparency
+# which strategies take an alpha mask: the position-only ones are dithered as always and masked afterwards, the two table
+# diffusions run their masked kernels (_run_masked); nothing else does, and nothing falls back to ignoring the mask
+_ALPHA_POSITION_STRATEGIES = (NoDitherStrategy, MatrixDitherStrategy, InterleavedGradientNoiseDitherStrategy, PatternDitherStrategy)
+_ALPHA_MASKED_STRATEGIES = (IntegerErrorDiffusionDitherStrategy, DotDiffusionDitherStrategy)
+
+
+class AlphaMode:
+    """How the alpha channel of an RGBA source becomes the one-bit transparency of a palettised result
+    (include/ditherpie_hip_alpha.h has the integer definitions).  Asked for per call (ImageDitherer.apply_dithering_rgba,
+    apply_dithering_indexed_alpha, apply_dithering_png(alpha=...), apply_dithering_frames_alpha): the ditherer itself has no alpha
+    setting.
+
+    mode       "threshold": a pixel is transparent where alpha < threshold (0 .. 256); "ordered": the alpha channel is itself
+               dithered with the Bayer matrix `matrix` ("2x2", "4x4", "8x8"), so a soft edge becomes a stipple
+    matte      None, or the colour the RGB is composited over before dithering: what half-transparent pixels that end up opaque
+               are blended with
+    fill       the colour bytes under a transparent pixel in the output (palette entry K of the indexed results)
+    Transparent pixels take no part: the palette (palette=None) is fitted to the opaque pixels, and the diffusion modes neither
+    read their hidden colour nor push error across them.  Not in the reference."""
+
+    MODES = ("threshold", "ordered")
+    MATRICES = ("2x2", "4x4", "8x8")
+
+    def __init__(self, mode: str = "threshold", threshold: int = 128, matrix: str = "4x4", matte=None, fill=(0, 0, 0)):
+        self.mode = mode
+        self.threshold = threshold
+        self.matrix = matrix
+        self.matte = matte
+        self.fill = fill
+
+    def __repr__(self):
+        return f"AlphaMode(mode={self.mode!r}, threshold={self.threshold!r}, matrix={self.matrix!r}, matte={self.matte!r}, fill={self.fill!r})"
+
+    def _settings(self):
+        """-> (mode, threshold, m, matte or None, fill) checked; ValueError otherwise (no device needed)."""
+        if self.mode not in self.MODES:
+            raise ValueError(f"alpha mode must be one of {self.MODES}, not {self.mode!r}")
+        if isinstance(self.threshold, bool) or not isinstance(self.threshold, (int, np.integer)) or not 0 <= self.threshold <= 256:
+            raise ValueError(f"alpha threshold must be an integer in 0 .. 256, not {self.threshold!r}")
+        if self.matrix not in self.MATRICES:
+            raise ValueError(f"alpha matrix must be one of {self.MATRICES}, not {self.matrix!r}")
+
+        def colour(c, what):
+            try:
+                t = tuple(int(v) for v in c)
+                ok = len(t) == 3 and all(a == b for a, b in zip(t, c)) and all(0 <= v <= 255 for v in t)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"alpha {what} must be three integers in 0 .. 255, not {c!r}")
+            return t
+        matte = None if self.matte is None else colour(self.matte, "matte")
+        return self.mode, int(self.threshold), int(self.matrix.split("x")[0]), matte, colour(self.fill, "fill")
 
 
 # ------------------------------------------------------------------------------------- ImageDitherer
@@ -1760,13 +1829,146 @@ class ImageDitherer:
         out.putpalette(colours.reshape(-1).tolist(), "RGB")
         return out
 
-    def apply_dithering_png(self, image, seg_bytes=None, blocks="fixed", assemble="host") -> bytes:
+    # -- transparency (include/ditherpie_hip_alpha.h) ------------------------------------------
+    def _alpha_strategy(self):
+        """The strategy of this ditherer if it takes a mask, ValueError naming the supported ones otherwise: before any launch."""
+        if not self.dither_mode:
+            self.dither_mode = DitherMode.NONE
+        strategy = self._get_dither_strategy(self.dither_mode)
+        if not isinstance(strategy, _ALPHA_POSITION_STRATEGIES + _ALPHA_MASKED_STRATEGIES):
+            name = self.dither_mode.value if isinstance(self.dither_mode, DitherMode) else type(strategy).__name__
+            raise ValueError(f"dither mode {name!r} does not take an alpha mask (supported: none, bayer, blue_noise, polka_dot, IGN, "
+                             "MatrixDitherStrategy instances, PatternDitherStrategy, IntegerErrorDiffusionDitherStrategy, "
+                             "DotDiffusionDitherStrategy)")
+        self._check_metric(strategy)
+        return strategy
+
+    def _dither_alpha(self, frames_rgba, alpha, y0, x0, kernel_fill):
+        """-> (dithered rgb [N,H,W,3], mask [N,H,W], colour under the masked pixels of the diffusions).  kernel_fill: None for
+        alpha.fill, "first" for the palette's first output colour (the indexed paths: to_indices then meets no missing colour)."""
+        import torch
+        from . import backend
+        if not isinstance(alpha, AlphaMode):
+            raise ValueError(f"alpha must be an AlphaMode, not {alpha!r}")
+        mode, threshold, m, matte, fill = alpha._settings()
+        strategy = self._alpha_strategy()
+        if not (isinstance(frames_rgba, torch.Tensor) and frames_rgba.is_cuda and frames_rgba.dtype == torch.uint8
+                and frames_rgba.dim() in (3, 4) and frames_rgba.shape[-1] == 4):
+            raise ValueError("frames must be a CUDA uint8 tensor [N,H,W,4] or [H,W,4]")
+        with torch.cuda.device(frames_rgba.device):
+            rgb, mask, _ = backend.alpha_split(frames_rgba, mode, threshold, m, matte, y0 if mode == "ordered" else 0,
+                                               x0 if mode == "ordered" else 0)
+            if self.palette is None:
+                first_rgb, first_mask = (rgb, mask) if rgb.dim() == 3 else (rgb[0], mask[0])
+                seen = first_rgb[first_mask == 0]                      # the opaque pixels of the first frame after the matte, raster order
+                if seen.shape[0] == 0:
+                    raise ValueError("the first frame has no opaque pixel: there is nothing to fit a palette to")
+                self._ensure_palette(np.ascontiguousarray(seen.cpu().numpy().reshape(1, -1, 3)))
+            pal = self._palette_on_device(strategy)
+            if kernel_fill == "first":
+                fill = tuple(int(v) for v in prepare_palette(self.palette, self.use_gamma)[1][0])
+            if isinstance(strategy, _ALPHA_MASKED_STRATEGIES):
+                if y0 or x0:
+                    raise ValueError("the diffusion modes hand errors across every edge a caller could cut: no (y0, x0)")
+                return strategy._run_masked(rgb, mask, pal, fill), mask, fill
+            return strategy._run(rgb, pal, y0=y0, x0=x0), mask, fill
+
+    def apply_dithering_frames_alpha(self, frames_rgba, alpha, y0: int = 0, x0: int = 0):
+        """uint8 CUDA tensor [N,H,W,4] (or [H,W,4]) -> (rgb [N,H,W,3] dithered, mask [N,H,W] with 1 at the transparent pixels), both in
+        HBM.  The RGB under a transparent pixel is not specified (alpha.fill in the diffusion modes, the dither of the hidden colour
+        in the position-only ones): backend.alpha_join(rgb, mask, alpha.fill) makes the RGBA frame.  palette=None is fitted to the
+        opaque pixels of the first frame after the matte (ValueError when there is none).  The position-only modes (none, the
+        threshold matrices, IGN, PatternDitherStrategy) dither as always and are masked afterwards; IntegerErrorDiffusionDitherStrategy
+        and DotDiffusionDitherStrategy run their masked kernels; every other mode is a ValueError before any launch.  (y0, x0): the
+        global coordinates of the frames' first pixel, for the position-only modes and the ordered alpha matrix."""
+        rgb, mask, _ = self._dither_alpha(frames_rgba, alpha, y0, x0, None)
+        return rgb, mask
+
+    def _check_alpha_colours(self):
+        if self.palette is not None and len(self.palette) > 255:
+            raise ValueError(f"an indexed result with a transparent key holds at most 255 colours, the palette has {len(self.palette)}")
+
+    def apply_dithering_frames_indexed_alpha(self, frames_rgba, alpha, y0: int = 0, x0: int = 0):
+        """apply_dithering_frames_alpha() as index planes: -> (planes [N,H,W] uint8, palette_u8 [K + 1, 3] numpy, key) with key = K, the
+        index of every transparent pixel, palette_u8[K] = alpha.fill and palette_u8[planes] the RGB result at the opaque pixels.
+        ValueError above 255 colours (the key needs an entry of its own, as the GIF / APNG writers' does)."""
+        import torch
+        from . import backend
+        if isinstance(alpha, AlphaMode):
+            alpha._settings()
+        self._alpha_strategy()
+        if self.palette is None and self.num_colors > 255:
+            raise ValueError(f"an indexed result with a transparent key holds at most 255 colours, not {self.num_colors}")
+        self._check_alpha_colours()
+        rgb, mask, _ = self._dither_alpha(frames_rgba, alpha, y0, x0, "first")
+        self._check_alpha_colours()
+        with torch.cuda.device(rgb.device):
+            planes, colours = _indexed(rgb, self.palette, self.use_gamma, None)
+            key = colours.shape[0]
+            backend.alpha_key(planes, mask, key, out=planes)
+        return planes, np.concatenate([colours, np.asarray(alpha.fill, np.uint8).reshape(1, 3)]), key
+
+    @staticmethod
+    def _rgba_on_device(image):
+        """PIL image -> its pixels as a uint8 CUDA tensor [H,W,4] (an image without an alpha channel is fully opaque): Pillow's raw
+        'RGBA' encoder into the pinned four-byte buffer the RGB path uses."""
+        rgba = image if image.mode == "RGBA" else image.convert("RGBA")
+        w, h = rgba.size
+        if w < 1 or h < 1:
+            raise ValueError("the image has no pixel")
+        pin_in, pin_out = _pinned_pair(h * w * 4)
+        if not _pil_rgbx_into(rgba, pin_in.numpy(), "RGBA"):
+            np.copyto(pin_in.numpy(), np.frombuffer(rgba.tobytes(), dtype=np.uint8))
+        return pin_in.view(h, w, 4).cuda(non_blocking=True), pin_out
+
+    def apply_dithering_rgba(self, image, alpha=None):
+        """PIL image (any mode; 'RGBA' is what it is for) -> PIL 'RGBA' image: the dither of the opaque pixels with alpha 255, alpha.fill
+        with alpha 0 at the transparent ones (alpha: an AlphaMode, default AlphaMode())."""
+        import torch
+        from PIL import Image
+        from . import backend
+        alpha = AlphaMode() if alpha is None else alpha
+        dev, pin_out = self._rgba_on_device(image)
+        h, w, _ = dev.shape
+        rgb, mask = self.apply_dithering_frames_alpha(dev, alpha)
+        out = backend.alpha_join(rgb, mask, alpha._settings()[4])
+        pin_out.view(h, w, 4).copy_(out, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return Image.frombytes("RGBA", (w, h), pin_out.numpy())       # (a copy into the image's own storage)
+
+    def apply_dithering_indexed_alpha(self, image, alpha=None):
+        """PIL image -> PIL 'P' image with info["transparency"] = K: entries 0 .. K-1 are the palette's out_colors, entry K is
+        alpha.fill and is the index of every transparent pixel; convert("RGBA") equals apply_dithering_rgba(image, alpha)."""
+        import torch
+        from PIL import Image
+        alpha = AlphaMode() if alpha is None else alpha
+        dev, pin_out = self._rgba_on_device(image)
+        h, w, _ = dev.shape
+        planes, colours, key = self.apply_dithering_frames_indexed_alpha(dev, alpha)
+        host_out = pin_out[:h * w]
+        host_out.view(h, w).copy_(planes, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out = Image.frombytes("P", (w, h), host_out.numpy())
+        out.putpalette(colours.reshape(-1).tolist(), "RGB")
+        out.info["transparency"] = key
+        return out
+
+    def _apply_dithering_png_alpha(self, image, alpha, seg_bytes, blocks, assemble) -> bytes:
+        from . import png
+        dev, _ = self._rgba_on_device(image)
+        planes, colours, key = self.apply_dithering_frames_indexed_alpha(dev, alpha)
+        return png.encode_png(planes, colours, seg_bytes, blocks=blocks, assemble=assemble, transparent=key)[0]
+
+    def apply_dithering_png(self, image, seg_bytes=None, blocks="fixed", assemble="host", *, alpha=None) -> bytes:
         """PIL image -> the bytes of a PNG-8 file whose decoding equals apply_dithering(image), exactly.  Host-in as
         apply_dithering_indexed; the index plane never comes back: it is compressed where it lies (png.encode_png: the
         zlib stream on the device, the container and its CRCs in Python) and only the compressed stream crosses to the
         host.  assemble="device": the container and its CRCs on the device as well (png.encode_png).  ValueError above
-        256 colours."""
+        256 colours.  alpha=AlphaMode(...) (keyword only): the image's alpha channel is honoured -- a PNG-8 with a tRNS chunk whose
+        decoding equals apply_dithering_rgba(image, alpha) (at most 255 colours); without it the alpha channel is dropped as before."""
         from . import png
+        if alpha is not None:
+            return self._apply_dithering_png_alpha(image, alpha, seg_bytes, blocks, assemble)
         rgb = image if image.mode == "RGB" else image.convert("RGB")
         w, h = rgb.size
         if w < 1 or h < 1:

@@ -8,7 +8,10 @@ uncompressed on the host, and the planes never leave the GPU.
 
 What a file is: the signature, IHDR (colour type 3, bit depth backend.png_depth(K): 1, 2, 4 or 8, no interlace), PLTE with
 exactly K entries, the stream in IDAT chunks of at most IDAT_BYTES, IEND.  Every row has filter 0.  No ancillary chunk: no
-tRNS, no gamma, no text.  Decoding gives palette[plane], exactly.
+gamma, no text, and no tRNS unless it is asked for.  Decoding gives palette[plane], exactly.
+transparent=T (keyword only, default None): palette entry T is fully transparent -- a tRNS chunk of T bytes of 255 and one 0
+follows PLTE (the entries behind T are opaque by the format's default); the palette must have more than T entries.  Without the
+keyword the files are what they were, byte for byte.
 
 Chunk CRCs are zlib.crc32 on the host, over the compressed bytes: a fraction of the plane (tools/bench_scripts/png_encode.py
 times it beside the kernels).  One size read-back and one block copy per call, as gif.GifWriter does.
@@ -47,14 +50,25 @@ def chunk(kind, data):
     return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)) & 0xFFFFFFFF)
 
 
-def container(width, height, depth, palette, stream, idat_bytes=IDAT_BYTES):
-    """The file around one zlib stream: signature, IHDR, PLTE, IDAT ..., IEND."""
+def _transparent(transparent, n_colours):
+    """The tRNS chunk of a key index (b"" for None); ValueError unless the palette has the entry."""
+    if transparent is None:
+        return b""
+    if isinstance(transparent, bool) or not isinstance(transparent, (int, np.integer)) or not 0 <= transparent < n_colours:
+        raise ValueError(f"transparent must be None or the index of a palette entry (0 ... {n_colours - 1}), not {transparent!r}")
+    return chunk(b"tRNS", b"\xff" * int(transparent) + b"\x00")
+
+
+def container(width, height, depth, palette, stream, idat_bytes=IDAT_BYTES, *, transparent=None):
+    """The file around one zlib stream: signature, IHDR, PLTE, (tRNS,) IDAT ..., IEND."""
     pal = _palette(palette)
     if not (1 <= int(width) < 2 ** 31 and 1 <= int(height) < 2 ** 31):
         raise ValueError("a PNG is 1 ... 2^31 - 1 pixels wide and high")
     if depth not in (1, 2, 4, 8) or pal.shape[0] > (1 << depth):
         raise ValueError(f"bit depth {depth!r} does not hold a palette of {pal.shape[0]}")
     parts = [PNG_SIGNATURE, chunk(b"IHDR", struct.pack(">IIBBBBB", int(width), int(height), depth, 3, 0, 0, 0)), chunk(b"PLTE", pal.tobytes())]
+    if transparent is not None:
+        parts.append(_transparent(transparent, pal.shape[0]))
     for a in range(0, max(len(stream), 1), int(idat_bytes)):
         parts.append(chunk(b"IDAT", stream[a:a + int(idat_bytes)]))
     parts.append(chunk(b"IEND", b""))
@@ -109,13 +123,13 @@ def _check_assemble(assemble, encoder):
         raise ValueError("assemble='device' builds the files on the GPU: it needs encoder='device'")
 
 
-def _files_on_device(planes, pal, depth, seg_bytes, blocks):
-    """The files of encode_png, assembled on the GPU: prefix = signature, IHDR, PLTE; one IDAT chunk; suffix = IEND."""
+def _files_on_device(planes, pal, depth, seg_bytes, blocks, transparent=None):
+    """The files of encode_png, assembled on the GPU: prefix = signature, IHDR, PLTE (, tRNS); one IDAT chunk; suffix = IEND."""
     from . import backend
     if blocks not in backend.PNG_BLOCKS:
         raise ValueError(f"blocks must be one of {backend.PNG_BLOCKS}, not {blocks!r}")
     p = _device_planes(planes)
-    head = container(p.shape[2], p.shape[1], depth, pal, b"")          # (checks the geometry as the host path does)
+    head = container(p.shape[2], p.shape[1], depth, pal, b"", transparent=transparent)   # (checks the geometry as the host path does)
     pre = head[:len(head) - 24]                                        # without the empty IDAT (12 bytes) and IEND (12)
     files = []
     for a in range(0, p.shape[0], backend.PNG_MAX_FRAMES):
@@ -127,26 +141,28 @@ def _files_on_device(planes, pal, depth, seg_bytes, blocks):
     return files
 
 
-def encode_png(planes, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
+def encode_png(planes, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host", *, transparent=None):
     """Index planes [N,H,W] (or [H,W]) and their palette [K,3] -> [the bytes of a PNG file per plane].  ValueError: more than
     256 colours, planes that are not one-byte indices, planes that are not on the GPU for the device encoder (or are, for
     the host encoder), a `blocks` outside backend.PNG_BLOCKS.  An index >= K is the caller's error (a decoder will show
     whatever entry its low bits name, or refuse the file).  blocks="dynamic" adds dynamic-Huffman blocks: smaller files that
     decode to the same pixels (include/ditherpie_hip_png_dyn.h).  assemble="device": chunk CRCs and the files themselves on
-    the GPU (include/ditherpie_hip_png_file.h), one IDAT chunk per file; refused with encoder="host"."""
+    the GPU (include/ditherpie_hip_png_file.h), one IDAT chunk per file; refused with encoder="host".  transparent=T: a tRNS
+    chunk that makes palette entry T transparent (ValueError unless the palette has more than T entries)."""
     from . import backend
     _check_assemble(assemble, encoder)
     pal = _palette(palette)
+    _transparent(transparent, pal.shape[0])
     depth = backend.png_depth(pal.shape[0])
     if assemble == "device":
-        return _files_on_device(planes, pal, depth, seg_bytes, blocks)
+        return _files_on_device(planes, pal, depth, seg_bytes, blocks, transparent)
     streams, shape = _streams(planes, depth, seg_bytes, encoder, blocks)
-    return [container(shape[2], shape[1], depth, pal, s) for s in streams]
+    return [container(shape[2], shape[1], depth, pal, s, transparent=transparent) for s in streams]
 
 
-def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
+def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fixed", assemble="host", *, transparent=None):
     """One plane [H,W] (or [1,H,W]) as a PNG file -> the number of bytes written."""
-    files = encode_png(plane, palette, seg_bytes, encoder, blocks, assemble)
+    files = encode_png(plane, palette, seg_bytes, encoder, blocks, assemble, transparent=transparent)
     if len(files) != 1:
         raise ValueError(f"write_png takes one plane, not {len(files)}: write_png_sequence writes several")
     with open(path, "wb") as f:
@@ -154,11 +170,11 @@ def write_png(path, plane, palette, seg_bytes=None, encoder="device", blocks="fi
     return len(files[0])
 
 
-def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device", blocks="fixed", assemble="host"):
+def write_png_sequence(pattern, planes, palette, start=1, seg_bytes=None, encoder="device", blocks="fixed", assemble="host", *, transparent=None):
     """Planes [N,H,W] as the files pattern % start, pattern % (start + 1), ... (the 'frame_%05d.png' of a frame
     directory) -> the list of paths written."""
     paths = []
-    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder, blocks, assemble)):
+    for k, data in enumerate(encode_png(planes, palette, seg_bytes, encoder, blocks, assemble, transparent=transparent)):
         path = str(pattern) % (int(start) + k)
         with open(path, "wb") as f:
             f.write(data)
